@@ -112,6 +112,37 @@ def pmc_passes(args, W, H):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_SURFELS_MAX = 700_000  # 80-byte records + their float64 index: 61.6 MB, under 64 MB with the frame result
+
+
+def frame_outputs(r, surfels):
+    """What a caller of the timed path receives for its last frame: the FrameResult (pose, tracker result) and the surfel map,
+    as float32 / float64 arrays.  A map larger than DUMP_SURFELS_MAX records is sampled at fixed, seeded indices."""
+    idx = np.arange(len(surfels), dtype=np.int64)
+    if len(idx) > DUMP_SURFELS_MAX:
+        idx = np.sort(np.random.default_rng(20260929).choice(len(idx), DUMP_SURFELS_MAX, replace=False))
+    t = r.track
+    out = {
+        "pose": np.array(r.pose, np.float32).reshape(4, 4),
+        "frame_scalars": np.array([r.surfels, r.tick, r.fused, r.fill_in, r.weighting, r.nid_score, r.tracking_ok, r.lost,
+                                   r.loop_ok, r.loop_constraints, r.loop_icp_error, r.loop_icp_count], np.float64),
+        "track_errors": np.array([t.lastICPError, t.lastICPCount, t.lastRGBError, t.lastRGBCount, t.lastSO3Error, t.lastSO3Count], np.float32),
+        "track_A": np.array(t.lastA, np.float64).reshape(6, 6),
+        "track_b": np.array(t.lastb, np.float64),
+        "track_iterations_run": np.array(t.iterations_run, np.float64),
+        "surfel_index": idx.astype(np.float64),
+    }
+    for f in surfels.dtype.names:
+        out["surfel_" + f] = np.ascontiguousarray(surfels[f][idx], np.float32)
+    return out
+
+
+def write_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def level0_kernel_name(names):
     """The level-0 resident kernel among rocprofv3's kernel names: `k_gn_level<ICP = true, RGB = true, P, EXIT>` with the largest P
     (pixels per thread: 3 at 640x480, levels 1 / 2 run P = 1)."""
@@ -177,7 +208,11 @@ def main():
     ap.add_argument("--time-delta", type=int, default=200,
                     help="active time window in frames (reference default 200); a small value with --loop-closure populates the INACTIVE "
                          "view on this cyclic stream, so the model-to-model tracker has correspondences")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step (pose, tracker result, surfel map) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` with N > 1 and no launcher around it: start N ranks (one per GPU, RCCL) ourselves
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -339,6 +374,8 @@ def main():
     elapsed = time.perf_counter() - t0
     res = ef.fetch(stream)
     M = int(res.surfels)
+    # (before anything else runs on this engine: the kernel-timing passes below go on with it)
+    dumped = frame_outputs(res, ef.globalModel().downloadMap()) if args.dump_outputs and rank == 0 else None
 
     elapsed = collab.max_over_ranks(elapsed, dev)  # the slowest rank defines the job time
     M_total = int(collab.sum_over_ranks(M, dev))
@@ -438,6 +475,9 @@ def main():
             ag1 = ns.exchange_time()
             rs = fusion.FrameResult()
             capi.check(fusion.lib.dms_fusion_fetch(capi.lib.dms_session_camera(ns.h, rank), C.byref(rs), st_s), "dms_fusion_fetch")
+            if args.dump_outputs and rank == 0:  # this loop is the headline: its camera's last frame and map are what was timed
+                cam_map = fusion.GlobalModel(W, H, handle=fusion.lib.dms_fusion_model(capi.lib.dms_session_camera(ns.h, rank)))
+                dumped = frame_outputs(rs, cam_map.downloadMap())
             el_s = collab.max_over_ranks(el_s, dev)
             ag_ms = (ag1[0] - ag0[0]) / max(1, ag1[1] - ag0[1]) if tr is not None else 0.0
             sess.update(elapsed=el_s, t_enq=t_enq_s, surfels=int(rs.surfels), surfels_total=int(collab.sum_over_ranks(int(rs.surfels), dev)),
@@ -454,6 +494,8 @@ def main():
             headline_loop = "dms_session_step_async over %s" % ("dms_transport_rccl" if tmode == "rccl" else tmode)
             elapsed, t_enq, M, M_total = el_s, t_enq_s, sess["surfels"], sess["surfels_total"]
         sess_done.set()
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped)
     rank_devices = [{"rank": rank, "device": local_rank, "name": torch.cuda.get_device_name(dev)}]
     if distributed:
         gathered = [None] * world

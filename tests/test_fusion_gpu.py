@@ -1633,7 +1633,7 @@ for c in (0, 1):
     assert got == ref[c], "camera %d differs" % c
 print("UNCHAINED_OK")
 '''
-    env = dict(os.environ, DMS_PERSIST_UNCHAINED="1", DMS_PERSIST_MAX_BLOCKS="120", GPU_MAX_HW_QUEUES="8",
+    env = dict(os.environ, DMS_PERSIST_UNCHAINED="1", DMS_PERSIST_MAX_BLOCKS="120",
                PYTHONPATH=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0 and "UNCHAINED_OK" in p.stdout, p.stdout[-2000:] + p.stderr[-3000:]
