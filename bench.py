@@ -18,6 +18,10 @@ The round-3 exchange (collab.InterMapMatcher over torch.distributed) runs first 
 fall-back leg: it becomes the headline only if the session loop cannot be set up or does not finish.
 `--session-loop` runs the same loop at N = 1 (a one-rank RCCL communicator carries the collectives).
 
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  `--full` adds every pass after the
+timed region that is not part of `value`: the "full" step, the other configurations, the session legs, per-kernel timings with the
+roofline and its nested PMC passes, and the CPU baseline (each of them can still be skipped with its --no-* option).
+
 Prints ONE JSON line on rank 0 (see DESIGN.md §Measurement for every field).
 """
 import argparse
@@ -38,7 +42,7 @@ CLOCK_GHZ = 2.4        # shader clock (MI355X_MICROARCH.md)
 
 def pmc_passes(args, W, H):
     """HBM traffic and vector-ALU activity of the level-0 tracker kernel from hardware counters of THIS build: three nested
-    `rocprofv3 --kernel-trace --pmc ...` runs of this script (20 steps; FETCH_SIZE and WRITE_SIZE do not fit one pass,
+    `rocprofv3 --kernel-trace --pmc ...` plain runs of this script (20 steps; FETCH_SIZE and WRITE_SIZE do not fit one pass,
     MI355X_MICROARCH.md "rocprofv3 PMC slots").  Returns None when rocprofv3 is not there or a pass fails."""
     import csv
     import glob
@@ -193,6 +197,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every pass that is not part of it (other legs, per-kernel timings and roofline, CPU baseline); "
+                         "the --no-* options below skip single ones of them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-pass", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the nested rocprofv3 counter passes (HBM traffic and VALU activity of the dominant kernel)")
@@ -200,7 +207,7 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=0, help="frames of the CPU baseline sample (0 = auto ~20 s)")
     ap.add_argument("--loop-closure", action="store_true",
                     help="time the 'full' frame step: local loop closure on (INACTIVE prediction + model-to-model tracking every frame)")
-    ap.add_argument("--no-full-leg", action="store_true", help="skip the extra 'full' (loop closure on) leg of the default run")
+    ap.add_argument("--no-full-leg", action="store_true", help="skip the extra 'full' (loop closure on) leg of a --full run")
     ap.add_argument("--no-config-legs", action="store_true", help="skip the short legs for BASELINE configs 2 / 4, n_pred = 3 and the populated full step")
     ap.add_argument("--no-session-leg", action="store_true", help="skip the collaborative-session leg (dms_session: two cameras, a merge by the reference's rule)")
     ap.add_argument("--session-loop", action="store_true",
@@ -568,7 +575,7 @@ def main():
                           "what": "SURVEY 8(d)'s algorithmic bytes of one frame (this run's surfel count, the 2 predictions actually run) x frames/s per GPU / 8 TB/s"}
 
     # ---- "full" frame step (report both): the same stream with local loop closure on ----
-    if rank == 0 and not distributed and not args.loop_closure and not args.no_full_leg:
+    if args.full and rank == 0 and not distributed and not args.loop_closure and not args.no_full_leg:
         ef_main = ef
         ef = make_engine(True)
         nfull = min(args.steps, 100)
@@ -599,7 +606,7 @@ def main():
     # ---- the other single-GPU configurations of BASELINE.json / SURVEY 8(d), short legs of their own (not in `value`) ----------
     # Each: a fresh engine, `warmup` untimed frames, then `n` frames timed like the main region (enqueue, one synchronise);
     # `hbm_frac_whole_frame` = SURVEY 8(d)'s contract bytes per frame B x frames/s / 8 TB/s with the leg's own surfel count.
-    if rank == 0 and not distributed and not args.loop_closure and not args.no_config_legs and (W, H) == (640, 480):
+    if args.full and rank == 0 and not distributed and not args.loop_closure and not args.no_config_legs and (W, H) == (640, 480):
         def leg(opts, what, it, rgb, n_pred, n_trk, Wl=W, Hl=H, Kl=K, n=50):
             if (Wl, Hl) == (W, H):
                 rl, dl, nu = rgb_t, dep_t, n_unique
@@ -658,7 +665,7 @@ def main():
     # the reference's rule verifies, the matched map's owner refines at full resolution (ReferenceFrame.h:72-110) and consumes the
     # other map; from then on both cameras track against and fuse into ONE map.  Timed per tick with the host in the loop (the session
     # synchronises where the reference does): before the merge, the merge tick itself, after it.  Not part of `value`.
-    if rank == 0 and not distributed and not args.loop_closure and not args.no_session_leg and (W, H) == (640, 480):
+    if args.full and rank == 0 and not distributed and not args.loop_closure and not args.no_session_leg and (W, H) == (640, 480):
         from densemonoslam_amd import session as session_mod
 
         n_ticks, q_from, off = 22, 6, 8
@@ -765,7 +772,7 @@ def main():
             }
         capi_mod.destroy_stream(st)
 
-    # The same session ACROSS ranks (with --gpus N; DMS_BENCH_SESSION=0 skips it, =1 also runs it over gloo): one camera per rank, camera r eight frames ahead of
+    # The same session ACROSS ranks (with --full --gpus N; DMS_BENCH_SESSION=0 skips it, =1 also runs it over gloo): one camera per rank, camera r eight frames ahead of
     # camera r - 1 on the corner path, RCCL transport (dms_transport_rccl) - or gloo through ctypes callbacks in the one-GPU rehearsal.
     # Cameras migrate to the consuming rank as their maps merge; rank 0 reports the per-tick times and the merge log.  Not part of
     # `value`; every rank takes part (the session's collectives).
@@ -874,7 +881,7 @@ def main():
         capi_mod.destroy_stream(st)
 
     sess_env = os.environ.get("DMS_BENCH_SESSION", "")
-    if distributed and (W, H) == (640, 480) and not args.loop_closure and (sess_env == "1" or (sess_env != "0" and backend == "nccl")):
+    if args.full and distributed and (W, H) == (640, 480) and not args.loop_closure and (sess_env == "1" or (sess_env != "0" and backend == "nccl")):
         import threading
 
         limit_s = int(os.environ.get("DMS_BENCH_SESSION_LIMIT", "180"))
@@ -902,7 +909,7 @@ def main():
         timer.cancel()
 
     # ---- per-kernel timing with HIP events on the launch stream (own passes, not in `value`) ------
-    if rank == 0 and not args.no_kernel_pass:
+    if args.full and rank == 0 and not args.no_kernel_pass:
         od = fusion.lib.dms_fusion_odometry(ef.h)
         nprof = min(args.steps, 20)
         next_frame = [n_total]
@@ -1077,7 +1084,7 @@ def main():
             }
 
     # ---- CPU baseline: the oracle (a port of the reference algorithm) on the host cores -----------
-    if rank == 0 and not distributed and not args.no_cpu_baseline:  # reported at N = 1 only
+    if args.full and rank == 0 and not distributed and not args.no_cpu_baseline:  # reported at N = 1 only
         from oracle import orc_pipeline  # checker / baseline only
 
         from oracle import orc as _orc
@@ -1143,7 +1150,7 @@ def main():
                       "(host.cpu_quota_cores), and threads beyond the quota only add barrier time - measured on such a host "
                       "(profiles/r05_cpu_baseline_threads.jsonl): 0.71 / 3.1 / 4.6 / 4.8 / 3.4 / 1.8 / 0.07 frames/s at 1 / 8 / 16 / 32 / 64 / 128 / 256 "
                       "threads; sixteen independent 16-thread cameras at once deliver 3.5 - 5.6 frames/s in aggregate (profiles/r05_cpu_sixteen_replicas.txt, DESIGN.md 6).  ~100 frames keep "
-                      "the default run inside its time budget.  A restatement written to be checked against, not tuned: it says nothing about kernel "
+                      "a --full run inside its time budget.  A restatement written to be checked against, not tuned: it says nothing about kernel "
                       "quality; one_core: the same with 1 thread for ~8 s.  Non-target" % (n_all, W, H, cores, nproc, nproc, ("%g" % quota) if quota else "no"),
         }
 

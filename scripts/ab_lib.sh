@@ -5,7 +5,7 @@ summ='import sys,json; j=json.loads(sys.stdin.read().strip().split(chr(10))[-1])
 for r in $(seq $reps); do
   for lib in "$@"; do
     d=$(DMS_LIB_PATH=$PWD/$lib python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-kernel-pass --no-full-leg --no-pmc --no-config-legs --no-session-leg 2>/dev/null | python -c "$summ")
-    l=$(DMS_LIB_PATH=$PWD/$lib python bench.py --steps 300 --warmup 20 --no-cpu-baseline --no-full-leg --no-pmc --no-config-legs --no-session-leg 2>/dev/null | python -c "$summ")
+    l=$(DMS_LIB_PATH=$PWD/$lib python bench.py --full --steps 300 --warmup 20 --no-cpu-baseline --no-full-leg --no-pmc --no-config-legs --no-session-leg 2>/dev/null | python -c "$summ")
     echo "$lib -> driver $d | 300 steps $l"
   done
 done

@@ -2,7 +2,7 @@
 # phase clocks of the level kernels for a list of environment settings: scripts/r06_phases.sh "ENV=a" "ENV=b" ...
 export PYTHONPATH=$PWD
 for v in "$@"; do
-  env $v python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-full-leg --no-pmc --no-config-legs --no-session-leg 2>/dev/null | python -c "
+  env $v python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-full-leg --no-pmc --no-config-legs --no-session-leg 2>/dev/null | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):
