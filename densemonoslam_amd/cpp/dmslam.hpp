@@ -16,11 +16,13 @@
 #pragma once
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/dmslam.h"
 #include "../../include/dmslam_ferns.h"
 #include "../../include/dmslam_fusion.h"
+#include "../../include/dmslam_render.h"
 
 namespace dms {
 
@@ -144,6 +146,48 @@ class GlobalModel {
       if (c == cluster) return true;
     return false;
   }
+  // The framebuffer the draw goes into (the reference draws into whatever GL framebuffer is bound): a dms_render_target, cleared by
+  // the host (dms_render_clear) as the GUI clears its view, and the stream the draws are enqueued on.
+  void bindRenderTarget(dms_render_target* t, dms_stream s = nullptr) {
+    target = t;
+    target_stream = s;
+  }
+  // GlobalModel::renderPointCloud (GlobalModel.cpp:419-505): the reference's arguments in the reference's order; mvp is row-major
+  // (pangolin's OpenGlMatrix is column-major: transpose it, e.g. with transposed16).  colorType precedence of :436-440, one draw per
+  // cluster into the bound target (:458-503), cluster_colors[i] for clusters[i] when drawClusters.
+  void renderPointCloud(const float* mvp16, const float threshold, const bool drawUnstable, const bool drawNormals, const bool drawColors,
+                        const bool drawPoints, const bool drawWindow, const bool drawTimes, const bool drawContributions, const int time,
+                        const int timeIdx, const int timeDelta, std::vector<int> clusters, bool drawClusters,
+                        std::vector<std::tuple<float, float, float>> cluster_colors) {
+    if (!target) throw std::runtime_error("renderPointCloud: no render target bound (bindRenderTarget)");
+    dms_render_params p = {};
+    for (int k = 0; k < 16; ++k) p.mvp[k] = mvp16[k];
+    p.threshold = threshold;
+    p.draw_unstable = drawUnstable;
+    p.draw_points = drawPoints;
+    p.draw_window = drawWindow;
+    p.color_type = drawContributions ? 4 : drawNormals ? 1 : drawColors ? 2 : drawTimes ? 3 : 0;
+    p.time = time;
+    p.time_idx = timeIdx;
+    p.time_delta = timeDelta;
+    p.use_cluster_color = drawClusters;
+    for (size_t i = 0; i < clusters.size(); i++) {
+      if (drawClusters) {
+        p.cluster_color[0] = std::get<0>(cluster_colors[i]);
+        p.cluster_color[1] = std::get<1>(cluster_colors[i]);
+        p.cluster_color[2] = std::get<2>(cluster_colors[i]);
+      }
+      dms_model* m = ctx ? dms_fusion_cluster_model(ctx, clusters[i]) : (clusters[i] == 0 ? h : nullptr);
+      if (!m) continue;  // a cluster without buffers draws nothing
+      check(dms_render_draw(target, m, &p, target_stream), "renderPointCloud");
+    }
+  }
+  static void transposed16(const double* column_major16, float* row_major16) {
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 4; ++c) row_major16[4 * r + c] = (float)column_major16[4 * c + r];
+  }
+  dms_render_target* target = nullptr;
+  dms_stream target_stream = nullptr;
   dms_model* h = nullptr;
   dms_fusion* ctx = nullptr;
 

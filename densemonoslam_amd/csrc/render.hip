@@ -1,0 +1,632 @@
+// G14 (draw): GlobalModel::renderPointCloud (GlobalModel.cpp:419-505) — the surfel map drawn from any viewpoint into a
+// render target, with the programs draw_global_surface.{vert,geom,frag} (discs) and draw_feedback.{vert,frag} (points).
+//
+// The same two-pass shape as the splat prediction (fusion_map.hip):
+//   pass 1, per surfel: vertex + geometry stage, rasterise the footprint (two triangles of the geometry stage's strip, or
+//           one pixel for a point), compete per pixel with a 64-bit atomicMin on
+//           key = depth24 << 40 | draw_seq << 32 | surfel id;
+//   pass 2, per pixel: a pixel whose winner belongs to this draw gets its colour and depth written.
+// GL_LESS with "the earlier primitive / draw wins a tie" is "the smallest key wins", across several draws into one target.
+// The rules OpenGL leaves open (coverage, interpolation, clipping, colour and depth conversion) are DESIGN §4 R6-R10, and
+// tests/render_ref.py restates them on the CPU.
+#include "surfel.hpp"
+#include "../../include/dmslam_render.h"
+
+using namespace dms;
+
+struct dms_render_target {
+  int width = 0, height = 0;
+  unsigned long long* key = nullptr;  // [H][W] row-major (window rows: row 0 at the bottom)
+  unsigned* color = nullptr;          // RGBA8
+  unsigned* depth = nullptr;          // 24-bit depth in the low bits
+  unsigned* clip_flag = nullptr;      // draw_seq + 1 of the last draw that met a surfel to clip (R8)
+  int seq = 0;                        // draws since the last clear
+};
+
+namespace dms {
+namespace {
+
+constexpr int kSub = 256;        // R6: window coordinates snapped to 1/256 px
+constexpr float kGuard = 255.f;  // R8: guard band |x|, |y| <= 255 w (window coordinates within 2^20 px, snapped within 2^28)
+constexpr int kSeg = 32;         // pixels of a footprint row one lane rasterises
+
+struct RenderArgs {
+  float mvp[16];
+  const float* pose_dev;  // camera-to-world in HBM: mvp is then the projection and the view is built on the device
+  int W, H;
+  float hw, hh;  // W / 2, H / 2
+  float threshold;
+  int unstable, window, colorType, time, timeIdx, timeDelta, cluster;
+  float cc[3];
+  unsigned seq;
+};
+
+// clip = M (p, 1), row by row, accumulated left to right
+struct c4 {
+  float x, y, z, w;
+};
+__device__ __forceinline__ c4 clip_of(const float* M, float x, float y, float z) {
+  c4 r;
+  r.x = ((M[0] * x + M[1] * y) + M[2] * z) + M[3];
+  r.y = ((M[4] * x + M[5] * y) + M[6] * z) + M[7];
+  r.z = ((M[8] * x + M[9] * y) + M[10] * z) + M[11];
+  r.w = ((M[12] * x + M[13] * y) + M[14] * z) + M[15];
+  return r;
+}
+
+// dmslam_render.h, dms_render_mvp_from_pose: P * F * inverse(pose), F = diag(1, -1, -1, 1) (right-down-forward camera to
+// right-up-back), the rigid inverse [R^T | -R^T t] and both products accumulated left to right
+__host__ __device__ inline void mvp_from_pose(const float* P, const float* T, float* out) {
+  float V[16];
+  for (int r = 0; r < 3; ++r) {
+    const float sg = r == 0 ? 1.f : -1.f;
+    V[4 * r + 0] = sg * T[0 + r];
+    V[4 * r + 1] = sg * T[4 + r];
+    V[4 * r + 2] = sg * T[8 + r];
+    V[4 * r + 3] = sg * -((T[0 + r] * T[3] + T[4 + r] * T[7]) + T[8 + r] * T[11]);
+  }
+  V[12] = V[13] = V[14] = 0.f;
+  V[15] = 1.f;
+  for (int r = 0; r < 4; ++r)
+    for (int c = 0; c < 4; ++c) out[4 * r + c] = ((P[4 * r] * V[c] + P[4 * r + 1] * V[4 + c]) + P[4 * r + 2] * V[8 + c]) + P[4 * r + 3] * V[12 + c];
+}
+
+// the effective clip-from-world matrix of the launch
+__device__ __forceinline__ void launch_mvp(const RenderArgs& a, float* M) {
+  if (a.pose_dev) {
+    float pose[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) pose[k] = a.pose_dev[k];
+    mvp_from_pose(a.mvp, pose, M);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) M[k] = a.mvp[k];
+  }
+}
+
+// ---- disc geometry (draw_global_surface.geom:185-212) -------------------------------------------------------------------
+// the four strip vertices P + x, P + y, P - y, P - x in clip space; texcoords (-1,-1) (1,-1) (-1,1) (1,1)
+__device__ __forceinline__ void disc_corners(const float* M, const float4& pc, const float4& nr, c4* v) {
+  const f3 xn = normalized3(mk3(nr.y - nr.z, -nr.x, nr.x));
+  const f3 x = mk3((xn.x * nr.w) * 1.41421356f, (xn.y * nr.w) * 1.41421356f, (xn.z * nr.w) * 1.41421356f);
+  const f3 y = cross3(mk3(nr.x, nr.y, nr.z), x);
+  v[0] = clip_of(M, pc.x + x.x, pc.y + x.y, pc.z + x.z);
+  v[1] = clip_of(M, pc.x + y.x, pc.y + y.y, pc.z + y.z);
+  v[2] = clip_of(M, pc.x - y.x, pc.y - y.y, pc.z - y.z);
+  v[3] = clip_of(M, pc.x - x.x, pc.y - x.y, pc.z - x.z);
+}
+
+// R8 plane distances: near z >= -w, then the guard band
+__device__ __forceinline__ float plane_dist(const c4& v, int k) {
+  const float gw = kGuard * v.w;
+  return k == 0 ? v.z + v.w : k == 1 ? gw - v.x : k == 2 ? gw + v.x : k == 3 ? gw - v.y : gw + v.y;
+}
+__device__ __forceinline__ unsigned outcode(const c4& v) {
+  unsigned o = 0;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) o |= (plane_dist(v, k) >= 0.f ? 0u : 1u) << k;
+  return o;
+}
+
+// a window-space vertex: snapped position, window depth, 1/w, texcoord
+struct WV {
+  int X, Y;
+  float z, iw, u, v;
+};
+__device__ __forceinline__ WV to_window(const RenderArgs& a, const c4& c, float u, float v) {
+  WV r;
+  const float xn = c.x / c.w, yn = c.y / c.w, zn = c.z / c.w;
+  r.X = (int)rintf(((xn + 1.f) * a.hw) * (float)kSub);
+  r.Y = (int)rintf(((yn + 1.f) * a.hh) * (float)kSub);
+  r.z = zn * 0.5f + 0.5f;
+  r.iw = 1.f / c.w;
+  r.u = u;
+  r.v = v;
+  return r;
+}
+
+// pixel rows / columns whose centres lie in [lo, hi] (snapped units)
+__device__ __forceinline__ int first_px(int lo) { return -((kSub / 2 - lo) >> 8); }
+__device__ __forceinline__ int last_px(int hi) { return (hi - kSub / 2) >> 8; }
+
+// R6 / R7 / R10: one triangle over pixels [xa, xb] of row py
+__device__ void raster_row(WV v0, WV v1, WV v2, int py, int xa, int xb, unsigned long long key_lo, float shift, int W,
+                           unsigned long long* __restrict__ zrow) {
+  long long area = (long long)(v1.X - v0.X) * (long long)(v2.Y - v0.Y) - (long long)(v1.Y - v0.Y) * (long long)(v2.X - v0.X);
+  if (area == 0) return;
+  if (area < 0) {
+    const WV t = v1;
+    v1 = v2;
+    v2 = t;
+    area = -area;
+  }
+  // edge k is opposite vertex k: e0 = v1 -> v2, e1 = v2 -> v0, e2 = v0 -> v1
+  const int ax0 = v1.X, ay0 = v1.Y, dx0 = v2.X - v1.X, dy0 = v2.Y - v1.Y;
+  const int ax1 = v2.X, ay1 = v2.Y, dx1 = v0.X - v2.X, dy1 = v0.Y - v2.Y;
+  const int ax2 = v0.X, ay2 = v0.Y, dx2 = v1.X - v0.X, dy2 = v1.Y - v0.Y;
+  const bool tl0 = dy0 < 0 || (dy0 == 0 && dx0 < 0), tl1 = dy1 < 0 || (dy1 == 0 && dx1 < 0), tl2 = dy2 < 0 || (dy2 == 0 && dx2 < 0);
+  const long long Py = (long long)py * kSub + kSub / 2, Px = (long long)xa * kSub + kSub / 2;
+  long long e0 = (long long)dx0 * (Py - ay0) - (long long)dy0 * (Px - ax0);
+  long long e1 = (long long)dx1 * (Py - ay1) - (long long)dy1 * (Px - ax1);
+  long long e2 = (long long)dx2 * (Py - ay2) - (long long)dy2 * (Px - ax2);
+  const long long s0 = -(long long)dy0 * kSub, s1 = -(long long)dy1 * kSub, s2 = -(long long)dy2 * kSub;
+  const float inv = 1.f / (float)(double)area;
+  for (int px = xa; px <= xb; ++px, e0 += s0, e1 += s1, e2 += s2) {
+    if (!((e0 > 0 || (e0 == 0 && tl0)) && (e1 > 0 || (e1 == 0 && tl1)) && (e2 > 0 || (e2 == 0 && tl2)))) continue;
+    const float b0 = (float)(double)e0 * inv, b1 = (float)(double)e1 * inv, b2 = (float)(double)e2 * inv;
+    const float z = (b0 * v0.z + b1 * v1.z) + b2 * v2.z;
+    if (!(z >= 0.f && z <= 1.f)) continue;  // R8: nothing beyond the far (or before the near) plane
+    const float q0 = b0 * v0.iw, q1 = b1 * v1.iw, q2 = b2 * v2.iw;
+    const float den = (q0 + q1) + q2;
+    const float u = ((q0 * v0.u + q1 * v1.u) + q2 * v2.u) / den;
+    const float v = ((q0 * v0.v + q1 * v1.v) + q2 * v2.v) / den;
+    if (u * u + v * v > 1.f) continue;  // draw_global_surface.frag:30-31
+    // .frag:35-42 + R10: the shifted depth is clamped to [0, 1] before the 24-bit conversion and the test
+    const float zf = fminf(fmaxf(z + shift, 0.f), 1.f);
+    const unsigned d = depth24(zf);
+    if (d >= 0xFFFFFFu) continue;  // GL_LESS against the cleared 1.0
+    const unsigned long long key = ((unsigned long long)d << 40) | key_lo;
+    if (key < zrow[px]) atomicMin(zrow + px, key);
+  }
+}
+
+// R8: a triangle that leaves the near plane or the guard band, clipped plane by plane (Sutherland-Hodgman); each new vertex is
+// interpolated from the inside end of its edge.  Rare: kept out of line (its polygon lives in private memory).
+struct CV {
+  c4 c;
+  float u, v;
+};
+__device__ __forceinline__ int clip_polygon(CV* poly, int n) {
+  CV tmp[9];
+  for (int k = 0; k < 5 && n > 0; ++k) {
+    int m = 0;
+    for (int i = 0; i < n; ++i) {
+      const CV A = poly[i], B = poly[(i + 1) % n];
+      const float da = plane_dist(A.c, k), db = plane_dist(B.c, k);
+      const bool ia = da >= 0.f, ib = db >= 0.f;
+      if (ia) tmp[m++] = A;
+      if (ia != ib) {
+        const CV& I = ia ? A : B;
+        const CV& O = ia ? B : A;
+        const float di = ia ? da : db, dout = ia ? db : da;
+        const float t = di / (di - dout);
+        CV r;
+        r.c.x = I.c.x + t * (O.c.x - I.c.x);
+        r.c.y = I.c.y + t * (O.c.y - I.c.y);
+        r.c.z = I.c.z + t * (O.c.z - I.c.z);
+        r.c.w = I.c.w + t * (O.c.w - I.c.w);
+        r.u = I.u + t * (O.u - I.u);
+        r.v = I.v + t * (O.v - I.v);
+        tmp[m++] = r;
+      }
+    }
+    n = m;
+    for (int i = 0; i < n; ++i) poly[i] = tmp[i];
+  }
+  return n;
+}
+
+__device__ __forceinline__ void raster_clipped_row(const RenderArgs& a, const c4* cv, int py, int xa, int xb, unsigned long long key_lo,
+                                                float shift, unsigned long long* __restrict__ zrow) {
+  const float tu[4] = {-1.f, 1.f, -1.f, 1.f}, tv[4] = {-1.f, -1.f, 1.f, 1.f};
+  const int tri[2][3] = {{0, 1, 2}, {2, 1, 3}};
+  for (int t = 0; t < 2; ++t) {
+    CV poly[9];
+    for (int k = 0; k < 3; ++k) {
+      const int i = tri[t][k];
+      poly[k].c = cv[i];
+      poly[k].u = tu[i];
+      poly[k].v = tv[i];
+    }
+    const int n = clip_polygon(poly, 3);
+    if (n < 3) continue;
+    bool ok = true;
+    for (int k = 0; k < n; ++k) ok = ok && poly[k].c.w > 0.f;
+    if (!ok) continue;
+    const WV w0 = to_window(a, poly[0].c, poly[0].u, poly[0].v);
+    WV wp = to_window(a, poly[1].c, poly[1].u, poly[1].v);
+    for (int k = 2; k < n; ++k) {  // fan (0, k-1, k)
+      const WV wk = to_window(a, poly[k].c, poly[k].u, poly[k].v);
+      raster_row(w0, wp, wk, py, xa, xb, key_lo, shift, a.W, zrow);
+      wp = wk;
+    }
+  }
+}
+
+// footprint of a clipped surfel: snapped bounds of every vertex the clip produces
+__device__ __forceinline__ bool clipped_bounds(const RenderArgs& a, const c4* cv, int& X0, int& X1, int& Y0, int& Y1) {
+  const int tri[2][3] = {{0, 1, 2}, {2, 1, 3}};
+  X0 = Y0 = 0x7fffffff;
+  X1 = Y1 = -0x7fffffff;
+  bool any = false;
+  for (int t = 0; t < 2; ++t) {
+    CV poly[9];
+    for (int k = 0; k < 3; ++k) {
+      poly[k].c = cv[tri[t][k]];
+      poly[k].u = poly[k].v = 0.f;
+    }
+    const int n = clip_polygon(poly, 3);
+    if (n < 3) continue;
+    bool ok = true;
+    for (int k = 0; k < n; ++k) ok = ok && poly[k].c.w > 0.f;
+    if (!ok) continue;
+    for (int k = 0; k < n; ++k) {
+      const WV w = to_window(a, poly[k].c, 0.f, 0.f);
+      X0 = min(X0, w.X), X1 = max(X1, w.X), Y0 = min(Y0, w.Y), Y1 = max(Y1, w.Y);
+    }
+    any = true;
+  }
+  return any;
+}
+
+// Pass 1 of the disc program.  A block runs the vertex + geometry stage for 256 surfels, parks the window-space strip of each
+// in LDS, and hands out footprint row segments (up to kSeg pixels) to its threads by a prefix sum + binary search, as
+// k_splat_project does with sprite rows: a surfel that covers hundreds of pixels is spread over many lanes.
+// CLIPPED = false: the surfels whose strip lies inside every plane of R8 (nearly all); one that does not raises *clip_flag
+// (= draw_seq + 1).  CLIPPED = true (launched behind it, returns at once unless the flag was raised in this draw): the others,
+// clipped again by every row worker.  Two instances, so that the clip's registers and private arrays do not weigh on the common
+// path.
+template <bool CLIPPED>
+__global__ __launch_bounds__(256) void k_render_discs(RenderArgs a, SurfelPlanes sp, const unsigned* __restrict__ d_count,
+                                                      unsigned long long* __restrict__ zbuf, unsigned* __restrict__ clip_flag) {
+  __shared__ int s_xy[8][256];     // X0 Y0 .. X3 Y3 (snapped), or the surfel's clip-space corners are recomputed (clipped)
+  __shared__ float s_zi[8][256];   // z0 iw0 .. z3 iw3
+  __shared__ float s_shift[256];   // depth shift of an unstable surfel
+  __shared__ int s_box[4][256];    // x0, width, y0, segments per row
+  __shared__ unsigned s_off[257];  // exclusive prefix of the segment counts
+  __shared__ unsigned s_w[4];
+  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+  if (CLIPPED && *clip_flag != a.seq + 1u) return;
+  const unsigned M = d_count[0];
+  float Mv[16];
+  launch_mvp(a, Mv);
+  for (unsigned base = blockIdx.x * 256u; base < M; base += gridDim.x * 256u) {
+    const unsigned i = base + t;
+    unsigned items = 0;
+    if (i < M) {
+      const float4 pc = sp.pos[i];
+      if (pc.w > a.threshold || a.unstable == 1) {  // draw_global_surface.vert:49
+        const float4 nr = sp.nrm[i];
+        c4 cv[4];
+        disc_corners(Mv, pc, nr, cv);
+        const unsigned o0 = outcode(cv[0]), o1 = outcode(cv[1]), o2 = outcode(cv[2]), o3 = outcode(cv[3]);
+        int X0, X1, Y0, Y1;
+        bool live = false;
+        const bool clipped = (o0 | o1 | o2 | o3) != 0u;
+        if (!CLIPPED && clipped) {
+          *clip_flag = a.seq + 1u;
+        } else if (!CLIPPED) {
+          const float tu[4] = {-1.f, 1.f, -1.f, 1.f}, tv[4] = {-1.f, -1.f, 1.f, 1.f};
+          X0 = Y0 = 0x7fffffff;
+          X1 = Y1 = -0x7fffffff;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const WV w = to_window(a, cv[k], tu[k], tv[k]);
+            s_xy[2 * k][t] = w.X;
+            s_xy[2 * k + 1][t] = w.Y;
+            s_zi[2 * k][t] = w.z;
+            s_zi[2 * k + 1][t] = w.iw;
+            X0 = min(X0, w.X), X1 = max(X1, w.X), Y0 = min(Y0, w.Y), Y1 = max(Y1, w.Y);
+          }
+          live = true;
+        } else if (clipped && (o0 & o1 & o2 & o3) == 0u) {
+          live = clipped_bounds(a, cv, X0, X1, Y0, Y1);
+        }
+        if (live) {
+          const int x0 = max(first_px(X0), 0), x1 = min(last_px(X1), a.W - 1);
+          const int y0 = max(first_px(Y0), 0), y1 = min(last_px(Y1), a.H - 1);
+          if (x1 >= x0 && y1 >= y0) {
+            const int w = x1 - x0 + 1, segs = (w + kSeg - 1) / kSeg;
+            items = (unsigned)((y1 - y0 + 1) * segs);
+            s_box[0][t] = x0;
+            s_box[1][t] = w;
+            s_box[2][t] = y0;
+            s_box[3][t] = segs;
+            s_shift[t] = pc.w <= a.threshold ? nr.w : 0.f;  // .geom:183, .frag:35-42
+          }
+        }
+      }
+    }
+    unsigned incl = items;
+    for (int off = 1; off < 64; off <<= 1) {
+      const unsigned up = __shfl_up(incl, off, 64);
+      if (lane >= off) incl += up;
+    }
+    if (lane == 63) s_w[wid] = incl;
+    __syncthreads();
+    unsigned wbase = 0;
+    for (int w = 0; w < wid; ++w) wbase += s_w[w];
+    s_off[t] = wbase + incl - items;
+    if (t == 255) s_off[256] = wbase + incl;
+    __syncthreads();
+    const unsigned total = s_off[256];
+    for (unsigned u = t; u < total; u += 256u) {
+      int lo = 0, hi = 256;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int mid = (lo + hi) >> 1;
+        if (s_off[mid] <= u)
+          lo = mid;
+        else
+          hi = mid;
+      }
+      const int j = lo;
+      const unsigned r = u - s_off[j];
+      const int segs = s_box[3][j];
+      const int py = s_box[2][j] + (int)(r / (unsigned)segs);
+      const int sg = (int)(r % (unsigned)segs);
+      const int xa = s_box[0][j] + sg * kSeg, xb = min(xa + kSeg - 1, s_box[0][j] + s_box[1][j] - 1);
+      const unsigned id = base + (unsigned)j;
+      const unsigned long long key_lo = ((unsigned long long)a.seq << 32) | (unsigned long long)id;
+      const float shift = s_shift[j];
+      unsigned long long* zrow = zbuf + (size_t)py * a.W;
+      if (!CLIPPED) {
+        WV v[4];
+        const float tu[4] = {-1.f, 1.f, -1.f, 1.f}, tv[4] = {-1.f, -1.f, 1.f, 1.f};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          v[k].X = s_xy[2 * k][j];
+          v[k].Y = s_xy[2 * k + 1][j];
+          v[k].z = s_zi[2 * k][j];
+          v[k].iw = s_zi[2 * k + 1][j];
+          v[k].u = tu[k];
+          v[k].v = tv[k];
+        }
+        // GL strip order: (v0, v1, v2), (v2, v1, v3)
+        raster_row(v[0], v[1], v[2], py, xa, xb, key_lo, shift, a.W, zrow);
+        raster_row(v[2], v[1], v[3], py, xa, xb, key_lo, shift, a.W, zrow);
+      } else {
+        c4 cv[4];
+        disc_corners(Mv, sp.pos[id], sp.nrm[id], cv);
+        raster_clipped_row(a, cv, py, xa, xb, key_lo, shift, zrow);
+      }
+    }
+    __syncthreads();  // the tables are rewritten by the next chunk
+  }
+}
+
+// Pass 1 of the point program (draw_feedback.vert:47-72): one size-1 point per surfel with conf > threshold, placed by R2
+__global__ __launch_bounds__(256) void k_render_points(RenderArgs a, SurfelPlanes sp, const unsigned* __restrict__ d_count,
+                                                       unsigned long long* __restrict__ zbuf) {
+  const unsigned M = d_count[0];
+  float Mv[16];
+  launch_mvp(a, Mv);
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += blockDim.x * gridDim.x) {
+    const float4 pc = sp.pos[i];
+    if (!(pc.w > a.threshold)) continue;
+    const c4 c = clip_of(Mv, pc.x, pc.y, pc.z);
+    if (!(c.w > 0.f)) continue;
+    const float xn = c.x / c.w, yn = c.y / c.w, zn = c.z / c.w;
+    if (!(xn >= -1.f && xn <= 1.f && yn >= -1.f && yn <= 1.f && zn >= -1.f && zn <= 1.f)) continue;
+    const int px = (int)floorf((xn + 1.f) * a.hw), py = (int)floorf((yn + 1.f) * a.hh);
+    if (px < 0 || py < 0 || px >= a.W || py >= a.H) continue;
+    const unsigned d = depth24(zn * 0.5f + 0.5f);
+    if (d >= 0xFFFFFFu) continue;
+    const unsigned long long key = ((unsigned long long)d << 40) | ((unsigned long long)a.seq << 32) | (unsigned long long)i;
+    unsigned long long* cell = zbuf + (size_t)py * a.W + px;
+    if (key < *cell) atomicMin(cell, key);
+  }
+}
+
+// R9 (a channel that is not finite writes 0, as llvmpipe does: tests/golden/ref_render.npz)
+__device__ __forceinline__ unsigned unorm8(float v) { return isfinite(v) ? (unsigned)floorf(fminf(fmaxf(v, 0.f), 1.f) * 255.f + 0.5f) : 0u; }
+__device__ __forceinline__ unsigned rgba8(const f3& c) { return unorm8(c.x) | (unorm8(c.y) << 8) | (unorm8(c.z) << 16) | (255u << 24); }
+__device__ __forceinline__ f3 shaded_grey(const float4& nr) {  // (.5 * |dot(n, 1)|) + .1
+  const float s = fabsf((nr.x + nr.y) + nr.z);
+  return mk3(0.5f * s + 0.1f, 0.5f * s + 0.1f, 0.5f * s + 0.1f);
+}
+
+// the colour of a winning surfel: draw_global_surface.geom:123-181 (discs) or draw_feedback.vert:297-314 (points)
+template <bool POINTS>
+__device__ __forceinline__ f3 surfel_colour(const RenderArgs& a, const SurfelPlanes& sp, size_t cap, unsigned i) {
+  // each plane only where a mode reads it: the cluster colour reads none, normals / ramp / contributions / grey the normal,
+  // decoded colour and ramp the colour plane, contributions and the window the time planes
+  f3 c;
+  if (a.cluster) {
+    c = mk3(a.cc[0], a.cc[1], a.cc[2]);
+  } else if (a.colorType == 1) {
+    const float4 nr = sp.nrm[i];
+    c = mk3(nr.x, nr.y, nr.z);
+  } else if (a.colorType == 2) {
+    c = decode_color(sp.col[i].x);
+  } else if (!POINTS && a.colorType == 3) {
+    const float4 nr = sp.nrm[i];
+    const float ratio = (2.f * (sp.col[i].z - 1.f)) / ((float)a.time - 1.f);
+    const float x = fmaxf(0.f, 1.f - ratio), y = fmaxf(0.f, ratio - 1.f), z = (1.f - x) - y;
+    const float s = fabsf((nr.x + nr.y) + nr.z) + 0.1f;
+    c = mk3(x * s, y * s, z * s);
+  } else if (!POINTS && a.colorType == 4) {
+    const float4 nr = sp.nrm[i];
+    const bool s0 = sp.times[i] != -3.f, s1 = sp.times[cap + i] != -3.f, s2 = sp.times[2 * cap + i] != -3.f;
+    const float g = ((s0 ? 0.0f : 0.0f) + (s1 ? 0.8f : 0.0f)) + (s2 ? 0.0f : 0.0f);
+    const float r = ((s0 ? 0.0f : 0.0f) + (s1 ? 0.1f : 0.0f)) + (s2 ? 0.8f : 0.0f);
+    const float b = ((s0 ? 0.8f : 0.0f) + (s1 ? 0.2f : 0.0f)) + (s2 ? 0.0f : 0.0f);
+    const float total = (float)((s0 ? 1 : 0) + (s1 ? 1 : 0) + (s2 ? 1 : 0));
+    const float s = fabsf((nr.x + nr.y) + nr.z);
+    c = mk3((r / total) * s + 0.1f, (g / total) * s + 0.1f, (b / total) * s + 0.1f);
+  } else {
+    c = shaded_grey(sp.nrm[i]);
+  }
+  if (!POINTS && a.window == 1) {  // .geom:173-182
+    const float dt = (float)a.time - sp.times[(size_t)a.timeIdx * cap + i];
+    if (dt > (float)a.timeDelta) c = mk3(c.x * 0.25f, c.y * 0.25f, c.z * 0.25f);
+    if (dt < (float)a.timeDelta) c = mk3(c.x * 0.f, c.y * 1.f, c.z * 0.f);
+  }
+  return c;
+}
+
+// Pass 2: the pixels this draw won get their colour and depth; the rest keep what earlier draws (or the clear) left
+template <bool POINTS>
+__global__ __launch_bounds__(256) void k_render_resolve(RenderArgs a, SurfelPlanes sp, size_t cap, const unsigned long long* __restrict__ zbuf,
+                                                        unsigned* __restrict__ color, unsigned* __restrict__ depth) {
+  const int n = a.W * a.H;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += blockDim.x * gridDim.x) {
+    const unsigned long long key = zbuf[p];
+    if (key == ~0ull || (unsigned)((key >> 32) & 0xFFu) != a.seq) continue;
+    const unsigned i = (unsigned)(key & 0xFFFFFFFFull);
+    color[p] = rgba8(surfel_colour<POINTS>(a, sp, cap, i));
+    depth[p] = (unsigned)(key >> 40);
+  }
+}
+
+__global__ void k_render_clear(unsigned long long* __restrict__ key, unsigned* __restrict__ color, unsigned* __restrict__ depth, int n,
+                               unsigned c, unsigned* __restrict__ clip_flag) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *clip_flag = 0u;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += blockDim.x * gridDim.x) {
+    key[p] = ~0ull;
+    color[p] = c;
+    depth[p] = 0xFFFFFFu;
+  }
+}
+
+int surfel_blocks(size_t upper) {
+  size_t b = (upper + 255) / 256;
+  if (b < 1) b = 1;
+  if (b > 4096) b = 4096;
+  return (int)b;
+}
+unsigned byte_of(float c) { return (unsigned)floorf(fminf(fmaxf(c, 0.f), 1.f) * 255.f + 0.5f); }
+
+}  // namespace
+}  // namespace dms
+
+extern "C" {
+
+int dms_render_target_create(dms_render_target** out, int width, int height) {
+  DMS_REQUIRE(out, "null argument");
+  *out = nullptr;
+  DMS_REQUIRE(width > 0 && height > 0 && width <= DMS_RENDER_MAX_EXTENT && height <= DMS_RENDER_MAX_EXTENT, "extent out of range");
+  dms_render_target* t = new dms_render_target();
+  t->width = width;
+  t->height = height;
+  const size_t n = (size_t)width * height;
+  hipError_t e = hipMalloc((void**)&t->key, n * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&t->color, n * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&t->depth, n * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&t->clip_flag, 256);
+  if (e != hipSuccess) {
+    dms_render_target_destroy(t);
+    return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
+  }
+  const float black[4] = {0.f, 0.f, 0.f, 0.f};
+  int rc = dms_render_clear(t, black, nullptr);
+  if (!rc) {
+    e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
+  }
+  if (rc) {
+    dms_render_target_destroy(t);
+    return rc;
+  }
+  *out = t;
+  return DMS_OK;
+}
+
+int dms_render_target_destroy(dms_render_target* t) {
+  if (!t) return DMS_OK;
+  if (t->key) (void)hipFree(t->key);
+  if (t->color) (void)hipFree(t->color);
+  if (t->depth) (void)hipFree(t->depth);
+  if (t->clip_flag) (void)hipFree(t->clip_flag);
+  delete t;
+  return DMS_OK;
+}
+
+int dms_render_clear(dms_render_target* t, const float clear_rgba[4], dms_stream s) {
+  DMS_REQUIRE(t && clear_rgba, "null argument");
+  const unsigned c = byte_of(clear_rgba[0]) | (byte_of(clear_rgba[1]) << 8) | (byte_of(clear_rgba[2]) << 16) | (byte_of(clear_rgba[3]) << 24);
+  const int n = t->width * t->height;
+  hipLaunchKernelGGL(k_render_clear, dim3(min((n + 255) / 256, 2048)), dim3(256), 0, (hipStream_t)s, t->key, t->color, t->depth, n, c, t->clip_flag);
+  DMS_CHECK_LAUNCH();
+  t->seq = 0;
+  return DMS_OK;
+}
+
+int dms_render_draw(dms_render_target* t, dms_model* m, const dms_render_params* p, dms_stream s) {
+  DMS_REQUIRE(t && m && p, "null argument");
+  DMS_REQUIRE(p->color_type >= 0 && p->color_type <= 4, "color_type must be 0..4");
+  DMS_REQUIRE(p->time_idx >= 0 && p->time_idx < DMS_MAX_SENSORS, "time_idx out of range");
+  DMS_REQUIRE(t->seq < DMS_RENDER_MAX_DRAWS, "too many draws since the last clear");
+  DMS_REQUIRE(!m->pending_update, "a deferred update pass is still pending (the frame step has not finished its index map)");
+  RenderArgs a;
+  memcpy(a.mvp, p->mvp, sizeof(a.mvp));
+  a.pose_dev = p->pose_dev;
+  a.W = t->width;
+  a.H = t->height;
+  a.hw = (float)t->width * 0.5f;
+  a.hh = (float)t->height * 0.5f;
+  a.threshold = p->threshold;
+  a.unstable = p->draw_unstable ? 1 : 0;
+  a.window = p->draw_window ? 1 : 0;
+  a.colorType = p->color_type;
+  a.time = p->time;
+  a.timeIdx = p->time_idx;
+  a.timeDelta = p->time_delta;
+  a.cluster = p->use_cluster_color ? 1 : 0;
+  a.cc[0] = p->cluster_color[0];
+  a.cc[1] = p->cluster_color[1];
+  a.cc[2] = p->cluster_color[2];
+  a.seq = (unsigned)t->seq;
+  const hipStream_t st = (hipStream_t)s;
+  const SurfelPlanes sp = m->buf[m->cur];
+  const int g = surfel_blocks(m->count_upper);
+  if (p->draw_points) {
+    hipLaunchKernelGGL(k_render_points, dim3(g), dim3(256), 0, st, a, sp, m->d_count, t->key);
+    DMS_CHECK_LAUNCH();
+  } else {
+    hipLaunchKernelGGL(k_render_discs<false>, dim3(g), dim3(256), 0, st, a, sp, m->d_count, t->key, t->clip_flag);
+    DMS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_render_discs<true>, dim3(g), dim3(256), 0, st, a, sp, m->d_count, t->key, t->clip_flag);
+    DMS_CHECK_LAUNCH();
+  }
+  const int n = t->width * t->height;
+  const dim3 rg(min((n + 255) / 256, 2048));
+  if (p->draw_points)
+    hipLaunchKernelGGL(k_render_resolve<true>, rg, dim3(256), 0, st, a, sp, m->cap, t->key, t->color, t->depth);
+  else
+    hipLaunchKernelGGL(k_render_resolve<false>, rg, dim3(256), 0, st, a, sp, m->cap, t->key, t->color, t->depth);
+  DMS_CHECK_LAUNCH();
+  ++t->seq;
+  return DMS_OK;
+}
+
+int dms_render_images(dms_render_target* t, dms_image2d* rgba8, dms_image2d* depth24_u32, dms_image2d* winner_u64) {
+  DMS_REQUIRE(t, "null argument");
+  if (rgba8) *rgba8 = dms_image2d{t->color, (size_t)t->width * 4, t->height, t->width};
+  if (depth24_u32) *depth24_u32 = dms_image2d{t->depth, (size_t)t->width * 4, t->height, t->width};
+  if (winner_u64) *winner_u64 = dms_image2d{t->key, (size_t)t->width * 8, t->height, t->width};
+  return DMS_OK;
+}
+
+int dms_render_target_size(const dms_render_target* t, int* width, int* height) {
+  DMS_REQUIRE(t && width && height, "null argument");
+  *width = t->width;
+  *height = t->height;
+  return DMS_OK;
+}
+
+int dms_render_mvp_from_pose(const float proj16[16], const float pose16[16], float out16[16]) {
+  DMS_REQUIRE(proj16 && pose16 && out16, "null argument");
+  mvp_from_pose(proj16, pose16, out16);
+  return DMS_OK;
+}
+
+int dms_render_frustum(int w, int h, float fu, float fv, float u0, float v0, float znear, float zfar, float out16[16]) {
+  DMS_REQUIRE(out16, "null argument");
+  DMS_REQUIRE(w > 0 && h > 0 && fu != 0.f && fv != 0.f && znear > 0.f && zfar > znear, "bad frustum");
+  const double n = znear, f = zfar;
+  const double L = -(double)u0 * n / fu, R = ((double)w - u0) * n / fu;
+  const double B = -(double)v0 * n / fv, T = ((double)h - v0) * n / fv;
+  double P[16] = {0};
+  P[0] = 2 * n / (R - L);
+  P[2] = (R + L) / (R - L);
+  P[5] = 2 * n / (T - B);
+  P[6] = (T + B) / (T - B);
+  P[10] = -(f + n) / (f - n);
+  P[11] = -(2 * f * n) / (f - n);
+  P[14] = -1.0;
+  for (int k = 0; k < 16; ++k) out16[k] = (float)P[k];
+  return DMS_OK;
+}
+
+}  // extern "C"

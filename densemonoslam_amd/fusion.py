@@ -361,6 +361,39 @@ class GlobalModel:
                                   maxDepth, int(isFern), None), "dms_model_clean")
         check(lib.dms_stream_sync(None))
 
+    def renderPointCloud(self, mvp, threshold, drawUnstable, drawNormals, drawColors, drawPoints, drawWindow, drawTimes,
+                         drawContributions, time, timeIdx, timeDelta, clusters=None, drawClusters=False, cluster_colors=None,
+                         target=None, size=None, clear_rgba=(0.0, 0.0, 0.0, 0.0), image_order=False, pose_dev=None, stream=None,
+                         context=None):
+        """GlobalModel::renderPointCloud (GlobalModel.cpp:419-505) with the reference's parameters in the reference's order.
+
+        clusters: the clusters drawn, one draw each into one target (the reference's loop over cluster_vbos; default: this map alone).
+        As in the reference they are cluster ids, resolved through `context` (the ElasticFusion whose map this is: its
+        globalModel(id); an id without buffers draws nothing) - or GlobalModel objects, drawn as they are.
+        cluster_colors[i] colours clusters[i] when drawClusters.  target: a RenderTarget drawn into as it is; without one a target of
+        `size` = (width, height) (default: the map's camera size) is created and cleared to clear_rgba.  Returns the numpy images of
+        RenderTarget.images (window rows unless image_order)."""
+        models = [self] if clusters is None else list(clusters)
+        own = target is None
+        if own:
+            w, h = size if size is not None else (self.width, self.height)
+            target = RenderTarget(w, h)
+            target.clear(clear_rgba, stream)
+        ct = color_type(drawNormals, drawColors, drawTimes, drawContributions)
+        for i, m in enumerate(models):
+            if not isinstance(m, GlobalModel):
+                if context is None:
+                    raise TypeError("cluster ids need the context that owns the clusters (context=)")
+                m = context.globalModel(int(m))
+                if m is None:
+                    continue
+            cc = cluster_colors[i] if drawClusters else None
+            target.draw(m, mvp, threshold, drawUnstable, drawPoints, drawWindow, ct, time, timeIdx, timeDelta, cc, pose_dev, stream)
+        out = target.images(image_order, stream)
+        if own:
+            target.close()
+        return out
+
 
 class IndexMap:
     """Model rendering into the camera (reference class IndexMap)."""
@@ -674,3 +707,93 @@ class ReferenceFrameRefiner:
         v = PredictOut()
         check(lib.dms_refframe_get_prediction(self.h, C.byref(v)), "dms_refframe_get_prediction")
         return capi.download_view(v.image, np.uint8, 4), capi.download_view(v.vertex, np.float32, 4), capi.download_view(v.normal, np.float32, 4)
+
+
+# ---- the map draw: GlobalModel::renderPointCloud (include/dmslam_render.h) ------------------------------------------------
+class RenderParams(C.Structure):
+    """dms_render_params"""
+    _fields_ = [("mvp", C.c_float * 16), ("pose_dev", _P), ("threshold", C.c_float), ("draw_unstable", _I), ("draw_points", _I),
+                ("draw_window", _I), ("color_type", _I), ("time", _I), ("time_idx", _I), ("time_delta", _I),
+                ("use_cluster_color", _I), ("cluster_color", C.c_float * 3)]
+
+
+lib.dms_render_target_create.argtypes = [C.POINTER(_P), _I, _I]
+lib.dms_render_target_destroy.argtypes = [_P]
+lib.dms_render_clear.argtypes = [_P, C.POINTER(C.c_float), _P]
+lib.dms_render_draw.argtypes = [_P, _P, C.POINTER(RenderParams), _P]
+lib.dms_render_images.argtypes = [_P, _I2, _I2, _I2]
+lib.dms_render_frustum.argtypes = [_I, _I, _F, _F, _F, _F, _F, _F, C.POINTER(C.c_float)]
+lib.dms_render_mvp_from_pose.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+
+
+def render_frustum(w, h, fu, fv, u0, v0, znear, zfar):
+    """pangolin::ProjectionMatrix(w, h, fu, fv, u0, v0, znear, zfar) as a row-major float 4 x 4 (dms_render_frustum)."""
+    o, op = _f16(np.zeros(16, np.float32))
+    check(lib.dms_render_frustum(int(w), int(h), fu, fv, u0, v0, znear, zfar, op), "dms_render_frustum")
+    return o.reshape(4, 4)
+
+
+def render_mvp_from_pose(proj, pose):
+    """proj * diag(1, -1, -1, 1) * inverse(pose) in the draw's fp32 order (dms_render_mvp_from_pose)."""
+    (_a, ap), (_b, bp) = _f16(proj), _f16(pose)
+    o, op = _f16(np.zeros(16, np.float32))
+    check(lib.dms_render_mvp_from_pose(ap, bp, op), "dms_render_mvp_from_pose")
+    return o.reshape(4, 4)
+
+
+def color_type(drawNormals=False, drawColors=False, drawTimes=False, drawContributions=False):
+    """renderPointCloud's colorType precedence (GlobalModel.cpp:436-440)."""
+    return 4 if drawContributions else 1 if drawNormals else 2 if drawColors else 3 if drawTimes else 0
+
+
+class RenderTarget:
+    """A W x H render target in HBM (colour RGBA8, 24-bit depth, winner key); rows are window rows (row 0 = bottom)."""
+
+    def __init__(self, width, height):
+        self.width, self.height = int(width), int(height)
+        h = C.c_void_p()
+        check(lib.dms_render_target_create(C.byref(h), self.width, self.height), "dms_render_target_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib.dms_render_target_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clear(self, rgba=(0.0, 0.0, 0.0, 0.0), stream=None):
+        c = (C.c_float * 4)(*[float(v) for v in rgba])
+        check(lib.dms_render_clear(self.h, c, stream), "dms_render_clear")
+
+    def draw(self, model, mvp=None, threshold=0.0, draw_unstable=False, draw_points=False, draw_window=False, color_type=0, time=0,
+             time_idx=0, time_delta=0, cluster_color=None, pose_dev=None, stream=None):
+        """One draw of `model` (a GlobalModel or a dms_model handle).  With pose_dev (device address of a camera-to-world pose),
+        `mvp` is the projection and the view is built on the device."""
+        p = RenderParams()
+        m = np.ascontiguousarray(np.eye(4, dtype=np.float32) if mvp is None else mvp, np.float32).reshape(16)
+        for k in range(16):
+            p.mvp[k] = float(m[k])
+        p.pose_dev = pose_dev
+        p.threshold = float(threshold)
+        p.draw_unstable, p.draw_points, p.draw_window = int(bool(draw_unstable)), int(bool(draw_points)), int(bool(draw_window))
+        p.color_type, p.time, p.time_idx, p.time_delta = int(color_type), int(time), int(time_idx), int(time_delta)
+        if cluster_color is not None:
+            p.use_cluster_color = 1
+            for k in range(3):
+                p.cluster_color[k] = float(cluster_color[k])
+        h = model.h if isinstance(model, GlobalModel) else C.c_void_p(model)
+        check(lib.dms_render_draw(self.h, h, C.byref(p), stream), "dms_render_draw")
+
+    def images(self, image_order=False, stream=None):
+        """(rgba u8 HxWx4, depth24 u32 HxW, winner key u64 HxW) after the work enqueued on `stream`; image_order flips the rows
+        so that row 0 is the top of the view."""
+        check(lib.dms_stream_sync(stream), "dms_stream_sync")
+        c, d, w = Image2D(), Image2D(), Image2D()
+        check(lib.dms_render_images(self.h, C.byref(c), C.byref(d), C.byref(w)), "dms_render_images")
+        out = (capi.download_view(c, np.uint8, 4), capi.download_view(d, np.uint32), capi.download_view(w, np.uint64))
+        return tuple(a[::-1].copy() for a in out) if image_order else out
