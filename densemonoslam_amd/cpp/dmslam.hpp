@@ -13,6 +13,7 @@
 //   IndexMap     (Core/src/IndexMap.h:33-205)                  -> dms::IndexMap
 //   ElasticFusion::processFrame (ElasticFusion.h:92-100)       -> dms::ElasticFusion::processFrame
 //   Ferns        (Core/src/Ferns.h:35-266)                     -> dms::Ferns
+//   GUI::drawFXAA (GUI/src/Tools/GUI.h:365-478)                -> dms::ShadedView::drawFXAA
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -23,6 +24,7 @@
 #include "../../include/dmslam_ferns.h"
 #include "../../include/dmslam_fusion.h"
 #include "../../include/dmslam_render.h"
+#include "../../include/dmslam_render_shaded.h"
 
 namespace dms {
 
@@ -193,6 +195,52 @@ class GlobalModel {
 
  private:
   bool owned;
+};
+
+// GUI::drawFXAA (GUI/src/Tools/GUI.h:365-478): the offscreen float buffer (default the GUI's 3840 x 2160) and the view it is
+// resolved into.  The host clears the view (clearView) as the GUI clears its window; drawFXAA draws one map into it.
+class ShadedView {
+ public:
+  ShadedView(int width, int height, int offscreenWidth = DMS_RENDER_OFFSCREEN_WIDTH, int offscreenHeight = DMS_RENDER_OFFSCREEN_HEIGHT,
+             dms_stream s = nullptr)
+      : stream(s) {
+    check(dms_render_target_create(&target, width, height), "dms_render_target_create");
+    if (int rc = dms_render_offscreen_create(&offscreen, offscreenWidth, offscreenHeight)) {
+      dms_render_target_destroy(target);
+      check(rc, "dms_render_offscreen_create");
+    }
+  }
+  ~ShadedView() {
+    dms_render_offscreen_destroy(offscreen);
+    dms_render_target_destroy(target);
+  }
+  ShadedView(const ShadedView&) = delete;
+  ShadedView& operator=(const ShadedView&) = delete;
+  void clearView(const float rgba[4]) { check(dms_render_clear(target, rgba, stream), "clearView"); }
+  // The reference's arguments in the reference's order, then the GUI's toggles.  mvp16 and mv16 are row-major (pangolin's
+  // OpenGlMatrix is column-major: transpose it, e.g. with GlobalModel::transposed16); lightpos is mv's translation column
+  // (GUI.h:404-408), signMult +1 with invertNormals, else -1 (:393), colorType normals 1, colours 2, times 3, else 0 (:395-398).
+  // timeIdx is the call's own (GUI.h:389 passes time: DESIGN.md §2.6).
+  void drawFXAA(const float* mvp16, const float* mv16, GlobalModel& model, const float threshold, const int time, const int timeIdx,
+                const int timeDelta, const bool invertNormals, const bool drawNormals, const bool drawColors, const bool drawTimes,
+                const bool drawUnstable, const bool drawWindow, const bool showcaseMode) {
+    dms_render_params p = {};
+    for (int k = 0; k < 16; ++k) p.mvp[k] = mvp16[k];
+    p.threshold = threshold;
+    p.draw_unstable = drawUnstable;
+    p.draw_window = drawWindow;
+    p.color_type = drawNormals ? 1 : drawColors ? 2 : drawTimes ? 3 : 0;
+    p.time = time;
+    p.time_idx = timeIdx;
+    p.time_delta = timeDelta;
+    const float lightpos[3] = {mv16[3], mv16[7], mv16[11]};
+    const float clear[4] = {showcaseMode ? 1.f : 0.05f, showcaseMode ? 1.f : 0.05f, showcaseMode ? 1.f : 0.3f, 0.f};
+    check(dms_render_shaded_draw(offscreen, model.h, &p, lightpos, invertNormals ? 1.f : -1.f, clear, stream), "drawFXAA");
+    check(dms_render_fxaa(target, offscreen, stream), "drawFXAA");
+  }
+  dms_render_target* target = nullptr;
+  dms_render_offscreen* offscreen = nullptr;
+  dms_stream stream = nullptr;
 };
 
 // IndexMap (IndexMap.h:39-162): the render targets of one camera and the three "draws" over a GlobalModel.

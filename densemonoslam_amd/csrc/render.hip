@@ -11,6 +11,7 @@
 // tests/render_ref.py restates them on the CPU.
 #include "surfel.hpp"
 #include "../../include/dmslam_render.h"
+#include "../../include/dmslam_render_shaded.h"
 
 using namespace dms;
 
@@ -86,14 +87,24 @@ __device__ __forceinline__ void launch_mvp(const RenderArgs& a, float* M) {
 
 // ---- disc geometry (draw_global_surface.geom:185-212) -------------------------------------------------------------------
 // the four strip vertices P + x, P + y, P - y, P - x in clip space; texcoords (-1,-1) (1,-1) (-1,1) (1,1)
-__device__ __forceinline__ void disc_corners(const float* M, const float4& pc, const float4& nr, c4* v) {
+// world positions of the four strip vertices (the geometry stage's `v`, .geom:122-140)
+__device__ __forceinline__ void disc_world(const float4& pc, const float4& nr, f3* w) {
   const f3 xn = normalized3(mk3(nr.y - nr.z, -nr.x, nr.x));
   const f3 x = mk3((xn.x * nr.w) * 1.41421356f, (xn.y * nr.w) * 1.41421356f, (xn.z * nr.w) * 1.41421356f);
   const f3 y = cross3(mk3(nr.x, nr.y, nr.z), x);
-  v[0] = clip_of(M, pc.x + x.x, pc.y + x.y, pc.z + x.z);
-  v[1] = clip_of(M, pc.x + y.x, pc.y + y.y, pc.z + y.z);
-  v[2] = clip_of(M, pc.x - y.x, pc.y - y.y, pc.z - y.z);
-  v[3] = clip_of(M, pc.x - x.x, pc.y - x.y, pc.z - x.z);
+  w[0] = mk3(pc.x + x.x, pc.y + x.y, pc.z + x.z);
+  w[1] = mk3(pc.x + y.x, pc.y + y.y, pc.z + y.z);
+  w[2] = mk3(pc.x - y.x, pc.y - y.y, pc.z - y.z);
+  w[3] = mk3(pc.x - x.x, pc.y - x.y, pc.z - x.z);
+}
+__device__ __forceinline__ void disc_corners(const float* M, const f3* w, c4* v) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = clip_of(M, w[k].x, w[k].y, w[k].z);
+}
+__device__ __forceinline__ void disc_corners(const float* M, const float4& pc, const float4& nr, c4* v) {
+  f3 w[4];
+  disc_world(pc, nr, w);
+  disc_corners(M, w, v);
 }
 
 // R8 plane distances: near z >= -w, then the guard band
@@ -129,6 +140,22 @@ __device__ __forceinline__ WV to_window(const RenderArgs& a, const c4& c, float 
 __device__ __forceinline__ int first_px(int lo) { return -((kSub / 2 - lo) >> 8); }
 __device__ __forceinline__ int last_px(int hi) { return (hi - kSub / 2) >> 8; }
 
+// R7 / R10 at a pixel a triangle covers (barycentrics b0..b2): the fragment's 24-bit depth, or 0xFFFFFFFF where there is none;
+// q0..q2 / den are its perspective weights
+__device__ __forceinline__ unsigned disc_fragment(const WV& v0, const WV& v1, const WV& v2, float b0, float b1, float b2, float shift,
+                                                  float& q0, float& q1, float& q2, float& den) {
+  const float z = (b0 * v0.z + b1 * v1.z) + b2 * v2.z;
+  if (!(z >= 0.f && z <= 1.f)) return 0xFFFFFFFFu;  // R8: nothing beyond the far (or before the near) plane
+  q0 = b0 * v0.iw, q1 = b1 * v1.iw, q2 = b2 * v2.iw;
+  den = (q0 + q1) + q2;
+  const float u = ((q0 * v0.u + q1 * v1.u) + q2 * v2.u) / den;
+  const float v = ((q0 * v0.v + q1 * v1.v) + q2 * v2.v) / den;
+  if (u * u + v * v > 1.f) return 0xFFFFFFFFu;  // draw_global_surface.frag:30-31
+  // .frag:35-42 + R10: the shifted depth is clamped to [0, 1] before the 24-bit conversion and the test
+  const float zf = fminf(fmaxf(z + shift, 0.f), 1.f);
+  return depth24(zf);
+}
+
 // R6 / R7 / R10: one triangle over pixels [xa, xb] of row py
 __device__ void raster_row(WV v0, WV v1, WV v2, int py, int xa, int xb, unsigned long long key_lo, float shift, int W,
                            unsigned long long* __restrict__ zrow) {
@@ -154,16 +181,8 @@ __device__ void raster_row(WV v0, WV v1, WV v2, int py, int xa, int xb, unsigned
   for (int px = xa; px <= xb; ++px, e0 += s0, e1 += s1, e2 += s2) {
     if (!((e0 > 0 || (e0 == 0 && tl0)) && (e1 > 0 || (e1 == 0 && tl1)) && (e2 > 0 || (e2 == 0 && tl2)))) continue;
     const float b0 = (float)(double)e0 * inv, b1 = (float)(double)e1 * inv, b2 = (float)(double)e2 * inv;
-    const float z = (b0 * v0.z + b1 * v1.z) + b2 * v2.z;
-    if (!(z >= 0.f && z <= 1.f)) continue;  // R8: nothing beyond the far (or before the near) plane
-    const float q0 = b0 * v0.iw, q1 = b1 * v1.iw, q2 = b2 * v2.iw;
-    const float den = (q0 + q1) + q2;
-    const float u = ((q0 * v0.u + q1 * v1.u) + q2 * v2.u) / den;
-    const float v = ((q0 * v0.v + q1 * v1.v) + q2 * v2.v) / den;
-    if (u * u + v * v > 1.f) continue;  // draw_global_surface.frag:30-31
-    // .frag:35-42 + R10: the shifted depth is clamped to [0, 1] before the 24-bit conversion and the test
-    const float zf = fminf(fmaxf(z + shift, 0.f), 1.f);
-    const unsigned d = depth24(zf);
+    float q0, q1, q2, den;
+    const unsigned d = disc_fragment(v0, v1, v2, b0, b1, b2, shift, q0, q1, q2, den);
     if (d >= 0xFFFFFFu) continue;  // GL_LESS against the cleared 1.0
     const unsigned long long key = ((unsigned long long)d << 40) | key_lo;
     if (key < zrow[px]) atomicMin(zrow + px, key);
@@ -176,27 +195,41 @@ struct CV {
   c4 c;
   float u, v;
 };
-__device__ __forceinline__ int clip_polygon(CV* poly, int n) {
-  CV tmp[9];
+struct CVW {  // the same with the world position (the shaded draw, R11)
+  c4 c;
+  float u, v;
+  f3 w;
+};
+__device__ __forceinline__ void lerp_attrs(CV& r, const CV& I, const CV& O, float t) {
+  r.u = I.u + t * (O.u - I.u);
+  r.v = I.v + t * (O.v - I.v);
+}
+__device__ __forceinline__ void lerp_attrs(CVW& r, const CVW& I, const CVW& O, float t) {
+  r.u = I.u + t * (O.u - I.u);
+  r.v = I.v + t * (O.v - I.v);
+  r.w = mk3(I.w.x + t * (O.w.x - I.w.x), I.w.y + t * (O.w.y - I.w.y), I.w.z + t * (O.w.z - I.w.z));
+}
+template <class V>
+__device__ __forceinline__ int clip_polygon(V* poly, int n) {
+  V tmp[9];
   for (int k = 0; k < 5 && n > 0; ++k) {
     int m = 0;
     for (int i = 0; i < n; ++i) {
-      const CV A = poly[i], B = poly[(i + 1) % n];
+      const V A = poly[i], B = poly[(i + 1) % n];
       const float da = plane_dist(A.c, k), db = plane_dist(B.c, k);
       const bool ia = da >= 0.f, ib = db >= 0.f;
       if (ia) tmp[m++] = A;
       if (ia != ib) {
-        const CV& I = ia ? A : B;
-        const CV& O = ia ? B : A;
+        const V& I = ia ? A : B;
+        const V& O = ia ? B : A;
         const float di = ia ? da : db, dout = ia ? db : da;
         const float t = di / (di - dout);
-        CV r;
+        V r;
         r.c.x = I.c.x + t * (O.c.x - I.c.x);
         r.c.y = I.c.y + t * (O.c.y - I.c.y);
         r.c.z = I.c.z + t * (O.c.z - I.c.z);
         r.c.w = I.c.w + t * (O.c.w - I.c.w);
-        r.u = I.u + t * (O.u - I.u);
-        r.v = I.v + t * (O.v - I.v);
+        lerp_attrs(r, I, O, t);
         tmp[m++] = r;
       }
     }
@@ -479,6 +512,225 @@ __global__ void k_render_clear(unsigned long long* __restrict__ key, unsigned* _
   }
 }
 
+// ---- the shaded view: GUI::drawFXAA (GUI/src/Tools/GUI.h:365-478) ------------------------------------
+// Pass A draws the map into an offscreen float buffer with draw_global_surface.{vert,geom} + draw_global_surface_phong.frag: the
+// keys come from pass 1 of the disc program unchanged (seq 0 after a clear); k_shaded_resolve is a visibility-buffer resolve: per
+// pixel it rebuilds the winner's strip, finds the one triangle (or fan piece of a clipped triangle) whose fragment won, interpolates
+// the world position there (R11) and evaluates the Phong program.  Pass B (k_render_fxaa) is fxaa.frag over that buffer into a
+// render target, followed by the NEAREST depth blit.
+
+// the fragment of triangle (v0, v1, v2) at pixel (px, py), exactly as raster_row produces it; its 24-bit depth (0xFFFFFFFF: none)
+// and, where there is one, the world position interpolated like the texcoord (R11)
+__device__ __forceinline__ unsigned pixel_fragment(WV v0, WV v1, WV v2, f3 w0, f3 w1, f3 w2, int px, int py, float shift, f3& out) {
+  long long area = (long long)(v1.X - v0.X) * (long long)(v2.Y - v0.Y) - (long long)(v1.Y - v0.Y) * (long long)(v2.X - v0.X);
+  if (area == 0) return 0xFFFFFFFFu;
+  if (area < 0) {
+    const WV t = v1;
+    v1 = v2;
+    v2 = t;
+    const f3 tw = w1;
+    w1 = w2;
+    w2 = tw;
+    area = -area;
+  }
+  const int dx0 = v2.X - v1.X, dy0 = v2.Y - v1.Y, dx1 = v0.X - v2.X, dy1 = v0.Y - v2.Y, dx2 = v1.X - v0.X, dy2 = v1.Y - v0.Y;
+  const bool tl0 = dy0 < 0 || (dy0 == 0 && dx0 < 0), tl1 = dy1 < 0 || (dy1 == 0 && dx1 < 0), tl2 = dy2 < 0 || (dy2 == 0 && dx2 < 0);
+  const long long Py = (long long)py * kSub + kSub / 2, Px = (long long)px * kSub + kSub / 2;
+  const long long e0 = (long long)dx0 * (Py - v1.Y) - (long long)dy0 * (Px - v1.X);
+  const long long e1 = (long long)dx1 * (Py - v2.Y) - (long long)dy1 * (Px - v2.X);
+  const long long e2 = (long long)dx2 * (Py - v0.Y) - (long long)dy2 * (Px - v0.X);
+  if (!((e0 > 0 || (e0 == 0 && tl0)) && (e1 > 0 || (e1 == 0 && tl1)) && (e2 > 0 || (e2 == 0 && tl2)))) return 0xFFFFFFFFu;
+  const float inv = 1.f / (float)(double)area;
+  const float b0 = (float)(double)e0 * inv, b1 = (float)(double)e1 * inv, b2 = (float)(double)e2 * inv;
+  float q0, q1, q2, den;
+  const unsigned d = disc_fragment(v0, v1, v2, b0, b1, b2, shift, q0, q1, q2, den);
+  if (d < 0xFFFFFFu) {
+    out.x = ((q0 * w0.x + q1 * w1.x) + q2 * w2.x) / den;
+    out.y = ((q0 * w0.y + q1 * w1.y) + q2 * w2.y) / den;
+    out.z = ((q0 * w0.z + q1 * w1.z) + q2 * w2.z) / den;
+  }
+  return d;
+}
+
+// a winner whose strip needs clipping (R8): its fan pieces in GL order, the first whose fragment has the winning depth
+__device__ __noinline__ bool clipped_winner(const RenderArgs& a, const c4* cv, const f3* wc, int px, int py, float shift, unsigned dwin, f3& out) {
+  const float tu[4] = {-1.f, 1.f, -1.f, 1.f}, tv[4] = {-1.f, -1.f, 1.f, 1.f};
+  const int tri[2][3] = {{0, 1, 2}, {2, 1, 3}};
+  for (int t = 0; t < 2; ++t) {
+    CVW poly[9];
+    for (int k = 0; k < 3; ++k) {
+      const int i = tri[t][k];
+      poly[k].c = cv[i];
+      poly[k].u = tu[i];
+      poly[k].v = tv[i];
+      poly[k].w = wc[i];
+    }
+    const int n = clip_polygon(poly, 3);
+    if (n < 3) continue;
+    bool ok = true;
+    for (int k = 0; k < n; ++k) ok = ok && poly[k].c.w > 0.f;
+    if (!ok) continue;
+    const WV w0 = to_window(a, poly[0].c, poly[0].u, poly[0].v);
+    WV wp = to_window(a, poly[1].c, poly[1].u, poly[1].v);
+    for (int k = 2; k < n; ++k) {  // fan (0, k-1, k)
+      const WV wk = to_window(a, poly[k].c, poly[k].u, poly[k].v);
+      if (pixel_fragment(w0, wp, wk, poly[0].w, poly[k - 1].w, poly[k].w, px, py, shift, out) == dwin) return true;
+      wp = wk;
+    }
+  }
+  return false;
+}
+
+__device__ __forceinline__ float4 operator+(const float4& p, const float4& q) { return make_float4(p.x + q.x, p.y + q.y, p.z + q.z, p.w + q.w); }
+
+// draw_global_surface_phong.frag:37-64 for colour c at world position v, normal n = signMult * normal (R12-R14); not clamped
+__device__ __forceinline__ float4 phong(const f3& c, const f3& n, const f3& v, const f3& light) {
+  const float4 ambient = make_float4(0.3f * c.x, 0.3f * c.y, 0.3f * c.z, 1.f);
+  float4 diffuse = make_float4(0.f, 0.f, 0.f, 0.f), specular = make_float4(0.f, 0.f, 0.f, 0.f);
+  const f3 lightDir = normalized3(mk3(light.x - v.x, light.y - v.y, light.z - v.z));
+  const float NdotL = dot3(n, lightDir);
+  if (NdotL > 0.f) diffuse = make_float4(c.x * NdotL, c.y * NdotL, c.z * NdotL, 1.f * NdotL);
+  const float nl = dot3(n, lightDir);
+  const f3 rVector = normalized3(mk3((2.f * n.x) * nl - lightDir.x, (2.f * n.y) * nl - lightDir.y, (2.f * n.z) * nl - lightDir.z));
+  const f3 viewVector = normalized3(mk3(-v.x, -v.y, -v.z));
+  const float RdotV = dot3(rVector, viewVector);
+  if (RdotV > 0.f) {  // R13: pow(RdotV, 32) = five squarings
+    float p = RdotV * RdotV;
+    p = p * p;
+    p = p * p;
+    p = p * p;
+    p = p * p;
+    specular = make_float4(p, p, p, p);
+  }
+  return (ambient + diffuse) + specular;
+}
+
+struct ShadeArgs {
+  float4 clear;
+  float light[3];
+  float sign;
+};
+
+// Pass A, per pixel of the offscreen buffer: the winner's Phong colour and depth, or the clear colour and depth 1.0
+__global__ __launch_bounds__(256) void k_shaded_resolve(RenderArgs a, ShadeArgs sa, SurfelPlanes sp, size_t cap,
+                                                        const unsigned long long* __restrict__ zbuf, float4* __restrict__ rgba,
+                                                        unsigned* __restrict__ depth) {
+  const int n = a.W * a.H;
+  float Mv[16];
+  launch_mvp(a, Mv);
+  const f3 light = mk3(sa.light[0], sa.light[1], sa.light[2]);
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += blockDim.x * gridDim.x) {
+    const unsigned long long key = zbuf[p];
+    if (key == ~0ull) {
+      rgba[p] = sa.clear;
+      depth[p] = 0xFFFFFFu;
+      continue;
+    }
+    const unsigned i = (unsigned)(key & 0xFFFFFFFFull), dwin = (unsigned)(key >> 40);
+    const int px = p % a.W, py = p / a.W;
+    const float4 pc = sp.pos[i], nr = sp.nrm[i];
+    const float shift = pc.w <= a.threshold ? nr.w : 0.f;
+    f3 wc[4];
+    c4 cv[4];
+    disc_world(pc, nr, wc);
+    disc_corners(Mv, wc, cv);
+    f3 v = mk3(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""));  // (every winner has its fragment: never kept)
+    if ((outcode(cv[0]) | outcode(cv[1]) | outcode(cv[2]) | outcode(cv[3])) == 0u) {
+      const float tu[4] = {-1.f, 1.f, -1.f, 1.f}, tv[4] = {-1.f, -1.f, 1.f, 1.f};
+      WV w[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) w[k] = to_window(a, cv[k], tu[k], tv[k]);
+      // GL strip order: (v0, v1, v2), (v2, v1, v3); the first fragment with the winning depth is the one GL_LESS kept
+      if (pixel_fragment(w[0], w[1], w[2], wc[0], wc[1], wc[2], px, py, shift, v) != dwin)
+        (void)pixel_fragment(w[2], w[1], w[3], wc[2], wc[1], wc[3], px, py, shift, v);
+    } else {
+      (void)clipped_winner(a, cv, wc, px, py, shift, dwin, v);
+    }
+    const f3 c = surfel_colour<false>(a, sp, cap, i);
+    rgba[p] = phong(c, mk3(sa.sign * nr.x, sa.sign * nr.y, sa.sign * nr.z), v, light);
+    depth[p] = dwin;
+  }
+}
+
+__global__ void k_offscreen_init(unsigned long long* __restrict__ key, float4* __restrict__ rgba, unsigned* __restrict__ depth, int n,
+                                 unsigned* __restrict__ clip_flag) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *clip_flag = 0u;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += blockDim.x * gridDim.x) {
+    key[p] = ~0ull;
+    rgba[p] = make_float4(0.f, 0.f, 0.f, 0.f);
+    depth[p] = 0xFFFFFFu;
+  }
+}
+
+__global__ void k_shaded_clear(unsigned long long* __restrict__ key, int n, unsigned* __restrict__ clip_flag) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *clip_flag = 0u;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += blockDim.x * gridDim.x) key[p] = ~0ull;
+}
+
+// R15: GL_LINEAR of an RGBA32F texture with GL_REPEAT (xyz only): texel origin s W - 0.5, fp32 weights, lerp a + w (b - a)
+__device__ __forceinline__ f3 tex_linear(const float4* __restrict__ img, int W, int H, float s, float t) {
+  const float x = s * (float)W - 0.5f, y = t * (float)H - 0.5f;
+  const float fx = floorf(x), fy = floorf(y);
+  const float ax = x - fx, ay = y - fy;
+  int i0 = (int)fx % W, j0 = (int)fy % H;
+  i0 += i0 < 0 ? W : 0;
+  j0 += j0 < 0 ? H : 0;
+  const int i1 = i0 + 1 == W ? 0 : i0 + 1, j1 = j0 + 1 == H ? 0 : j0 + 1;
+  const float4 t00 = img[(size_t)j0 * W + i0], t10 = img[(size_t)j0 * W + i1];
+  const float4 t01 = img[(size_t)j1 * W + i0], t11 = img[(size_t)j1 * W + i1];
+  const f3 r0 = mk3(t00.x + ax * (t10.x - t00.x), t00.y + ax * (t10.y - t00.y), t00.z + ax * (t10.z - t00.z));
+  const f3 r1 = mk3(t01.x + ax * (t11.x - t01.x), t01.y + ax * (t11.y - t01.y), t01.z + ax * (t11.z - t01.z));
+  return mk3(r0.x + ay * (r1.x - r0.x), r0.y + ay * (r1.y - r0.y), r0.z + ay * (r1.z - r0.z));
+}
+
+__device__ __forceinline__ float luma(const f3& c) { return (c.x * 0.299f + c.y * 0.587f) + c.z * 0.114f; }
+
+// fxaa.frag:34-88 at texcoord (s, t) of a W x H float buffer (R16, R18).  The N / E / W / S fetches of the shader reach no output
+// and are not made.
+__device__ __forceinline__ f3 fxaa(const float4* __restrict__ img, int W, int H, float s, float t) {
+  const float ivx = 1.f / (float)W, ivy = 1.f / (float)H;
+  const f3 rgbNW = tex_linear(img, W, H, s + -1.f * ivx, t + -1.f * ivy);
+  const f3 rgbNE = tex_linear(img, W, H, s + 1.f * ivx, t + -1.f * ivy);
+  const f3 rgbSW = tex_linear(img, W, H, s + -1.f * ivx, t + 1.f * ivy);
+  const f3 rgbSE = tex_linear(img, W, H, s + 1.f * ivx, t + 1.f * ivy);
+  const f3 rgbM = tex_linear(img, W, H, s, t);
+  const float lumaNW = luma(rgbNW), lumaNE = luma(rgbNE), lumaSW = luma(rgbSW), lumaSE = luma(rgbSE), lumaM = luma(rgbM);
+  const float lumaMin = fminf(lumaM, fminf(fminf(lumaNW, lumaNE), fminf(lumaSW, lumaSE)));
+  const float lumaMax = fmaxf(lumaM, fmaxf(fmaxf(lumaNW, lumaNE), fmaxf(lumaSW, lumaSE)));
+  float dx = -((lumaNW + lumaNE) - (lumaSW + lumaSE));
+  float dy = (lumaNW + lumaSW) - (lumaNE + lumaSE);
+  const float dirReduce = fmaxf((((lumaNW + lumaNE) + lumaSW) + lumaSE) * (0.25f * (1.f / 8.f)), 1.f / 128.f);
+  const float rcpDirMin = 1.f / (fminf(fabsf(dx), fabsf(dy)) + dirReduce);
+  dx = fminf(8.f, fmaxf(-8.f, dx * rcpDirMin)) * ivx;
+  dy = fminf(8.f, fmaxf(-8.f, dy * rcpDirMin)) * ivy;
+  const float c1 = 1.f / 3.f - 0.5f, c2 = 2.f / 3.f - 0.5f;
+  const f3 a1 = tex_linear(img, W, H, s + dx * c1, t + dy * c1), a2 = tex_linear(img, W, H, s + dx * c2, t + dy * c2);
+  const f3 rgbA = mk3(0.5f * (a1.x + a2.x), 0.5f * (a1.y + a2.y), 0.5f * (a1.z + a2.z));
+  const f3 b1 = tex_linear(img, W, H, s + dx * -0.5f, t + dy * -0.5f), b2 = tex_linear(img, W, H, s + dx * 0.5f, t + dy * 0.5f);
+  const f3 rgbB = mk3(rgbA.x * 0.5f + 0.25f * (b1.x + b2.x), rgbA.y * 0.5f + 0.25f * (b1.y + b2.y), rgbA.z * 0.5f + 0.25f * (b1.z + b2.z));
+  const float lumaB = luma(rgbB);
+  return (lumaB < lumaMin || lumaB > lumaMax) ? rgbA : rgbB;
+}
+
+// Pass B, per pixel of the target: the FXAA quad at window depth 0.5 under GL_LESS, then the NEAREST depth blit (R17), which
+// replaces depth and winner (as a draw with sequence number seq)
+__global__ __launch_bounds__(256) void k_render_fxaa(const float4* __restrict__ img, const unsigned long long* __restrict__ skey,
+                                                     const unsigned* __restrict__ sdepth, int SW, int SH, int W, int H, unsigned seq,
+                                                     unsigned* __restrict__ color, unsigned* __restrict__ depth,
+                                                     unsigned long long* __restrict__ key) {
+  const int n = W * H;
+  const unsigned quad = depth24(0.5f);
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += blockDim.x * gridDim.x) {
+    const int x = p % W, y = p / W;
+    if (quad < depth[p]) color[p] = rgba8(fxaa(img, SW, SH, ((float)x + 0.5f) / (float)W, ((float)y + 0.5f) / (float)H));
+    const int sx = (int)(((2ll * x + 1) * SW) / (2ll * W)), sy = (int)(((2ll * y + 1) * SH) / (2ll * H));
+    const size_t q = (size_t)sy * SW + sx;
+    const unsigned long long k = skey[q];
+    depth[p] = sdepth[q];
+    key[p] = k == ~0ull ? k : (k & ~(0xFFull << 32)) | ((unsigned long long)seq << 32);
+  }
+}
+
 int surfel_blocks(size_t upper) {
   size_t b = (upper + 255) / 256;
   if (b < 1) b = 1;
@@ -626,6 +878,128 @@ int dms_render_frustum(int w, int h, float fu, float fv, float u0, float v0, flo
   P[11] = -(2 * f * n) / (f - n);
   P[14] = -1.0;
   for (int k = 0; k < 16; ++k) out16[k] = (float)P[k];
+  return DMS_OK;
+}
+
+}  // extern "C"
+
+// ---- the shaded view (include/dmslam_render_shaded.h) -------------------------------------------------------------------------
+struct dms_render_offscreen {
+  int width = 0, height = 0;
+  unsigned long long* key = nullptr;  // [H][W] (window rows)
+  float4* rgba = nullptr;             // RGBA32F
+  unsigned* depth = nullptr;          // 24-bit depth
+  unsigned* clip_flag = nullptr;      // 1 when the last draw met a surfel to clip (R8)
+};
+
+extern "C" {
+
+int dms_render_offscreen_create(dms_render_offscreen** out, int width, int height) {
+  DMS_REQUIRE(out, "null argument");
+  *out = nullptr;
+  DMS_REQUIRE(width > 0 && height > 0 && width <= DMS_RENDER_MAX_EXTENT && height <= DMS_RENDER_MAX_EXTENT, "extent out of range");
+  dms_render_offscreen* o = new dms_render_offscreen();
+  o->width = width;
+  o->height = height;
+  const size_t n = (size_t)width * height;
+  hipError_t e = hipMalloc((void**)&o->key, n * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&o->rgba, n * 16);
+  if (e == hipSuccess) e = hipMalloc((void**)&o->depth, n * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&o->clip_flag, 256);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_offscreen_init, dim3(min(((int)n + 255) / 256, 2048)), dim3(256), 0, nullptr, o->key, o->rgba, o->depth, (int)n,
+                       o->clip_flag);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess) {
+    dms_render_offscreen_destroy(o);
+    return hip_fail(e, "dms_render_offscreen_create", __FILE__, __LINE__);
+  }
+  *out = o;
+  return DMS_OK;
+}
+
+int dms_render_offscreen_destroy(dms_render_offscreen* o) {
+  if (!o) return DMS_OK;
+  if (o->key) (void)hipFree(o->key);
+  if (o->rgba) (void)hipFree(o->rgba);
+  if (o->depth) (void)hipFree(o->depth);
+  if (o->clip_flag) (void)hipFree(o->clip_flag);
+  delete o;
+  return DMS_OK;
+}
+
+int dms_render_offscreen_size(const dms_render_offscreen* o, int* width, int* height) {
+  DMS_REQUIRE(o && width && height, "null argument");
+  *width = o->width;
+  *height = o->height;
+  return DMS_OK;
+}
+
+int dms_render_shaded_draw(dms_render_offscreen* o, dms_model* m, const dms_render_params* p, const float light_pos[3], float sign_mult,
+                           const float clear_rgba[4], dms_stream s) {
+  DMS_REQUIRE(o && m && p && light_pos && clear_rgba, "null argument");
+  DMS_REQUIRE(!p->draw_points, "the shaded view draws discs (draw_points must be 0)");
+  DMS_REQUIRE(!p->use_cluster_color, "the shaded view has no cluster colour");
+  DMS_REQUIRE(p->color_type >= 0 && p->color_type <= 3, "color_type must be 0..3");
+  DMS_REQUIRE(p->time_idx >= 0 && p->time_idx < DMS_MAX_SENSORS, "time_idx out of range");
+  DMS_REQUIRE(!m->pending_update, "a deferred update pass is still pending (the frame step has not finished its index map)");
+  RenderArgs a;
+  memcpy(a.mvp, p->mvp, sizeof(a.mvp));
+  a.pose_dev = p->pose_dev;
+  a.W = o->width;
+  a.H = o->height;
+  a.hw = (float)o->width * 0.5f;
+  a.hh = (float)o->height * 0.5f;
+  a.threshold = p->threshold;
+  a.unstable = p->draw_unstable ? 1 : 0;
+  a.window = p->draw_window ? 1 : 0;
+  a.colorType = p->color_type;
+  a.time = p->time;
+  a.timeIdx = p->time_idx;
+  a.timeDelta = p->time_delta;
+  a.cluster = 0;
+  a.cc[0] = a.cc[1] = a.cc[2] = 0.f;
+  a.seq = 0u;
+  ShadeArgs sa;
+  sa.clear = make_float4(clear_rgba[0], clear_rgba[1], clear_rgba[2], clear_rgba[3]);
+  sa.light[0] = light_pos[0];
+  sa.light[1] = light_pos[1];
+  sa.light[2] = light_pos[2];
+  sa.sign = sign_mult;
+  const hipStream_t st = (hipStream_t)s;
+  const SurfelPlanes sp = m->buf[m->cur];
+  const int n = o->width * o->height;
+  const dim3 rg(min((n + 255) / 256, 2048));
+  hipLaunchKernelGGL(k_shaded_clear, rg, dim3(256), 0, st, o->key, n, o->clip_flag);
+  DMS_CHECK_LAUNCH();
+  const int g = surfel_blocks(m->count_upper);
+  hipLaunchKernelGGL(k_render_discs<false>, dim3(g), dim3(256), 0, st, a, sp, m->d_count, o->key, o->clip_flag);
+  DMS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_render_discs<true>, dim3(g), dim3(256), 0, st, a, sp, m->d_count, o->key, o->clip_flag);
+  DMS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_shaded_resolve, rg, dim3(256), 0, st, a, sa, sp, m->cap, o->key, o->rgba, o->depth);
+  DMS_CHECK_LAUNCH();
+  return DMS_OK;
+}
+
+int dms_render_fxaa(dms_render_target* t, const dms_render_offscreen* o, dms_stream s) {
+  DMS_REQUIRE(t && o, "null argument");
+  DMS_REQUIRE(t->seq < DMS_RENDER_MAX_DRAWS, "too many draws since the last clear");
+  const int n = t->width * t->height;
+  hipLaunchKernelGGL(k_render_fxaa, dim3(min((n + 255) / 256, 2048)), dim3(256), 0, (hipStream_t)s, o->rgba, o->key, o->depth, o->width,
+                     o->height, t->width, t->height, (unsigned)t->seq, t->color, t->depth, t->key);
+  DMS_CHECK_LAUNCH();
+  ++t->seq;
+  return DMS_OK;
+}
+
+int dms_render_offscreen_images(dms_render_offscreen* o, dms_image2d* rgba32f, dms_image2d* depth24_u32, dms_image2d* winner_u64) {
+  DMS_REQUIRE(o, "null argument");
+  if (rgba32f) *rgba32f = dms_image2d{o->rgba, (size_t)o->width * 16, o->height, o->width};
+  if (depth24_u32) *depth24_u32 = dms_image2d{o->depth, (size_t)o->width * 4, o->height, o->width};
+  if (winner_u64) *winner_u64 = dms_image2d{o->key, (size_t)o->width * 8, o->height, o->width};
   return DMS_OK;
 }
 

@@ -797,3 +797,91 @@ class RenderTarget:
         check(lib.dms_render_images(self.h, C.byref(c), C.byref(d), C.byref(w)), "dms_render_images")
         out = (capi.download_view(c, np.uint8, 4), capi.download_view(d, np.uint32), capi.download_view(w, np.uint64))
         return tuple(a[::-1].copy() for a in out) if image_order else out
+
+
+# ---- the shaded view: GUI::drawFXAA (include/dmslam_render_shaded.h) -----------------------------------------------------
+lib.dms_render_offscreen_create.argtypes = [C.POINTER(_P), _I, _I]
+lib.dms_render_offscreen_destroy.argtypes = [_P]
+lib.dms_render_shaded_draw.argtypes = [_P, _P, C.POINTER(RenderParams), C.POINTER(C.c_float), _F, C.POINTER(C.c_float), _P]
+lib.dms_render_fxaa.argtypes = [_P, _P, _P]
+lib.dms_render_offscreen_images.argtypes = [_P, _I2, _I2, _I2]
+OFFSCREEN_SIZE = (3840, 2160)  # the GUI's offscreen buffer (GUI.h:57)
+
+
+def fxaa_clear_colour(showcaseMode=False):
+    """drawFXAA's clear colour (GUI.h:374-377)"""
+    return (1.0, 1.0, 1.0, 0.0) if showcaseMode else (0.05, 0.05, 0.3, 0.0)
+
+
+class ShadedView:
+    """GUI::drawFXAA (GUI/src/Tools/GUI.h:365-478): an offscreen float buffer (default the GUI's 3840 x 2160) and the W x H view it
+    is resolved into (a RenderTarget, `self.target`).  draw() is stage A (Phong into the buffer), fxaa() stage B (FXAA into the view,
+    then the depth blit); drawFXAA() is the GUI's call.  Rows are window rows (row 0 = bottom)."""
+
+    def __init__(self, width, height, offscreen=OFFSCREEN_SIZE):
+        self.target = RenderTarget(width, height)
+        self.width, self.height = self.target.width, self.target.height
+        self.off_width, self.off_height = int(offscreen[0]), int(offscreen[1])
+        h = C.c_void_p()
+        check(lib.dms_render_offscreen_create(C.byref(h), self.off_width, self.off_height), "dms_render_offscreen_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib.dms_render_offscreen_destroy(self.h)
+            self.h = None
+        if getattr(self, "target", None) is not None:
+            self.target.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clear(self, rgba=(0.0, 0.0, 0.0, 0.0), stream=None):
+        """glClear of the view (the GUI clears it before the maps are drawn)"""
+        self.target.clear(rgba, stream)
+
+    def draw(self, model, mvp=None, light_pos=(0.0, 0.0, 0.0), sign_mult=-1.0, clear_rgba=fxaa_clear_colour(), threshold=0.0,
+             draw_unstable=False, draw_window=False, color_type=0, time=0, time_idx=0, time_delta=0, pose_dev=None, stream=None):
+        """Stage A (dms_render_shaded_draw): clear the buffer, draw `model` with the Phong program.  With pose_dev, `mvp` is the
+        projection and the view is built on the device."""
+        p = RenderParams()
+        m = np.ascontiguousarray(np.eye(4, dtype=np.float32) if mvp is None else mvp, np.float32).reshape(16)
+        for k in range(16):
+            p.mvp[k] = float(m[k])
+        p.pose_dev = pose_dev
+        p.threshold = float(threshold)
+        p.draw_unstable, p.draw_window = int(bool(draw_unstable)), int(bool(draw_window))
+        p.color_type, p.time, p.time_idx, p.time_delta = int(color_type), int(time), int(time_idx), int(time_delta)
+        lp = (C.c_float * 3)(*[float(v) for v in light_pos])
+        cc = (C.c_float * 4)(*[float(v) for v in clear_rgba])
+        h = model.h if isinstance(model, GlobalModel) else C.c_void_p(model)
+        check(lib.dms_render_shaded_draw(self.h, h, C.byref(p), lp, float(sign_mult), cc, stream), "dms_render_shaded_draw")
+
+    def fxaa(self, stream=None):
+        """Stage B (dms_render_fxaa): the buffer through FXAA into the view, then its depth and winners blitted over the view's"""
+        check(lib.dms_render_fxaa(self.target.h, self.h, stream), "dms_render_fxaa")
+
+    def drawFXAA(self, mvp, mv, model, threshold, time, timeIdx, timeDelta, invertNormals, drawNormals=False, drawColors=False,
+                 drawTimes=False, drawUnstable=False, drawWindow=False, showcaseMode=False, stream=None):
+        """GUI::drawFXAA with the reference's arguments in the reference's order, then the GUI's toggles.  mvp and mv are row-major
+        (pangolin's OpenGlMatrix transposed); lightpos is mv's translation column (GUI.h:404-408), signMult +1 with invertNormals,
+        else -1 (:393).  timeIdx is the call's own (GUI.h:389 passes `time`)."""
+        mv = np.asarray(mv, np.float32).reshape(4, 4)
+        ct = color_type(drawNormals, drawColors, drawTimes)
+        self.draw(model, mvp, mv[:3, 3], 1.0 if invertNormals else -1.0, fxaa_clear_colour(showcaseMode), threshold, drawUnstable,
+                  drawWindow, ct, time, timeIdx, timeDelta, stream=stream)
+        self.fxaa(stream)
+
+    def offscreen_images(self, stream=None):
+        """(rgba f32 HxWx4, depth24 u32 HxW, winner key u64 HxW) of the offscreen buffer"""
+        check(lib.dms_stream_sync(stream), "dms_stream_sync")
+        c, d, w = Image2D(), Image2D(), Image2D()
+        check(lib.dms_render_offscreen_images(self.h, C.byref(c), C.byref(d), C.byref(w)), "dms_render_offscreen_images")
+        return capi.download_view(c, np.float32, 4), capi.download_view(d, np.uint32), capi.download_view(w, np.uint64)
+
+    def images(self, image_order=False, stream=None):
+        """the view's (rgba u8, depth24 u32, winner key u64), as RenderTarget.images"""
+        return self.target.images(image_order, stream)
