@@ -119,6 +119,21 @@ class ContextT {
   void computeFeedbackBuffers(const int& /*maxDepthProcessed*/) {
     if (fusion && dms_fusion_compute_feedback(fusion, nullptr) != DMS_OK) throw std::runtime_error(dms_last_error());
   }
+  // Context::feedbackBuffers() (Context.h:235-237): the RAW and FILTERED live-frame clouds, for
+  // feedbackBuffers().at(FeedbackBuffer::RAW)->render(mvp, pose, drawNormals, drawColors) (MainController.cpp:479-491); they draw into
+  // the target bound with bindRenderTarget (the reference draws into whatever GL framebuffer is bound)
+  std::map<std::string, FeedbackBuffer*>& feedbackBuffers() {
+    if (m_feedbackBuffers.empty()) {
+      m_raw.reset(new FeedbackBuffer(&fusion, DMS_CLOUD_RAW));
+      m_filtered.reset(new FeedbackBuffer(&fusion, DMS_CLOUD_FILTERED));
+      m_feedbackBuffers[FeedbackBuffer::RAW] = m_raw.get();
+      m_feedbackBuffers[FeedbackBuffer::FILTERED] = m_filtered.get();
+    }
+    return m_feedbackBuffers;
+  }
+  void bindRenderTarget(dms_render_target* t, dms_stream s = nullptr) {
+    for (auto& kv : feedbackBuffers()) kv.second->bindRenderTarget(t, s);
+  }
   bool& lost() { return m_lost; }
   // Context::fillIn() (Context.h; FillIn.h:33-35: vertexTexture / normalTexture / imageTexture): views of the context's fill-in
   // images in HBM, what the inter-map block hands to resolveRelativeTransformationFern (ElasticFusion.cpp:601-603)
@@ -183,6 +198,8 @@ class ContextT {
   std::vector<std::pair<unsigned long long int, Mat4>> m_poseGraph;
   std::vector<int64_t> m_poseLogTimes;
   std::unique_ptr<FillInTextures> m_fillIn;
+  std::unique_ptr<FeedbackBuffer> m_raw, m_filtered;
+  std::map<std::string, FeedbackBuffer*> m_feedbackBuffers;
 };
 
 // The deformation graphs stay with the caller (their optimisation is CPU + CHOLMOD, SURVEY 8 "out of scope"); what the reference's
@@ -654,4 +671,5 @@ class ElasticFusionT {
 // the reference's names (DMS_EIGEN_MATRIX4F_DECLARED: a build without Eigen that declares its own Eigen::Matrix4f stand-in)
 typedef dms::ElasticFusionT<Eigen::Matrix4f> ElasticFusion;
 typedef dms::ContextT<Eigen::Matrix4f> Context;
+typedef dms::FeedbackBuffer FeedbackBuffer;
 #endif

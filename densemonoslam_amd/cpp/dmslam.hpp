@@ -14,6 +14,7 @@
 //   ElasticFusion::processFrame (ElasticFusion.h:92-100)       -> dms::ElasticFusion::processFrame
 //   Ferns        (Core/src/Ferns.h:35-266)                     -> dms::Ferns
 //   GUI::drawFXAA (GUI/src/Tools/GUI.h:365-478)                -> dms::ShadedView::drawFXAA
+//   FeedbackBuffer::render (Shaders/FeedbackBuffer.cpp:145-187) -> dms::FeedbackBuffer::render
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -24,6 +25,7 @@
 #include "../../include/dmslam_ferns.h"
 #include "../../include/dmslam_fusion.h"
 #include "../../include/dmslam_render.h"
+#include "../../include/dmslam_render_cloud.h"
 #include "../../include/dmslam_render_shaded.h"
 
 namespace dms {
@@ -241,6 +243,57 @@ class ShadedView {
   dms_render_target* target = nullptr;
   dms_render_offscreen* offscreen = nullptr;
   dms_stream stream = nullptr;
+};
+
+// FeedbackBuffer (Shaders/FeedbackBuffer.h): the RAW or FILTERED live-frame cloud of one camera, for its render().  The buffer's
+// content is the context's (dms_fusion_compute_feedback); like GlobalModel it draws into a bound dms_render_target.
+template <class Dummy>
+struct FeedbackBufferNames {
+  static const std::string RAW, FILTERED;
+};
+template <class Dummy>
+const std::string FeedbackBufferNames<Dummy>::RAW = "RAW";
+template <class Dummy>
+const std::string FeedbackBufferNames<Dummy>::FILTERED = "FILTERED";
+
+class FeedbackBuffer : public FeedbackBufferNames<void> {
+ public:
+  // ctx: where the owning camera keeps its dms_fusion (created by its first frame); which: DMS_CLOUD_RAW / DMS_CLOUD_FILTERED
+  FeedbackBuffer(dms_fusion* const* ctx, int which) : ctx(ctx), which(which) {}
+  void bindRenderTarget(dms_render_target* t, dms_stream s = nullptr) {
+    target = t;
+    target_stream = s;
+  }
+  // FeedbackBuffer::render(mvp, pose, drawNormals, drawColors) with the reference's argument types: mvp a pangolin::OpenGlMatrix
+  // (anything with a column-major m[16]), transposed here as for the map draw; pose an Eigen::Matrix4f (anything with (r, c))
+  template <class GlMatrix, class Mat4>
+  void render(const GlMatrix& mvp, const Mat4& pose, const bool drawNormals, const bool drawColors) {
+    float mvp16[16], pose16[16];
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 4; ++c) {
+        mvp16[4 * r + c] = (float)mvp.m[4 * c + r];
+        pose16[4 * r + c] = pose(r, c);
+      }
+    render16(mvp16, pose16, drawNormals, drawColors);
+  }
+  // the same with row-major arrays
+  void render16(const float* mvp16, const float* pose16, const bool drawNormals, const bool drawColors) {
+    if (!target) throw std::runtime_error("FeedbackBuffer::render: no render target bound (bindRenderTarget)");
+    if (!*ctx) throw std::runtime_error("FeedbackBuffer::render: the camera has not processed a frame yet");
+    dms_render_cloud_params p = {};
+    for (int k = 0; k < 16; ++k) {
+      p.mvp[k] = mvp16[k];
+      p.model_pose[k] = pose16[k];
+    }
+    p.color_type = drawNormals ? 1 : drawColors ? 2 : 0;  // FeedbackBuffer.cpp:154
+    check(dms_fusion_render_cloud(target, *ctx, which, &p, target_stream), "FeedbackBuffer::render");
+  }
+  dms_render_target* target = nullptr;
+  dms_stream target_stream = nullptr;
+
+ private:
+  dms_fusion* const* ctx;
+  int which;
 };
 
 // IndexMap (IndexMap.h:39-162): the render targets of one camera and the three "draws" over a GlobalModel.

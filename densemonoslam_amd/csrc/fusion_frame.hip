@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/dmslam_render_cloud.h"
 #include "internal.hpp"
 #include "smallmath.hpp"
 #include "surfel.hpp"
@@ -898,6 +899,16 @@ int dms_fusion_compute_feedback(dms_fusion* f, dms_stream st) {
   DMS_REQUIRE(f, "null argument");
   DMS_REQUIRE(!f->in_frame && f->frames > 0, "computeFeedbackBuffers: between frames, after the first");
   return snapshot_feedback(f, (hipStream_t)st);
+}
+
+// FeedbackBuffer::render of the context's RAW / FILTERED buffer (MainController.cpp:475-493): the kept inputs, drawn by render.hip
+int dms_fusion_render_cloud(dms_render_target* t, dms_fusion* f, int which, const dms_render_cloud_params* p, dms_stream st) {
+  DMS_REQUIRE(t && f && p, "null argument");
+  DMS_REQUIRE(which == DMS_CLOUD_RAW || which == DMS_CLOUD_FILTERED, "which must be DMS_CLOUD_RAW or DMS_CLOUD_FILTERED");
+  DMS_REQUIRE(!f->in_frame, "between frames only");
+  DMS_REQUIRE(f->fb_valid, "no feedback buffers (before the first frame)");
+  // computeFeedbackBuffers takes `const int& maxDepthProcessed` (Context.h:211): 25.0f -> 25
+  return dms_render_cloud(t, &f->fb_rgba, which == DMS_CLOUD_RAW ? &f->fb_dm : &f->fb_dmf, &f->cam, (float)(int)f->p.maxDepthProcessed, p, st);
 }
 
 int dms_fusion_set_cluster(dms_fusion* f, int cluster) {

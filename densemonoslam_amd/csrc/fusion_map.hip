@@ -276,30 +276,7 @@ struct BootArgs {
   float maxDepth;
 };
 
-// geometry.glsl:19-39: vertex / central-difference normal on a float depth map.
-// texcoords are the uv-buffer values; x = tx * cols, y = ty * rows.
-__device__ __forceinline__ f3 fb_vertex(const float* depth, int cols, int sx, int sy, float x, float y, float cx, float cy, float ifx,
-                                        float ify) {
-  const float z = depth[(size_t)sy * cols + sx];
-  return mk3(((x - cx) * z) * ifx, ((y - cy) * z) * ify, z);
-}
-
-__device__ __forceinline__ f3 fb_normal(const float* depth, int cols, int rows, const f3& vPosition, float tx, float ty, float x, float y,
-                                        float cx, float cy, float ifx, float ify) {
-  const float colsf = (float)cols, rowsf = (float)rows;
-  const int sx = texel(tx, colsf, cols), sy = texel(ty, rowsf, rows);
-  const int sxf = texel(tx + (1.0f / colsf), colsf, cols), sxb = texel(tx - (1.0f / colsf), colsf, cols);
-  const int syf = texel(ty + (1.0f / rowsf), rowsf, rows), syb = texel(ty - (1.0f / rowsf), rowsf, rows);
-  const f3 xf = fb_vertex(depth, cols, sxf, sy, x + 1.f, y, cx, cy, ifx, ify);
-  const f3 xb = fb_vertex(depth, cols, sxb, sy, x - 1.f, y, cx, cy, ifx, ify);
-  const f3 yf = fb_vertex(depth, cols, sx, syf, x, y + 1.f, cx, cy, ifx, ify);
-  const f3 yb = fb_vertex(depth, cols, sx, syb, x, y - 1.f, cx, cy, ifx, ify);
-  const f3 del_x = mk3(((xb.x + vPosition.x) / 2.f) - ((xf.x + vPosition.x) / 2.f), ((xb.y + vPosition.y) / 2.f) - ((xf.y + vPosition.y) / 2.f),
-                       ((xb.z + vPosition.z) / 2.f) - ((xf.z + vPosition.z) / 2.f));
-  const f3 del_y = mk3(((yb.x + vPosition.x) / 2.f) - ((yf.x + vPosition.x) / 2.f), ((yb.y + vPosition.y) / 2.f) - ((yf.y + vPosition.y) / 2.f),
-                       ((yb.z + vPosition.z) / 2.f) - ((yf.z + vPosition.z) / 2.f));
-  return normalized3(cross3(del_x, del_y));
-}
+// (fb_vertex / fb_normal, geometry.glsl:19-39, live in surfel.hpp: the cloud draw of render.hip shares them)
 
 // element e = column-major pixel (x = e / rows, y = e % rows): GlobalModel.cpp:100-108 order
 __global__ __launch_bounds__(256) void k_boot_flags(BootArgs a, unsigned char* __restrict__ keep, unsigned* __restrict__ block_count) {

@@ -12,6 +12,7 @@
 #include "surfel.hpp"
 #include "../../include/dmslam_render.h"
 #include "../../include/dmslam_render_shaded.h"
+#include "../../include/dmslam_render_cloud.h"
 
 using namespace dms;
 
@@ -418,6 +419,21 @@ __global__ __launch_bounds__(256) void k_render_discs(RenderArgs a, SurfelPlanes
   }
 }
 
+// R2 / R3 of a size-1 point at clip position c: the target pixel and the 64-bit key compete by atomicMin (order-free)
+__device__ __forceinline__ void place_point(const c4& c, int W, int H, float hw, float hh, unsigned long long key_lo,
+                                            unsigned long long* __restrict__ zbuf) {
+  if (!(c.w > 0.f)) return;
+  const float xn = c.x / c.w, yn = c.y / c.w, zn = c.z / c.w;
+  if (!(xn >= -1.f && xn <= 1.f && yn >= -1.f && yn <= 1.f && zn >= -1.f && zn <= 1.f)) return;
+  const int px = (int)floorf((xn + 1.f) * hw), py = (int)floorf((yn + 1.f) * hh);
+  if (px < 0 || py < 0 || px >= W || py >= H) return;
+  const unsigned d = depth24(zn * 0.5f + 0.5f);
+  if (d >= 0xFFFFFFu) return;
+  const unsigned long long key = ((unsigned long long)d << 40) | key_lo;
+  unsigned long long* cell = zbuf + (size_t)py * W + px;
+  if (key < *cell) atomicMin(cell, key);
+}
+
 // Pass 1 of the point program (draw_feedback.vert:47-72): one size-1 point per surfel with conf > threshold, placed by R2
 __global__ __launch_bounds__(256) void k_render_points(RenderArgs a, SurfelPlanes sp, const unsigned* __restrict__ d_count,
                                                        unsigned long long* __restrict__ zbuf) {
@@ -427,17 +443,7 @@ __global__ __launch_bounds__(256) void k_render_points(RenderArgs a, SurfelPlane
   for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += blockDim.x * gridDim.x) {
     const float4 pc = sp.pos[i];
     if (!(pc.w > a.threshold)) continue;
-    const c4 c = clip_of(Mv, pc.x, pc.y, pc.z);
-    if (!(c.w > 0.f)) continue;
-    const float xn = c.x / c.w, yn = c.y / c.w, zn = c.z / c.w;
-    if (!(xn >= -1.f && xn <= 1.f && yn >= -1.f && yn <= 1.f && zn >= -1.f && zn <= 1.f)) continue;
-    const int px = (int)floorf((xn + 1.f) * a.hw), py = (int)floorf((yn + 1.f) * a.hh);
-    if (px < 0 || py < 0 || px >= a.W || py >= a.H) continue;
-    const unsigned d = depth24(zn * 0.5f + 0.5f);
-    if (d >= 0xFFFFFFu) continue;
-    const unsigned long long key = ((unsigned long long)d << 40) | ((unsigned long long)a.seq << 32) | (unsigned long long)i;
-    unsigned long long* cell = zbuf + (size_t)py * a.W + px;
-    if (key < *cell) atomicMin(cell, key);
+    place_point(clip_of(Mv, pc.x, pc.y, pc.z), a.W, a.H, a.hw, a.hh, ((unsigned long long)a.seq << 32) | (unsigned long long)i, zbuf);
   }
 }
 
@@ -731,6 +737,96 @@ __global__ __launch_bounds__(256) void k_render_fxaa(const float4* __restrict__ 
   }
 }
 
+// ---- the live-frame clouds: FeedbackBuffer::render (include/dmslam_render_cloud.h) ----------------------------
+// The reference fills a 60-byte vertex per pixel (vertex_feedback.{vert,geom}) and draws that buffer with the point program.  Here no
+// buffer is made: pass 1 runs the emit test and the position of every source pixel and competes for the target pixel like
+// k_render_points; pass 2 rebuilds, for the pixels this draw won, what the colour mode reads - the colour bytes, or the
+// central-difference normal from the SAME depth image - from the source pixel e = x * rows + y held in the key.
+struct CloudArgs {
+  float mvp[16];
+  const float* pose_dev;   // the view, as RenderArgs
+  float model[16];         // the program's `pose` uniform
+  const float* model_dev;  // the same in HBM (overrides model)
+  const uchar4* rgba;
+  const float* depth;  // metric; rows tightly packed
+  int cols, rows;
+  float cx, cy, ifx, ify, maxDepth;
+  int W, H;
+  float hw, hh;
+  int colorType;
+  unsigned seq;
+};
+
+// R19: clip = MVP_eff * (pose * (p, 1)): two matrix-vector products, each row accumulated left to right, no 4 x 4 product
+__host__ __device__ inline c4 clip_of4(const float* M, const c4& v) {
+  c4 r;
+  r.x = ((M[0] * v.x + M[1] * v.y) + M[2] * v.z) + M[3] * v.w;
+  r.y = ((M[4] * v.x + M[5] * v.y) + M[6] * v.z) + M[7] * v.w;
+  r.z = ((M[8] * v.x + M[9] * v.y) + M[10] * v.z) + M[11] * v.w;
+  r.w = ((M[12] * v.x + M[13] * v.y) + M[14] * v.z) + M[15] * v.w;
+  return r;
+}
+__host__ __device__ inline c4 cloud_clip(const float* V, const float* P, float x, float y, float z) {
+  c4 p1;
+  p1.x = x, p1.y = y, p1.z = z, p1.w = 1.f;
+  return clip_of4(V, clip_of4(P, p1));
+}
+// the launch's view (as launch_mvp) and model matrix
+__device__ __forceinline__ void cloud_matrices(const CloudArgs& a, float* V, float* P) {
+  if (a.pose_dev) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) P[k] = a.pose_dev[k];
+    mvp_from_pose(a.mvp, P, V);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) V[k] = a.mvp[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 16; ++k) P[k] = a.model_dev ? a.model_dev[k] : a.model[k];
+}
+
+// Pass 1, one thread per source pixel (row-major: coalesced depth reads; the atomicMin does not care about the order)
+__global__ __launch_bounds__(256) void k_cloud_points(CloudArgs a, unsigned long long* __restrict__ zbuf) {
+  float V[16], P[16];
+  cloud_matrices(a, V, P);
+  const int n = a.cols * a.rows;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += blockDim.x * gridDim.x) {
+    const float z = a.depth[p];
+    if (!(z > 0.f && !(z > a.maxDepth))) continue;  // vertex_feedback.vert:55-62 + .geom:38: emitted iff 0 < z <= maxDepth
+    const int py = p / a.cols, px = p - py * a.cols;
+    const float x = uv_coord(px, a.cols) * (float)a.cols, y = uv_coord(py, a.rows) * (float)a.rows;
+    if (!(surfel_confidence(x, y, a.cx, a.cy, 1.0f) > 0.f)) continue;  // draw_feedback.vert:37, threshold 0
+    const f3 v = fb_vertex(a.depth, a.cols, px, py, x, y, a.cx, a.cy, a.ifx, a.ify);
+    const unsigned e = (unsigned)px * (unsigned)a.rows + (unsigned)py;  // R21
+    place_point(cloud_clip(V, P, v.x, v.y, v.z), a.W, a.H, a.hw, a.hh, ((unsigned long long)a.seq << 32) | (unsigned long long)e, zbuf);
+  }
+}
+
+// Pass 2, per target pixel this draw won (draw_feedback.vert:39-54 for the winner's source pixel)
+__global__ __launch_bounds__(256) void k_cloud_resolve(CloudArgs a, const unsigned long long* __restrict__ zbuf, unsigned* __restrict__ color,
+                                                       unsigned* __restrict__ depth) {
+  const int n = a.W * a.H;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += blockDim.x * gridDim.x) {
+    const unsigned long long key = zbuf[p];
+    if (key == ~0ull || (unsigned)((key >> 32) & 0xFFu) != a.seq) continue;
+    const unsigned e = (unsigned)(key & 0xFFFFFFFFull);
+    const int px = (int)(e / (unsigned)a.rows), py = (int)(e - (unsigned)px * (unsigned)a.rows);
+    f3 c;
+    if (a.colorType == 2) {
+      const uchar4 b = a.rgba[(size_t)py * a.cols + px];
+      c = decode_color(encode_color_bytes(b.x, b.y, b.z));  // vertex_feedback.vert:68, draw_feedback.vert:49
+    } else {
+      const float tx = uv_coord(px, a.cols), ty = uv_coord(py, a.rows);
+      const float x = tx * (float)a.cols, y = ty * (float)a.rows;
+      const f3 v = fb_vertex(a.depth, a.cols, px, py, x, y, a.cx, a.cy, a.ifx, a.ify);
+      const f3 nl = fb_normal(a.depth, a.cols, a.rows, v, tx, ty, x, y, a.cx, a.cy, a.ifx, a.ify);  // R20: NEAREST taps
+      c = a.colorType == 1 ? nl : shaded_grey(make_float4(nl.x, nl.y, nl.z, 0.f));
+    }
+    color[p] = rgba8(c);
+    depth[p] = (unsigned)(key >> 40);
+  }
+}
+
 int surfel_blocks(size_t upper) {
   size_t b = (upper + 255) / 256;
   if (b < 1) b = 1;
@@ -1000,6 +1096,59 @@ int dms_render_offscreen_images(dms_render_offscreen* o, dms_image2d* rgba32f, d
   if (rgba32f) *rgba32f = dms_image2d{o->rgba, (size_t)o->width * 16, o->height, o->width};
   if (depth24_u32) *depth24_u32 = dms_image2d{o->depth, (size_t)o->width * 4, o->height, o->width};
   if (winner_u64) *winner_u64 = dms_image2d{o->key, (size_t)o->width * 8, o->height, o->width};
+  return DMS_OK;
+}
+
+}  // extern "C"
+
+// ---- the live-frame clouds (include/dmslam_render_cloud.h) --------------------------------------------------------------------
+extern "C" {
+
+int dms_render_cloud_clip(const float mvp_eff16[16], const float model_pose16[16], const float point3[3], float clip4[4]) {
+  DMS_REQUIRE(mvp_eff16 && model_pose16 && point3 && clip4, "null argument");
+  const c4 c = cloud_clip(mvp_eff16, model_pose16, point3[0], point3[1], point3[2]);
+  clip4[0] = c.x, clip4[1] = c.y, clip4[2] = c.z, clip4[3] = c.w;
+  return DMS_OK;
+}
+
+int dms_render_cloud(dms_render_target* t, const dms_image2d* rgba, const dms_image2d* depth_metric, const dms_camera* cam, float max_depth,
+                     const dms_render_cloud_params* p, dms_stream s) {
+  DMS_REQUIRE(t && rgba && depth_metric && cam && p, "null argument");
+  DMS_REQUIRE(rgba->data && depth_metric->data, "null image");
+  DMS_REQUIRE(depth_metric->cols > 0 && depth_metric->rows > 0 && rgba->cols == depth_metric->cols && rgba->rows == depth_metric->rows,
+              "shape mismatch");
+  DMS_REQUIRE(rgba->pitch == (size_t)rgba->cols * 4 && depth_metric->pitch == (size_t)depth_metric->cols * 4, "rows must be tightly packed");
+  // (2^30 pixels: the grid-stride index of pass 1 and the source index e of the key stay far inside 31 bits)
+  DMS_REQUIRE((long long)depth_metric->cols * depth_metric->rows <= DMS_CLOUD_MAX_PIXELS, "image too large");
+  DMS_REQUIRE(p->color_type >= 0 && p->color_type <= 2, "color_type must be 0..2");
+  DMS_REQUIRE(t->seq < DMS_RENDER_MAX_DRAWS, "too many draws since the last clear");
+  CloudArgs a;
+  memcpy(a.mvp, p->mvp, sizeof(a.mvp));
+  a.pose_dev = p->pose_dev;
+  memcpy(a.model, p->model_pose, sizeof(a.model));
+  a.model_dev = p->model_pose_dev;
+  a.rgba = (const uchar4*)rgba->data;
+  a.depth = (const float*)depth_metric->data;
+  a.cols = depth_metric->cols;
+  a.rows = depth_metric->rows;
+  a.cx = cam->cx;
+  a.cy = cam->cy;
+  a.ifx = 1.0f / cam->fx;  // cam = (cx, cy, 1/fx, 1/fy), float reciprocals (FeedbackBuffer.cpp:93-96)
+  a.ify = 1.0f / cam->fy;
+  a.maxDepth = max_depth;
+  a.W = t->width;
+  a.H = t->height;
+  a.hw = (float)t->width * 0.5f;
+  a.hh = (float)t->height * 0.5f;
+  a.colorType = p->color_type;
+  a.seq = (unsigned)t->seq;
+  const hipStream_t st = (hipStream_t)s;
+  const int ns = a.cols * a.rows, n = t->width * t->height;
+  hipLaunchKernelGGL(k_cloud_points, dim3(min((ns + 255) / 256, 2048)), dim3(256), 0, st, a, t->key);
+  DMS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_cloud_resolve, dim3(min((n + 255) / 256, 2048)), dim3(256), 0, st, a, t->key, t->color, t->depth);
+  DMS_CHECK_LAUNCH();
+  ++t->seq;
   return DMS_OK;
 }
 

@@ -128,6 +128,31 @@ __host__ __device__ __forceinline__ float uv_coord(int i, int n) {
   return (float)((double)((float)i / (float)n) + 1.0 / (double)(2.0f * (float)n));
 }
 
+// geometry.glsl:19-39: vertex / central-difference normal on a float depth map.
+// texcoords are the uv-buffer values; x = tx * cols, y = ty * rows.
+__device__ __forceinline__ f3 fb_vertex(const float* depth, int cols, int sx, int sy, float x, float y, float cx, float cy, float ifx,
+                                        float ify) {
+  const float z = depth[(size_t)sy * cols + sx];
+  return mk3(((x - cx) * z) * ifx, ((y - cy) * z) * ify, z);
+}
+
+__device__ __forceinline__ f3 fb_normal(const float* depth, int cols, int rows, const f3& vPosition, float tx, float ty, float x, float y,
+                                        float cx, float cy, float ifx, float ify) {
+  const float colsf = (float)cols, rowsf = (float)rows;
+  const int sx = texel(tx, colsf, cols), sy = texel(ty, rowsf, rows);
+  const int sxf = texel(tx + (1.0f / colsf), colsf, cols), sxb = texel(tx - (1.0f / colsf), colsf, cols);
+  const int syf = texel(ty + (1.0f / rowsf), rowsf, rows), syb = texel(ty - (1.0f / rowsf), rowsf, rows);
+  const f3 xf = fb_vertex(depth, cols, sxf, sy, x + 1.f, y, cx, cy, ifx, ify);
+  const f3 xb = fb_vertex(depth, cols, sxb, sy, x - 1.f, y, cx, cy, ifx, ify);
+  const f3 yf = fb_vertex(depth, cols, sx, syf, x, y + 1.f, cx, cy, ifx, ify);
+  const f3 yb = fb_vertex(depth, cols, sx, syb, x, y - 1.f, cx, cy, ifx, ify);
+  const f3 del_x = mk3(((xb.x + vPosition.x) / 2.f) - ((xf.x + vPosition.x) / 2.f), ((xb.y + vPosition.y) / 2.f) - ((xf.y + vPosition.y) / 2.f),
+                       ((xb.z + vPosition.z) / 2.f) - ((xf.z + vPosition.z) / 2.f));
+  const f3 del_y = mk3(((yb.x + vPosition.x) / 2.f) - ((yf.x + vPosition.x) / 2.f), ((yb.y + vPosition.y) / 2.f) - ((yf.y + vPosition.y) / 2.f),
+                       ((yb.z + vPosition.z) / 2.f) - ((yf.z + vPosition.z) / 2.f));
+  return normalized3(cross3(del_x, del_y));
+}
+
 // G8: update (update.vert:42-104) of surfel `id` by its winning measurement `slot`, in place
 __device__ __forceinline__ void fuse_update_apply(unsigned id, unsigned slot, const float4* __restrict__ slot_pos, const float4* __restrict__ slot_col,
                                                   const float4* __restrict__ slot_nrm, const SurfelPlanes& sp, size_t cap, int time, int timeIdx) {

@@ -602,6 +602,17 @@ class ElasticFusion:
     def computeFeedbackBuffers(self, stream=None):
         check(lib.dms_fusion_compute_feedback(self.h, stream), "dms_fusion_compute_feedback")
 
+    def renderCloud(self, target, which, mvp=None, model_pose=None, color_type=0, pose_dev=None, model_pose_dev=None, stream=None):
+        """One live-frame cloud (dms_fusion_render_cloud) into `target` (a RenderTarget): which = CLOUD_RAW / CLOUD_FILTERED of the
+        feedback inputs; model_pose (host 4 x 4, default identity) or model_pose_dev (device address, e.g. poseDevice()) is the
+        program's `pose`; mvp / pose_dev are the view as in RenderTarget.draw."""
+        p = _cloud_params(mvp, model_pose, color_type, pose_dev, model_pose_dev)
+        check(lib.dms_fusion_render_cloud(target.h, self.h, int(which), C.byref(p), stream), "dms_fusion_render_cloud")
+
+    def feedbackBuffers(self):
+        """Context::feedbackBuffers(): {FeedbackBuffer.RAW: ..., FeedbackBuffer.FILTERED: ...}"""
+        return {FeedbackBuffer.RAW: FeedbackBuffer(self, CLOUD_RAW), FeedbackBuffer.FILTERED: FeedbackBuffer(self, CLOUD_FILTERED)}
+
     def clusters(self):
         """(ids, current id)"""
         ids = (C.c_int * 64)()
@@ -885,3 +896,60 @@ class ShadedView:
     def images(self, image_order=False, stream=None):
         """the view's (rgba u8, depth24 u32, winner key u64), as RenderTarget.images"""
         return self.target.images(image_order, stream)
+
+
+# ---- the live-frame clouds: FeedbackBuffer::render (include/dmslam_render_cloud.h) ------------------------------------------
+CLOUD_RAW, CLOUD_FILTERED = 0, 1
+
+
+class RenderCloudParams(C.Structure):
+    """dms_render_cloud_params"""
+    _fields_ = [("mvp", C.c_float * 16), ("pose_dev", _P), ("model_pose", C.c_float * 16), ("model_pose_dev", _P), ("color_type", _I)]
+
+
+lib.dms_render_cloud_clip.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+lib.dms_render_cloud.argtypes = [_P, _I2, _I2, _K, _F, C.POINTER(RenderCloudParams), _P]
+lib.dms_fusion_render_cloud.argtypes = [_P, _P, _I, C.POINTER(RenderCloudParams), _P]
+
+
+def _cloud_params(mvp, model_pose, color_type, pose_dev, model_pose_dev):
+    p = RenderCloudParams()
+    m = np.ascontiguousarray(np.eye(4, dtype=np.float32) if mvp is None else mvp, np.float32).reshape(16)
+    t = np.ascontiguousarray(np.eye(4, dtype=np.float32) if model_pose is None else model_pose, np.float32).reshape(16)
+    for k in range(16):
+        p.mvp[k], p.model_pose[k] = float(m[k]), float(t[k])
+    p.pose_dev, p.model_pose_dev, p.color_type = pose_dev, model_pose_dev, int(color_type)
+    return p
+
+
+def render_cloud_clip(mvp_eff, model_pose, point):
+    """mvp_eff * (model_pose * (point, 1)) in the draw's fp32 order (dms_render_cloud_clip): the clip position (x, y, z, w)."""
+    (_a, ap), (_b, bp) = _f16(mvp_eff), _f16(model_pose)
+    pt = (C.c_float * 3)(*[float(v) for v in point])
+    out = (C.c_float * 4)()
+    check(lib.dms_render_cloud_clip(ap, bp, pt, out), "dms_render_cloud_clip")
+    return np.array(out[:], np.float32)
+
+
+def render_cloud(target, rgba, depth_metric, K, max_depth, mvp=None, model_pose=None, color_type=0, pose_dev=None, model_pose_dev=None,
+                 stream=None):
+    """One cloud over any colour (H x W x 4 u8) and metric depth (H x W f32) image - arrays or DeviceImages - with intrinsics
+    K = (fx, fy, cx, cy): dms_render_cloud."""
+    c, dm = _img(rgba, np.uint8), _img(depth_metric, np.float32)
+    k = _cam(K)
+    p = _cloud_params(mvp, model_pose, color_type, pose_dev, model_pose_dev)
+    check(lib.dms_render_cloud(target.h, c.ref, dm.ref, C.byref(k), float(max_depth), C.byref(p), stream), "dms_render_cloud")
+    if not isinstance(rgba, DeviceImage) or not isinstance(depth_metric, DeviceImage):
+        check(lib.dms_stream_sync(stream))  # the temporary uploads must outlive the draw
+
+
+class FeedbackBuffer:
+    """FeedbackBuffer (Shaders/FeedbackBuffer.h) of a context, for its render(): ctx.feedbackBuffers()[FeedbackBuffer.RAW]."""
+    RAW, FILTERED = "RAW", "FILTERED"
+
+    def __init__(self, context, which):
+        self.context, self.which = context, which
+
+    def render(self, mvp, pose, drawNormals, drawColors, target, pose_dev=None, model_pose_dev=None, stream=None):
+        """FeedbackBuffer::render(mvp, pose, drawNormals, drawColors) into `target` (mvp row-major: transpose pangolin's)."""
+        self.context.renderCloud(target, self.which, mvp, pose, 1 if drawNormals else 2 if drawColors else 0, pose_dev, model_pose_dev, stream)
