@@ -109,6 +109,7 @@ class ContextT {
     if (fusion) dms_fusion_destroy(fusion);
     if (rgb_dev) dms_device_free(rgb_dev);
     if (depth_dev) dms_device_free(depth_dev);
+    if (m_panels) dms_panels_destroy(m_panels);
   }
   ContextT(const ContextT&) = delete;
   const int& id() const { return m_id; }
@@ -133,6 +134,39 @@ class ContextT {
   }
   void bindRenderTarget(dms_render_target* t, dms_stream s = nullptr) {
     for (auto& kv : feedbackBuffers()) kv.second->bindRenderTarget(t, s);
+    m_panelStream = s;
+  }
+  // The image panels (MainController.cpp:649-664).  textures() (Context.h:231-233) has the two the GUI shows, RGB and DEPTH_NORM;
+  // indexMap() the ACTIVE prediction's renderDepth / drawTex / imageTex.  The two intermediates live in a dms_panels made on first use;
+  // the panel passes run on the stream given to bindRenderTarget.
+  dms_panels* panels() {
+    if (!fusion) throw std::runtime_error("Context: the camera has not processed a frame yet");
+    if (!m_panels) {
+      dms_image2d v;
+      if (dms_fusion_get_image(fusion, 0, &v) || dms_panels_create(&m_panels, v.cols, v.rows)) throw std::runtime_error(dms_last_error());
+    }
+    return m_panels;
+  }
+  std::map<std::string, GPUTexture*>& textures() {
+    dms_image2d rgb, norm;
+    if (dms_fusion_get_image(fusion, 0, &rgb) || dms_panels_images(panels(), &norm, nullptr))
+      throw std::runtime_error(dms_last_error());
+    m_texRgb = GPUTexture(rgb, DMS_PANEL_RGBA8, DMS_PANEL_LINEAR);
+    m_texNorm = GPUTexture(norm, DMS_PANEL_L8, DMS_PANEL_LINEAR);
+    m_textures[GPUTexture::RGB] = &m_texRgb;
+    m_textures[GPUTexture::DEPTH_NORM] = &m_texNorm;
+    return m_textures;
+  }
+  PanelIndexMap& indexMap() {
+    panels();
+    if (!m_indexMap) m_indexMap.reset(new PanelIndexMap(&fusion, &m_panels, &m_panelStream));
+    return *m_indexMap;
+  }
+  // ElasticFusion::normaliseDepth's body for this camera (ElasticFusion.cpp:770-779): the uniforms scaled by 1000.f
+  void normaliseDepth(const float& minVal, const float& maxVal) {
+    dms_image2d d;
+    if (dms_fusion_get_image(fusion, 1, &d) || dms_depth_norm(panels(), &d, minVal * 1000.f, maxVal * 1000.f, m_panelStream))
+      throw std::runtime_error(dms_last_error());
   }
   bool& lost() { return m_lost; }
   // Context::fillIn() (Context.h; FillIn.h:33-35: vertexTexture / normalTexture / imageTexture): views of the context's fill-in
@@ -200,6 +234,11 @@ class ContextT {
   std::unique_ptr<FillInTextures> m_fillIn;
   std::unique_ptr<FeedbackBuffer> m_raw, m_filtered;
   std::map<std::string, FeedbackBuffer*> m_feedbackBuffers;
+  dms_panels* m_panels = nullptr;
+  dms_stream m_panelStream = nullptr;
+  GPUTexture m_texRgb, m_texNorm;
+  std::map<std::string, GPUTexture*> m_textures;
+  std::unique_ptr<PanelIndexMap> m_indexMap;
 };
 
 // The deformation graphs stay with the caller (their optimisation is CPU + CHOLMOD, SURVEY 8 "out of scope"); what the reference's
@@ -540,6 +579,8 @@ class ElasticFusionT {
   }
   const int& getTimeDelta() const { return timeDelta; }
   const float& getConfidenceThreshold() const { return confidence; }
+  // ElasticFusion::normaliseDepth (ElasticFusion.cpp:770-779): depth_norm.frag over the context's raw depth into its DEPTH_NORM texture
+  void normaliseDepth(Context& context, const float& minVal, const float& maxVal) { context.normaliseDepth(minVal, maxVal); }
   const float& getMaxDepthProcessed() const { return FrontEndOptions::get().maxDepthProcessed; }
 
   // the GUI-driven setters (ElasticFusion.h:168-226, ElasticFusion.cpp:1023-1043; MainController.cpp:760-775 calls them every
@@ -672,4 +713,5 @@ class ElasticFusionT {
 typedef dms::ElasticFusionT<Eigen::Matrix4f> ElasticFusion;
 typedef dms::ContextT<Eigen::Matrix4f> Context;
 typedef dms::FeedbackBuffer FeedbackBuffer;
+typedef dms::GPUTexture GPUTexture;
 #endif

@@ -15,6 +15,7 @@
 //   Ferns        (Core/src/Ferns.h:35-266)                     -> dms::Ferns
 //   GUI::drawFXAA (GUI/src/Tools/GUI.h:365-478)                -> dms::ShadedView::drawFXAA
 //   FeedbackBuffer::render (Shaders/FeedbackBuffer.cpp:145-187) -> dms::FeedbackBuffer::render
+//   GUI::displayImg (GUI/src/Tools/GUI.h:340-350)                -> dms::displayImg(target, viewport, GPUTexture*)
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -26,6 +27,7 @@
 #include "../../include/dmslam_fusion.h"
 #include "../../include/dmslam_render.h"
 #include "../../include/dmslam_render_cloud.h"
+#include "../../include/dmslam_render_panels.h"
 #include "../../include/dmslam_render_shaded.h"
 
 namespace dms {
@@ -294,6 +296,64 @@ class FeedbackBuffer : public FeedbackBufferNames<void> {
  private:
   dms_fusion* const* ctx;
   int which;
+};
+
+// ---- the image panels (include/dmslam_render_panels.h; GUI/src/MainController.cpp:649-664) ---------------------------------------------
+// GPUTexture (GPUTexture.h) as GUI::displayImg sees one: a device image, its format, and the filter its `draw` flag selected
+// (Context.h:158-181: RGB and DEPTH_NORM LINEAR; IndexMap.cpp:42-65: drawTexture and imageTexture NEAREST).
+template <class Dummy>
+struct GPUTextureNames {
+  static const std::string RGB, DEPTH_RAW, DEPTH_NORM;
+};
+template <class Dummy>
+const std::string GPUTextureNames<Dummy>::RGB = "RGB";
+template <class Dummy>
+const std::string GPUTextureNames<Dummy>::DEPTH_RAW = "DEPTH";
+template <class Dummy>
+const std::string GPUTextureNames<Dummy>::DEPTH_NORM = "DEPTH_NORM";
+
+struct GPUTexture : public GPUTextureNames<void> {
+  GPUTexture() { view.data = nullptr, view.pitch = 0, view.rows = view.cols = 0; }
+  GPUTexture(const dms_image2d& v, int format, int filter) : view(v), format(format), filter(filter) {}
+  dms_image2d view;
+  int format = DMS_PANEL_RGBA8, filter = DMS_PANEL_NEAREST;
+};
+
+// GUI::displayImg (GUI/src/Tools/GUI.h:340-350) with the view's rectangle given instead of looked up in pangolin: the image upside
+// down over `vp` of `target`, times the current colour (the reference sets white just before, MainController.cpp:658)
+inline void displayImg(dms_render_target* target, const dms_viewport& vp, const GPUTexture* img, dms_stream s = nullptr, float r = 1.f,
+                       float g = 1.f, float b = 1.f) {
+  const float color[3] = {r, g, b};
+  check(dms_render_blit(target, &img->view, img->format, img->filter, &vp, color, s), "displayImg");
+}
+
+// what Context::indexMap() hands the GUI: renderDepth(depthCutoff), drawTex() and imageTex() of the camera's ACTIVE prediction
+class PanelIndexMap {
+ public:
+  PanelIndexMap(dms_fusion* const* ctx, dms_panels* const* panels, dms_stream const* stream) : ctx(ctx), panels(panels), stream(stream) {}
+  void renderDepth(const float depthCutoff) {  // IndexMap::renderDepth (IndexMap.cpp:219-251)
+    dms_image2d v;
+    check(dms_fusion_get_image(*ctx, 10, &v), "dms_fusion_get_image");
+    check(dms_model_depth_image(*panels, &v, depthCutoff, *stream), "IndexMap::renderDepth");
+  }
+  GPUTexture* drawTex() {
+    dms_image2d m;
+    check(dms_panels_images(*panels, nullptr, &m), "dms_panels_images");
+    draw = GPUTexture(m, DMS_PANEL_RGBA8, DMS_PANEL_NEAREST);
+    return &draw;
+  }
+  GPUTexture* imageTex() {
+    dms_image2d v;
+    check(dms_fusion_get_image(*ctx, 9, &v), "dms_fusion_get_image");
+    image = GPUTexture(v, DMS_PANEL_RGBA8, DMS_PANEL_NEAREST);
+    return &image;
+  }
+
+ private:
+  dms_fusion* const* ctx;
+  dms_panels* const* panels;
+  dms_stream const* stream;
+  GPUTexture draw, image;
 };
 
 // IndexMap (IndexMap.h:39-162): the render targets of one camera and the three "draws" over a GlobalModel.

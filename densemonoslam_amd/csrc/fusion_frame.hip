@@ -911,6 +911,15 @@ int dms_fusion_render_cloud(dms_render_target* t, dms_fusion* f, int which, cons
   return dms_render_cloud(t, &f->fb_rgba, which == DMS_CLOUD_RAW ? &f->fb_dm : &f->fb_dmf, &f->cam, (float)(int)f->p.maxDepthProcessed, p, st);
 }
 
+// the GUI's image column (MainController.cpp:649-664): normaliseDepth, renderDepth and the four displayImg calls, drawn by render.hip
+int dms_fusion_draw_panels(dms_render_target* t, dms_panels* p, dms_fusion* f, const dms_viewport viewports[4], float depth_cutoff,
+                           int which_mask, dms_stream st) {
+  DMS_REQUIRE(t && p && f && viewports, "null argument");
+  DMS_REQUIRE(!f->in_frame, "between frames only");
+  DMS_REQUIRE(f->frames > 0, "no images (before the first frame)");
+  return drawPanelColumn(t, p, &f->rgba, &f->depth_raw, &f->pred.image, &f->pred.vertex, viewports, depth_cutoff, which_mask, (hipStream_t)st);
+}
+
 int dms_fusion_set_cluster(dms_fusion* f, int cluster) {
   DMS_REQUIRE(f, "null argument");
   DMS_REQUIRE(!f->in_frame, "between frames only");

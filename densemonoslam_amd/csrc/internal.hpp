@@ -1,6 +1,7 @@
 // Internal C++ entry points shared between translation units of libdmslam_hip.so.
 #pragma once
 #include "common.hpp"
+#include "../../include/dmslam_render_panels.h"
 
 namespace dms {
 
@@ -45,5 +46,10 @@ int computeRgbResidual(float minScale, const dms_image2d* dIdx, const dms_image2
 int so3Step(const dms_image2d* lastImage, const dms_image2d* nextImage, const dms_mat33* imageBasis, const dms_mat33* kinv,
             const dms_mat33* krlr, void* workspace, size_t workspace_bytes, float* A, float* b, float* residual, int threads,
             int blocks, hipStream_t s);
+
+
+// render.hip: the panel column of dmslam_render_panels.h over the four source images, one launch
+int drawPanelColumn(dms_render_target* t, dms_panels* p, const dms_image2d* rgba, const dms_image2d* depth_u16, const dms_image2d* model_rgba,
+                    const dms_image2d* vertex, const dms_viewport* viewports, float depth_cutoff, int which_mask, hipStream_t s);
 
 }  // namespace dms

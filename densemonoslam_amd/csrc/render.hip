@@ -13,8 +13,16 @@
 #include "../../include/dmslam_render.h"
 #include "../../include/dmslam_render_shaded.h"
 #include "../../include/dmslam_render_cloud.h"
+#include "../../include/dmslam_render_panels.h"
+#include "internal.hpp"
 
 using namespace dms;
+
+struct dms_panels {
+  int width = 0, height = 0;
+  unsigned char* norm = nullptr;  // DEPTH_NORM, L8 (R26), image rows
+  unsigned* model = nullptr;      // the Model image (drawTexture), RGBA8, image rows
+};
 
 struct dms_render_target {
   int width = 0, height = 0;
@@ -827,6 +835,162 @@ __global__ __launch_bounds__(256) void k_cloud_resolve(CloudArgs a, const unsign
   }
 }
 
+// ---- the image panels: GUI::displayImg of DEPTH_NORM, Model, RGB and ModelImage (include/dmslam_render_panels.h, R22-R26) ------------
+// Two shader passes (depth_norm.frag through ComputePack::compute, visualise_textures.frag through IndexMap::renderDepth) and a
+// textured quad per panel.  A texel is fetched as four floats in [0, 1] from one of four kinds of source; the two "derived" kinds run
+// the shader pass on the fly from the raw depth / the vertex image, which is how the fused column blits DEPTH_NORM and the Model image
+// in the launch that also stores them: the same device functions, hence the same bytes, as the separate calls.
+enum { kSrcRGBA8 = 0, kSrcL8 = 1, kSrcDepthNorm = 2, kSrcModelDepth = 3 };
+
+struct PanelSrc {
+  const void* data;  // image rows, tightly packed
+  int W, H, kind;
+  unsigned lo, hi;  // depth_norm.frag: uint(minVal), uint(maxVal)
+  float maxv;       // maxVal, or visualise_textures.frag's maxDepth
+};
+
+// depth_norm.frag:12-18 stored by R26
+__device__ __forceinline__ unsigned depth_norm_byte(unsigned v, unsigned lo, unsigned hi, float maxv) {
+  return (v > lo && v < hi) ? unorm8(1.0f - (float)v / maxv) : 0u;
+}
+// visualise_textures.frag:12-23: a discarded texel keeps the clear colour (0, 0, 0, 0)
+__device__ __forceinline__ unsigned model_depth_rgba(float z, float maxDepth) {
+  if (z > maxDepth || z <= 0.f) return 0u;
+  return unorm8(1.0f - z / maxDepth) * 0x01010101u;
+}
+
+// R25: a texel as floats, byte / 255; luminance expands to (L, L, L, 1)
+__device__ __forceinline__ float4 panel_texel(const PanelSrc& s, int ix, int iy) {
+  const size_t q = (size_t)iy * s.W + ix;
+  unsigned px;
+  if (s.kind == kSrcL8 || s.kind == kSrcDepthNorm) {
+    const unsigned L = s.kind == kSrcL8 ? (unsigned)((const unsigned char*)s.data)[q]
+                                        : depth_norm_byte((unsigned)((const unsigned short*)s.data)[q], s.lo, s.hi, s.maxv);
+    const float l = (float)L / 255.f;
+    return make_float4(l, l, l, 1.f);
+  }
+  if (s.kind == kSrcModelDepth)
+    px = model_depth_rgba(((const float4*)s.data)[q].z, s.maxv);
+  else
+    px = ((const unsigned*)s.data)[q];
+  return make_float4((float)(px & 255u) / 255.f, (float)((px >> 8) & 255u) / 255.f, (float)((px >> 16) & 255u) / 255.f, (float)(px >> 24) / 255.f);
+}
+
+// R22-R25: the colour bytes of viewport pixel (i, j) (j counted from the viewport's bottom row) of a vw x vh viewport
+__device__ __forceinline__ unsigned panel_sample(const PanelSrc& s, int filter, int i, int j, int vw, int vh, float cr, float cg, float cb) {
+  const float u = (((float)i + 0.5f) / (float)vw) * (float)s.W;             // R22
+  const float v = (((float)(vh - 1 - j) + 0.5f) / (float)vh) * (float)s.H;  // flipped: the viewport's top row shows image row 0
+  float4 c;
+  if (filter == DMS_PANEL_NEAREST) {  // R23
+    c = panel_texel(s, min((int)floorf(u), s.W - 1), min((int)floorf(v), s.H - 1));
+  } else {  // R24
+    const float x = u - 0.5f, y = v - 0.5f;
+    const float fx = floorf(x), fy = floorf(y);
+    const float ax = x - fx, ay = y - fy;
+    const int i0 = min(max((int)fx, 0), s.W - 1), i1 = min(max((int)fx + 1, 0), s.W - 1);
+    const int j0 = min(max((int)fy, 0), s.H - 1), j1 = min(max((int)fy + 1, 0), s.H - 1);
+    const float4 t00 = panel_texel(s, i0, j0), t10 = panel_texel(s, i1, j0), t01 = panel_texel(s, i0, j1), t11 = panel_texel(s, i1, j1);
+    const float w00 = (1.f - ax) * (1.f - ay), w10 = ax * (1.f - ay), w01 = (1.f - ax) * ay, w11 = ax * ay;
+    c.x = ((w00 * t00.x + w10 * t10.x) + w01 * t01.x) + w11 * t11.x;
+    c.y = ((w00 * t00.y + w10 * t10.y) + w01 * t01.y) + w11 * t11.y;
+    c.z = ((w00 * t00.z + w10 * t10.z) + w01 * t01.z) + w11 * t11.z;
+    c.w = ((w00 * t00.w + w10 * t10.w) + w01 * t01.w) + w11 * t11.w;
+  }
+  return unorm8(c.x * cr) | (unorm8(c.y * cg) << 8) | (unorm8(c.z * cb) << 16) | (unorm8(c.w) << 24);  // R25, R9
+}
+
+// both shader passes over source pixels [4 q, 4 q + 4): either input may be null.  vec: the u16 row is 8-byte aligned (one ushort4
+// load); the vertex row is always read as float4, the outputs are written as uchar4 / 32-bit words.
+__device__ __forceinline__ void panel_passes(int q, int n, const unsigned short* __restrict__ depth, const float4* __restrict__ vertex,
+                                             unsigned char* __restrict__ norm, unsigned* __restrict__ model, unsigned lo, unsigned hi,
+                                             float maxv, float maxDepth, bool vec) {
+  const int p0 = 4 * q;
+  if (p0 + 3 < n) {
+    if (depth) {
+      unsigned v0, v1, v2, v3;
+      if (vec) {
+        const ushort4 d = ((const ushort4*)depth)[q];
+        v0 = d.x, v1 = d.y, v2 = d.z, v3 = d.w;
+      } else {
+        v0 = depth[p0], v1 = depth[p0 + 1], v2 = depth[p0 + 2], v3 = depth[p0 + 3];
+      }
+      ((unsigned*)norm)[q] = depth_norm_byte(v0, lo, hi, maxv) | (depth_norm_byte(v1, lo, hi, maxv) << 8) |
+                             (depth_norm_byte(v2, lo, hi, maxv) << 16) | (depth_norm_byte(v3, lo, hi, maxv) << 24);
+    }
+    if (vertex) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) model[p0 + k] = model_depth_rgba(vertex[p0 + k].z, maxDepth);
+    }
+  } else {
+    for (int p = p0; p < n; ++p) {
+      if (depth) norm[p] = (unsigned char)depth_norm_byte(depth[p], lo, hi, maxv);
+      if (vertex) model[p] = model_depth_rgba(vertex[p].z, maxDepth);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_panel_passes(int n, const unsigned short* __restrict__ depth, const float4* __restrict__ vertex,
+                                                      unsigned char* __restrict__ norm, unsigned* __restrict__ model, unsigned lo, unsigned hi,
+                                                      float maxv, float maxDepth, bool vec) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (4 * q < n) panel_passes(q, n, depth, vertex, norm, model, lo, hi, maxv, maxDepth, vec);
+}
+
+// one blit, one thread per pixel of the viewport
+__global__ __launch_bounds__(256) void k_panel_blit(PanelSrc s, int filter, dms_viewport vp, float cr, float cg, float cb,
+                                                    unsigned* __restrict__ color, int TW) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= vp.w * vp.h) return;
+  const int j = p / vp.w, i = p - j * vp.w;
+  color[(size_t)(vp.y + j) * TW + (vp.x + i)] = panel_sample(s, filter, i, j, vp.w, vp.h, cr, cg, cb);
+}
+
+// the column in one launch: items [0, start[0]) are the quads of the two passes, [start[k], start[k + 1]) the pixels of panel k's
+// viewport.  No item reads what another writes (the blits of DEPTH_NORM and Model run the pass per tap), and a pixel that a later
+// panel of the mask also covers is left to that panel, as the separate calls in order leave it.
+struct ColumnArgs {
+  PanelSrc src[4];
+  dms_viewport vp[4];
+  int start[5];
+  int mask, n, TW;
+  unsigned char* norm;
+  unsigned* model;
+  unsigned* color;
+  float maxDepth;
+};
+__global__ __launch_bounds__(256) void k_panel_column(ColumnArgs a) {
+  const int it = blockIdx.x * blockDim.x + threadIdx.x;
+  if (it < a.start[0]) {
+    panel_passes(it, a.n, (const unsigned short*)a.src[0].data, (const float4*)a.src[1].data, a.norm, a.model, a.src[0].lo, a.src[0].hi,
+                 a.src[0].maxv, a.maxDepth, true);
+    return;
+  }
+  if (it >= a.start[4]) return;
+  const int k = it < a.start[1] ? 0 : it < a.start[2] ? 1 : it < a.start[3] ? 2 : 3;
+  const dms_viewport vp = a.vp[k];
+  const int p = it - a.start[k];
+  const int j = p / vp.w, i = p - j * vp.w;
+  const int x = vp.x + i, y = vp.y + j;
+  for (int m = k + 1; m < 4; ++m) {
+    const dms_viewport o = a.vp[m];
+    if (((a.mask >> m) & 1) && x >= o.x && x < o.x + o.w && y >= o.y && y < o.y + o.h) return;
+  }
+  // LINEAR: RGB and DEPTH_NORM (Context.h:158-160, 179-181); NEAREST: drawTexture and imageTexture (IndexMap.cpp:42-47, 59-65)
+  const int filter = (k == DMS_PANEL_DEPTH_NORM || k == DMS_PANEL_RGB) ? DMS_PANEL_LINEAR : DMS_PANEL_NEAREST;
+  a.color[(size_t)y * a.TW + x] = panel_sample(a.src[k], filter, i, j, vp.w, vp.h, 1.f, 1.f, 1.f);
+}
+
+// GLSL's uint(float) where C leaves it open: clamped to [0, 2^32 - 1], 0 for NaN
+unsigned to_uint(float x) { return !(x > 0.f) ? 0u : x >= 4294967296.f ? 0xFFFFFFFFu : (unsigned)x; }
+
+bool viewport_ok(const dms_render_target* t, const dms_viewport& v) {
+  return v.w > 0 && v.h > 0 && v.x >= 0 && v.y >= 0 && v.x <= t->width - v.w && v.y <= t->height - v.h;
+}
+bool panel_image_ok(const dms_image2d* im, size_t elem) {
+  return im->data && im->cols > 0 && im->rows > 0 && im->cols <= DMS_RENDER_MAX_EXTENT && im->rows <= DMS_RENDER_MAX_EXTENT &&
+         im->pitch == (size_t)im->cols * elem;
+}
+
 int surfel_blocks(size_t upper) {
   size_t b = (upper + 255) / 256;
   if (b < 1) b = 1;
@@ -1153,3 +1317,128 @@ int dms_render_cloud(dms_render_target* t, const dms_image2d* rgba, const dms_im
 }
 
 }  // extern "C"
+
+// ---- the image panels (include/dmslam_render_panels.h) ------------------------------------------------------------------------------
+extern "C" {
+
+int dms_panels_create(dms_panels** out, int width, int height) {
+  DMS_REQUIRE(out, "null argument");
+  *out = nullptr;
+  DMS_REQUIRE(width > 0 && height > 0 && width <= DMS_RENDER_MAX_EXTENT && height <= DMS_RENDER_MAX_EXTENT, "extent out of range");
+  dms_panels* p = new dms_panels();
+  p->width = width;
+  p->height = height;
+  const size_t n = (size_t)width * height;
+  hipError_t e = hipMalloc((void**)&p->norm, (n + 3) / 4 * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&p->model, n * 4);
+  if (e == hipSuccess) e = hipMemset(p->norm, 0, (n + 3) / 4 * 4);
+  if (e == hipSuccess) e = hipMemset(p->model, 0, n * 4);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    dms_panels_destroy(p);
+    return hip_fail(e, "dms_panels_create", __FILE__, __LINE__);
+  }
+  *out = p;
+  return DMS_OK;
+}
+
+int dms_panels_destroy(dms_panels* p) {
+  if (!p) return DMS_OK;
+  if (p->norm) (void)hipFree(p->norm);
+  if (p->model) (void)hipFree(p->model);
+  delete p;
+  return DMS_OK;
+}
+
+int dms_panels_images(dms_panels* p, dms_image2d* depth_norm_l8, dms_image2d* model_rgba8) {
+  DMS_REQUIRE(p, "null argument");
+  if (depth_norm_l8) *depth_norm_l8 = dms_image2d{p->norm, (size_t)p->width, p->height, p->width};
+  if (model_rgba8) *model_rgba8 = dms_image2d{p->model, (size_t)p->width * 4, p->height, p->width};
+  return DMS_OK;
+}
+
+int dms_depth_norm(dms_panels* p, const dms_image2d* depth_u16, float min_val, float max_val, dms_stream s) {
+  DMS_REQUIRE(p && depth_u16, "null argument");
+  DMS_REQUIRE(panel_image_ok(depth_u16, 2), "null or empty image, or padded rows");
+  DMS_REQUIRE(depth_u16->cols == p->width && depth_u16->rows == p->height, "shape mismatch");
+  const int n = p->width * p->height, q = (n + 3) / 4;
+  hipLaunchKernelGGL(k_panel_passes, dim3((q + 255) / 256), dim3(256), 0, (hipStream_t)s, n, (const unsigned short*)depth_u16->data,
+                     (const float4*)nullptr, p->norm, p->model, to_uint(min_val), to_uint(max_val), max_val, 0.f,
+                     ((uintptr_t)depth_u16->data & 7u) == 0);
+  DMS_CHECK_LAUNCH();
+  return DMS_OK;
+}
+
+int dms_model_depth_image(dms_panels* p, const dms_image2d* vertex_rgba32f, float max_depth, dms_stream s) {
+  DMS_REQUIRE(p && vertex_rgba32f, "null argument");
+  DMS_REQUIRE(panel_image_ok(vertex_rgba32f, 16), "null or empty image, or padded rows");
+  DMS_REQUIRE(((uintptr_t)vertex_rgba32f->data & 15u) == 0, "the vertex image must be 16-byte aligned");
+  DMS_REQUIRE(vertex_rgba32f->cols == p->width && vertex_rgba32f->rows == p->height, "shape mismatch");
+  const int n = p->width * p->height, q = (n + 3) / 4;
+  hipLaunchKernelGGL(k_panel_passes, dim3((q + 255) / 256), dim3(256), 0, (hipStream_t)s, n, (const unsigned short*)nullptr,
+                     (const float4*)vertex_rgba32f->data, p->norm, p->model, 0u, 0u, 0.f, max_depth, false);
+  DMS_CHECK_LAUNCH();
+  return DMS_OK;
+}
+
+int dms_render_blit(dms_render_target* t, const dms_image2d* image, int format, int filter, const dms_viewport* vp, const float color_rgb[3],
+                    dms_stream s) {
+  DMS_REQUIRE(t && image && vp && color_rgb, "null argument");
+  DMS_REQUIRE(format == DMS_PANEL_RGBA8 || format == DMS_PANEL_L8, "format must be DMS_PANEL_RGBA8 or DMS_PANEL_L8");
+  DMS_REQUIRE(filter == DMS_PANEL_NEAREST || filter == DMS_PANEL_LINEAR, "filter must be DMS_PANEL_NEAREST or DMS_PANEL_LINEAR");
+  DMS_REQUIRE(panel_image_ok(image, format == DMS_PANEL_RGBA8 ? 4 : 1), "null or empty image, or padded rows");
+  DMS_REQUIRE(format != DMS_PANEL_RGBA8 || ((uintptr_t)image->data & 3u) == 0, "an RGBA8 image must be 4-byte aligned");
+  DMS_REQUIRE(viewport_ok(t, *vp), "the viewport is empty or leaves the target");
+  PanelSrc src{image->data, image->cols, image->rows, format == DMS_PANEL_RGBA8 ? kSrcRGBA8 : kSrcL8, 0u, 0u, 0.f};
+  const int n = vp->w * vp->h;
+  hipLaunchKernelGGL(k_panel_blit, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)s, src, filter, *vp, color_rgb[0], color_rgb[1],
+                     color_rgb[2], t->color, t->width);
+  DMS_CHECK_LAUNCH();
+  return DMS_OK;
+}
+
+}  // extern "C"
+
+namespace dms {
+int drawPanelColumn(dms_render_target* t, dms_panels* p, const dms_image2d* rgba, const dms_image2d* depth_u16, const dms_image2d* model_rgba,
+                    const dms_image2d* vertex, const dms_viewport* viewports, float depth_cutoff, int which_mask, hipStream_t s) {
+  DMS_REQUIRE(which_mask >= 0 && which_mask <= DMS_PANEL_ALL, "which_mask must be 0..15");
+  DMS_REQUIRE(panel_image_ok(rgba, 4) && panel_image_ok(depth_u16, 2) && panel_image_ok(model_rgba, 4) && panel_image_ok(vertex, 16),
+              "the context's images are not tightly packed");
+  const int W = p->width, H = p->height;
+  DMS_REQUIRE(rgba->cols == W && rgba->rows == H && depth_u16->cols == W && depth_u16->rows == H && model_rgba->cols == W &&
+                  model_rgba->rows == H && vertex->cols == W && vertex->rows == H,
+              "the panels are of another size than the context");
+  DMS_REQUIRE(((uintptr_t)depth_u16->data & 7u) == 0 && ((uintptr_t)vertex->data & 15u) == 0 && ((uintptr_t)rgba->data & 3u) == 0 &&
+                  ((uintptr_t)model_rgba->data & 3u) == 0,
+              "misaligned image");
+  ColumnArgs a;
+  const float maxv = depth_cutoff * 1000.f;  // normaliseDepth (ElasticFusion.cpp:774-775)
+  a.src[DMS_PANEL_DEPTH_NORM] = PanelSrc{depth_u16->data, W, H, kSrcDepthNorm, to_uint(0.3f * 1000.f), to_uint(maxv), maxv};
+  a.src[DMS_PANEL_MODEL] = PanelSrc{vertex->data, W, H, kSrcModelDepth, 0u, 0u, depth_cutoff};
+  a.src[DMS_PANEL_RGB] = PanelSrc{rgba->data, W, H, kSrcRGBA8, 0u, 0u, 0.f};
+  a.src[DMS_PANEL_MODEL_IMAGE] = PanelSrc{model_rgba->data, W, H, kSrcRGBA8, 0u, 0u, 0.f};
+  a.n = W * H;
+  int items = (a.n + 3) / 4;
+  a.start[0] = items;
+  for (int k = 0; k < 4; ++k) {
+    if ((which_mask >> k) & 1) {
+      DMS_REQUIRE(viewport_ok(t, viewports[k]), "a viewport is empty or leaves the target");
+      a.vp[k] = viewports[k];
+      items += viewports[k].w * viewports[k].h;
+    } else {
+      a.vp[k] = dms_viewport{0, 0, 0, 0};
+    }
+    a.start[k + 1] = items;
+  }
+  a.mask = which_mask;
+  a.TW = t->width;
+  a.norm = p->norm;
+  a.model = p->model;
+  a.color = t->color;
+  a.maxDepth = depth_cutoff;
+  hipLaunchKernelGGL(k_panel_column, dim3((items + 255) / 256), dim3(256), 0, s, a);
+  DMS_CHECK_LAUNCH();
+  return DMS_OK;
+}
+}  // namespace dms

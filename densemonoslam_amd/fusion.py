@@ -609,6 +609,35 @@ class ElasticFusion:
         p = _cloud_params(mvp, model_pose, color_type, pose_dev, model_pose_dev)
         check(lib.dms_fusion_render_cloud(target.h, self.h, int(which), C.byref(p), stream), "dms_fusion_render_cloud")
 
+    def drawPanels(self, target, panels, viewports, depth_cutoff, which_mask=15, stream=None):
+        """The GUI's image column in one launch (dms_fusion_draw_panels): viewports = four (x, y, w, h) for DEPTH_NORM, Model, RGB,
+        ModelImage; depth_cutoff is gui->depthCutoff."""
+        vps = (Viewport * 4)(*[Viewport(*[int(v) for v in vp]) for vp in viewports])
+        check(lib.dms_fusion_draw_panels(target.h, panels.h, self.h, vps, float(depth_cutoff), int(which_mask), stream), "dms_fusion_draw_panels")
+
+
+    def drawPanelsSeparately(self, target, panels, viewports, depth_cutoff, which_mask=15, stream=None):
+        """The same column as the reference issues it (MainController.cpp:649-664): normaliseDepth, renderDepth and one displayImg per
+        panel, six launches."""
+        views = {}
+        for k, img in ((PANEL_DEPTH_NORM, 1), (PANEL_MODEL, 10), (PANEL_RGB, 0), (PANEL_MODEL_IMAGE, 9)):
+            views[k] = Image2D()
+            check(lib.dms_fusion_get_image(self.h, img, C.byref(views[k])), "dms_fusion_get_image")
+        cut = np.float32(depth_cutoff)
+        check(lib.dms_depth_norm(panels.h, C.byref(views[PANEL_DEPTH_NORM]), float(np.float32(0.3) * np.float32(1000.0)), float(cut * np.float32(1000.0)),
+                                 stream), "dms_depth_norm")
+        check(lib.dms_model_depth_image(panels.h, C.byref(views[PANEL_MODEL]), float(cut), stream), "dms_model_depth_image")
+        white = (C.c_float * 3)(1.0, 1.0, 1.0)
+        for k in range(4):
+            if not (which_mask >> k) & 1:
+                continue
+            vp = Viewport(*[int(v) for v in viewports[k]])
+            if k in (PANEL_DEPTH_NORM, PANEL_MODEL):
+                panels.blit(target, k, viewports[k], stream=stream)
+            else:
+                check(lib.dms_render_blit(target.h, C.byref(views[k]), PANEL_RGBA8, PANEL_LINEAR if k == PANEL_RGB else PANEL_NEAREST, C.byref(vp),
+                                          white, stream), "dms_render_blit")
+
     def feedbackBuffers(self):
         """Context::feedbackBuffers(): {FeedbackBuffer.RAW: ..., FeedbackBuffer.FILTERED: ...}"""
         return {FeedbackBuffer.RAW: FeedbackBuffer(self, CLOUD_RAW), FeedbackBuffer.FILTERED: FeedbackBuffer(self, CLOUD_FILTERED)}
@@ -953,3 +982,91 @@ class FeedbackBuffer:
     def render(self, mvp, pose, drawNormals, drawColors, target, pose_dev=None, model_pose_dev=None, stream=None):
         """FeedbackBuffer::render(mvp, pose, drawNormals, drawColors) into `target` (mvp row-major: transpose pangolin's)."""
         self.context.renderCloud(target, self.which, mvp, pose, 1 if drawNormals else 2 if drawColors else 0, pose_dev, model_pose_dev, stream)
+
+
+# ---- the image panels: GUI::displayImg of DEPTH_NORM, Model, RGB, ModelImage (include/dmslam_render_panels.h) -----------------
+PANEL_RGBA8, PANEL_L8 = 0, 1
+PANEL_NEAREST, PANEL_LINEAR = 0, 1
+PANEL_DEPTH_NORM, PANEL_MODEL, PANEL_RGB, PANEL_MODEL_IMAGE, PANEL_ALL = 0, 1, 2, 3, 15
+
+
+class Viewport(C.Structure):
+    """dms_viewport: x, y of the bottom-left pixel in window coordinates, width, height"""
+    _fields_ = [("x", _I), ("y", _I), ("w", _I), ("h", _I)]
+
+
+lib.dms_panels_create.argtypes = [C.POINTER(_P), _I, _I]
+lib.dms_panels_destroy.argtypes = [_P]
+lib.dms_panels_images.argtypes = [_P, _I2, _I2]
+lib.dms_depth_norm.argtypes = [_P, _I2, _F, _F, _P]
+lib.dms_model_depth_image.argtypes = [_P, _I2, _F, _P]
+lib.dms_render_blit.argtypes = [_P, _I2, _I, _I, C.POINTER(Viewport), C.POINTER(C.c_float), _P]
+lib.dms_fusion_draw_panels.argtypes = [_P, _P, _P, C.POINTER(Viewport), _F, _I, _P]
+
+
+def render_blit(target, image, fmt, filt, viewport, color=(1.0, 1.0, 1.0), stream=None):
+    """RenderToViewport(true) with the depth test off (dms_render_blit): `image` (H x W x 4 u8 for PANEL_RGBA8, H x W u8 for PANEL_L8,
+    image order; an array or a DeviceImage) stretched upside down over viewport = (x, y, w, h) of `target`, times `color`."""
+    im = _img(image, np.uint8)
+    vp = Viewport(*[int(v) for v in viewport])
+    c = (C.c_float * 3)(*[float(v) for v in color])
+    check(lib.dms_render_blit(target.h, im.ref, int(fmt), int(filt), C.byref(vp), c, stream), "dms_render_blit")
+    if not isinstance(image, DeviceImage):
+        check(lib.dms_stream_sync(stream))  # the temporary upload must outlive the blit
+
+
+class Panels:
+    """dms_panels: the DEPTH_NORM (L8) and Model (RGBA8) images of one camera size, with the two passes that fill them."""
+
+    def __init__(self, width, height):
+        self.width, self.height = int(width), int(height)
+        h = C.c_void_p()
+        check(lib.dms_panels_create(C.byref(h), self.width, self.height), "dms_panels_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib.dms_panels_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def normaliseDepth(self, depth_u16, min_val, max_val, stream=None):
+        """depth_norm.frag (dms_depth_norm); min_val / max_val already scaled (the reference: 0.3f * 1000.f, depthCutoff * 1000.f)"""
+        d = _img(depth_u16, np.uint16)
+        check(lib.dms_depth_norm(self.h, d.ref, float(min_val), float(max_val), stream), "dms_depth_norm")
+        if not isinstance(depth_u16, DeviceImage):
+            check(lib.dms_stream_sync(stream))
+
+    def renderDepth(self, vertex, max_depth, stream=None):
+        """visualise_textures.frag (dms_model_depth_image) over an H x W x 4 f32 vertex image"""
+        v = _img(vertex, np.float32)
+        check(lib.dms_model_depth_image(self.h, v.ref, float(max_depth), stream), "dms_model_depth_image")
+        if not isinstance(vertex, DeviceImage):
+            check(lib.dms_stream_sync(stream))
+
+    def views(self):
+        """(DEPTH_NORM, Model image) as dms_image2d device views"""
+        n, m = Image2D(), Image2D()
+        check(lib.dms_panels_images(self.h, C.byref(n), C.byref(m)), "dms_panels_images")
+        return n, m
+
+    def images(self, stream=None):
+        """(DEPTH_NORM u8 HxW, Model image u8 HxWx4), image order, after the work enqueued on `stream`"""
+        check(lib.dms_stream_sync(stream), "dms_stream_sync")
+        n, m = self.views()
+        return capi.download_view(n, np.uint8), capi.download_view(m, np.uint8, 4)
+
+    def blit(self, target, which, viewport, color=(1.0, 1.0, 1.0), stream=None):
+        """GUI::displayImg of one of the two intermediates: PANEL_DEPTH_NORM (LINEAR) or PANEL_MODEL (NEAREST)"""
+        n, m = self.views()
+        vp = Viewport(*[int(v) for v in viewport])
+        c = (C.c_float * 3)(*[float(v) for v in color])
+        if which == PANEL_DEPTH_NORM:
+            check(lib.dms_render_blit(target.h, C.byref(n), PANEL_L8, PANEL_LINEAR, C.byref(vp), c, stream), "dms_render_blit")
+        else:
+            check(lib.dms_render_blit(target.h, C.byref(m), PANEL_RGBA8, PANEL_NEAREST, C.byref(vp), c, stream), "dms_render_blit")
