@@ -49,6 +49,8 @@ int splat_predict(dms_model* m, const dms_pose_block* pose, const dms_camera* ca
                   int timeIdx, int maxTime, int timeDelta, int active, unsigned long long* zbuf, dms_predict_out* out,
                   dms_image2d* depth_out, int zclean, hipStream_t s, const float* second_conf_time_maxtime = nullptr,
                   unsigned long long* zbuf2 = nullptr, int resolve_only = 0, const FillArgs* fill = nullptr, const TrackInitArgs* init = nullptr);
+int splat_project_only(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, float maxDepth, float confThreshold, int time,
+                       int timeIdx, int maxTime, int timeDelta, int active, unsigned long long* zbuf, hipStream_t s, const ProjectRider* rider);
 int model_sample_graph(dms_model* m, int sampleRate, float* rows4_host, int max_rows, int* n_host, hipStream_t s);
 int model_flush_pending(dms_model* m, hipStream_t s);
 // fusion_fuse.hip
@@ -358,6 +360,24 @@ struct dms_fusion {
   bool pre_valid = false;        // zbuf2 holds a projection
   int pre_tick = 0;              // ... rendered for this tick
   unsigned long pre_version = 0; // ... of this version of the map
+  // lazy_final_prediction: a frame whose final prediction (ElasticFusion.cpp:586) nobody reads before the next frame's tracking
+  // prediction overwrites it projects for that next prediction only (into zbuf2) and keeps what is needed to render the skipped
+  // one on demand (materialise_final_prediction).  The record lives from the end of that frame to the beginning of the next one:
+  // the fill-in reads the frame's live images, which that next frame's live half leaves alone (it takes the other set) but which
+  // the frame after it reuses.
+  struct LazyRecord {
+    bool pending = false;
+    float confidence = 0.f, maxDepth = 0.f;
+    int tick = 0, timeIdx = 0, timeDelta = 0;
+    int pass_geom = 0, pass_rgb = 0;      // lost / lost || frameToFrameRGB of that frame (a lost camera is never deferred: 0 / ftf)
+    dms_image2d depth_filtered, rgba;     // the fill-in's inputs: that frame's live image set
+    dms_model* model = nullptr;
+    unsigned long version = 0;            // the map the eager prediction would have shown
+    hipStream_t stream = nullptr;         // the frame's stream: the skipped prediction is enqueued where the eager one would have been
+  } lazy;
+  dms_pose_block* lazy_pose = nullptr;    // device: the pose block (pose + inverse) of the deferred frame, copied by its project launch
+  bool lazy_observed = false;             // the final prediction's images have been asked for, pending record or not: eager (the dual pass) for the rest of the context's life
+  long lazy_deferred = 0, lazy_materialised = 0, lazy_stale = 0;
   FrameState* state = nullptr;
   FrameState* h_state_dev = nullptr;  // device view of h_state
   FrameState* h_state = nullptr;  // pinned, four slots, frame % 4 (the host may read a slot once that frame's event has completed)
@@ -463,6 +483,7 @@ void layout(dms_fusion* f, Carve& c) {
   f->zbuf2 = (unsigned long long*)c.take(N * 8);
   f->tickets = (unsigned*)c.take(2048 + 512 + 1024);  // + the subsample masks (128 words at word 512) + the thumbnail masks (256 words at word 640)
   f->state = (FrameState*)c.take(sizeof(FrameState));
+  f->lazy_pose = (dms_pose_block*)c.take(sizeof(dms_pose_block));
 }
 
 struct FTimer {
@@ -524,8 +545,9 @@ void drain(dms_fusion* f) {
 // prediction (confidence 0.7, next tick).  mode 2 (that next frame's begin): resolve zbuf2 if it is still what this
 // prediction would render — nothing changed the map, the pose comes from the previous frame — else project as usual.
 int predict(dms_fusion* f, float confidence, hipStream_t s, void* state_mirror = nullptr, bool dense_test = false, int mode = 0,
-            bool have_prior = false, const TrackInitArgs* track_init = nullptr, bool* track_init_taken = nullptr) {
+            bool have_prior = false, const TrackInitArgs* track_init = nullptr, bool* track_init_taken = nullptr, bool one_call = false) {
   int rc;
+  f->lazy.pending = false;  // (whatever this call renders is newer than a prediction skipped earlier)
   FillArgs fa;
   const FillArgs* fused = nullptr;
   // passthrough = lost (geometry), lost || frameToFrameRGB (image) (ElasticFusion.cpp:704-712)
@@ -576,7 +598,46 @@ int predict(dms_fusion* f, float confidence, hipStream_t s, void* state_mirror =
       // (a projection rendered ahead for this camera's next frame is stale by then when other cameras fuse into the same map: not rendered)
       const bool dual = mode == 1 && f->p.share_projection && f->p.hybrid_tracking && f->model->sharers == 1;
       if (dual && f->pre_valid && (rc = clear_zbuf(f->zbuf2, W * H, s))) return rc;  // (never consumed)
-      if ((rc = splat_predict(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, confidence, f->tick, f->p.timeIdx, f->tick,
+      // lazy_final_prediction: this prediction's images (f->pred, f->fill) are overwritten by the next frame's tracking prediction;
+      // when nothing can read them before that, only that next prediction is projected.  Their readers, all in this file:
+      //   in a frame: the armed frame block (fill_thumb in this very resolve), NID key-framing, the local loop block and the ORB
+      //     global loop block (f->pred against f->pred_old) - they read a prediction of their own earlier in the frame, but such a
+      //     context is a caller that looks at the view: it stays eager, as do a lost camera (pass-through fill-in, the tick stops),
+      //     the two-phase _begin / _end form (the caller is between the halves for a reason: a deformation graph, a loop) and the
+      //     bootstrap frame;
+      //   between frames: dms_fusion_get_image 9 - 15, dms_fusion_draw_panels, dms_fusion_thumbnails and dms_fusion_frame_block
+      //     (the session's fern insertion, key-frame export and camera migration go through these), and dms_fusion_join_map and
+      //     dms_fusion_import_camera, which change the map under the record - each calls materialise_final_prediction first, and
+      //     the first such call makes the context eager whether a record is pending or not: the views dms_fusion_get_image
+      //     hands out stay valid for the context's life, and a caller may keep one and read through it after later frames
+      //     without asking again (Context::fillIn of cpp/ElasticFusion.h does); dms_fusion_predict and
+      //     dms_fusion_apply_global_loop_* render the images anew (the record is dropped above);
+      //   the result mirror (h_state): written by block 0 of the project launch below instead of the resolve's.
+      // dms_fusion_arm_frame_block reads nothing: it makes the NEXT frame eager through armed_now.
+      const bool defer = dual && one_call && fused && state_mirror && f->p.lazy_final_prediction && !f->lazy_observed && !f->armed_now.block &&
+                         !f->p.nid_keyframing && !f->p.local_loop_closure && !f->p.hybrid_loops && !f->lost && !f->cur_bootstrap;
+      if (defer) {
+        const ProjectRider rider = {(const unsigned*)f->state, (unsigned*)state_mirror, (int)(sizeof(FrameState) / 4),
+                                    (const unsigned*)&f->state->cur, (unsigned*)f->lazy_pose, (int)(sizeof(dms_pose_block) / 4)};
+        if ((rc = splat_project_only(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, second[0], next_tick, f->p.timeIdx, next_tick,
+                                     f->p.timeDelta, 1, f->zbuf2, s, &rider)))
+          return rc;
+        dms_fusion::LazyRecord& r = f->lazy;
+        r.pending = true;
+        r.confidence = confidence;
+        r.maxDepth = f->p.maxDepthProcessed;
+        r.tick = f->tick;
+        r.timeIdx = f->p.timeIdx;
+        r.timeDelta = f->p.timeDelta;
+        r.pass_geom = 0;
+        r.pass_rgb = f->p.frameToFrameRGB ? 1 : 0;
+        r.depth_filtered = f->depth_filtered;
+        r.rgba = f->rgba;
+        r.model = f->model;
+        r.version = f->model->version;
+        r.stream = s;
+        f->lazy_deferred += 1;
+      } else if ((rc = splat_predict(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, confidence, f->tick, f->p.timeIdx, f->tick,
                               f->p.timeDelta, 1, f->zbuf, &f->pred, nullptr, 1, s, dual ? second : nullptr, dual ? f->zbuf2 : nullptr, 0,
                               fused, fused ? track_init : nullptr)))
         return rc;
@@ -597,6 +658,34 @@ int predict(dms_fusion* f, float confidence, hipStream_t s, void* state_mirror =
   return DMS_OK;
 }
 
+// The final prediction a deferred frame skipped (lazy_final_prediction), rendered now: the ordinary project + resolve + fill-in
+// with the arguments that frame would have used, at the pose it ended with, enqueued on that frame's stream - the same bits as the
+// eager path as long as the map is the one that frame left.  A map changed since (dms_model_upload / consume on the handle; joins
+// are materialised before they change anything) is counted as stale and rendered as it is NOW, at the recorded pose, tick and
+// threshold: the eager images would have shown the map before the change.  The context is eager from here on (lazy_observed),
+// whether a record was pending or not - a caller that has looked once may hold a view and look again without asking; one that
+// looks every frame pays one extra project pass once.  `consumer`: the stream the caller reads the images on; unless
+// that is the frame's stream the call synchronises, so that the images are complete for any reader.
+int materialise_final_prediction(dms_fusion* f, hipStream_t consumer, bool consumer_known) {
+  f->lazy_observed = true;
+  if (!f->lazy.pending) return DMS_OK;
+  const dms_fusion::LazyRecord r = f->lazy;
+  f->lazy.pending = false;
+  f->lazy_materialised += 1;
+  if (r.model != f->model || r.version != f->model->version) f->lazy_stale += 1;
+  int rc;
+  FillArgs fa;
+  if ((rc = fill_args(&f->pred, &r.depth_filtered, &r.rgba, &f->cam, r.pass_geom, r.pass_rgb, &f->fill, nullptr, nullptr, 0, nullptr, &fa))) return rc;
+  {
+    FTimer t(f, r.stream, "predict");
+    if ((rc = splat_predict(f->model, f->lazy_pose, &f->cam, r.maxDepth, r.confidence, r.tick, r.timeIdx, r.tick, r.timeDelta, 1, f->zbuf, &f->pred,
+                            nullptr, 1, r.stream, nullptr, nullptr, 0, &fa, nullptr)))
+      return rc;
+  }
+  if (!consumer_known || consumer != r.stream) DMS_HIP(hipStreamSynchronize(r.stream));
+  return DMS_OK;
+}
+
 // Device half of the ORB-triggered global loop closure.  `active_new` = 0: the form inside processFrame (ElasticFusion.cpp:293-326):
 // ACTIVE prediction at orbTcwOld, INACTIVE at orbTcwNew, every sample with 0 < z < maxDepthProcessed (the time test is commented
 // out there).  1: ElasticFusion::applyGlobalLoop (:1158-1200): ACTIVE at orbTcwNew, INACTIVE at orbTcwOld, time > 0 required.
@@ -608,6 +697,7 @@ int global_loop_device(dms_fusion* f, const float* orbTcwOld, const float* orbTc
   memcpy(b.v, orbTcwNew, sizeof(b.v));
   hipLaunchKernelGGL(k_pose_blocks2, dim3(1), dim3(64), 0, s, f->orb_pose, a, b);
   DMS_CHECK_LAUNCH();
+  f->lazy.pending = false;  // (f->pred is rendered anew below)
   FTimer t(f, s, "global_loop");
   const int act = active_new ? 1 : 0;
   // predict(context, rf) with currPose = the ACTIVE pose (:294-296 / :1158-1160): only its vertex map is consumed
@@ -710,6 +800,7 @@ void dms_fusion_default_params(dms_fusion_params* p, int width, int height, floa
   p->share_projection = 1;
   p->fused_fill_in = 1;
   p->hybrid_loops = 0;
+  p->lazy_final_prediction = 1;
 }
 
 // far depth cut-offs raise the static exponents of the trackers' first reductions (canon.hpp): set at creation and whenever the
@@ -810,6 +901,7 @@ int dms_fusion_create(dms_fusion** out, const dms_fusion_params* p) {
   if (const char* ft = getenv("DMS_FOLD_TRACK_INIT")) f->fold_track_init = atoi(ft) != 0;
   if (const char* hl = getenv("DMS_HOST_LAG")) f->host_lag = atoi(hl) == 3 ? 3 : 2;
   if (const char* lm = getenv("DMS_LATE_MAIN")) f->late_forced = atoi(lm) != 0 ? 1 : 0;
+  if (const char* lz = getenv("DMS_LAZY_FINAL_PREDICTION")) f->p.lazy_final_prediction = atoi(lz) != 0 ? 1 : 0;  // A/B runs
   if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_inputs, hipEventDisableTiming);
   if (e == hipSuccess) e = hipMemset(f->arena, 0, f->arena_bytes);
   if (e == hipSuccess) e = hipHostMalloc((void**)&f->h_state, 4 * sizeof(FrameState), hipHostMallocMapped);
@@ -917,6 +1009,7 @@ int dms_fusion_draw_panels(dms_render_target* t, dms_panels* p, dms_fusion* f, c
   DMS_REQUIRE(t && p && f && viewports, "null argument");
   DMS_REQUIRE(!f->in_frame, "between frames only");
   DMS_REQUIRE(f->frames > 0, "no images (before the first frame)");
+  if (int rc = materialise_final_prediction(f, (hipStream_t)st, true)) return rc;
   return drawPanelColumn(t, p, &f->rgba, &f->depth_raw, &f->pred.image, &f->pred.vertex, viewports, depth_cutoff, which_mask, (hipStream_t)st);
 }
 
@@ -994,6 +1087,7 @@ int dms_fusion_process_frame_begin(dms_fusion* f, const void* rgb_dev, int rgb_c
   DMS_REQUIRE(f && rgb_dev && depth_dev, "null argument");
   DMS_REQUIRE(rgb_channels == 3 || rgb_channels == 4, "rgb_channels must be 3 or 4");
   DMS_REQUIRE(!f->in_frame, "dms_fusion_process_frame_end has not been called for the previous frame");
+  f->lazy.pending = false;  // the skipped prediction of the previous frame: from here on the images are this frame's, as they always were
   f->armed_now = f->armed;  // (the arming holds for this frame only, whatever path it takes)
   f->armed = dms_fusion::ArmedBlock();
   f->armed_written = false;
@@ -1360,7 +1454,7 @@ int dms_fusion_process_frame_begin(dms_fusion* f, const void* rgb_dev, int rgb_c
   return DMS_OK;
 }
 
-int dms_fusion_process_frame_end(dms_fusion* f, const float* graph_host, int graph_nodes, const float* newPose16, dms_stream st) {
+static int process_frame_end(dms_fusion* f, const float* graph_host, int graph_nodes, const float* newPose16, dms_stream st, bool one_call) {
   DMS_REQUIRE(f, "null argument");
   DMS_REQUIRE(f->in_frame, "dms_fusion_process_frame_begin has not been called");
   DMS_REQUIRE(graph_nodes == 0 || graph_host, "null graph");
@@ -1429,7 +1523,7 @@ int dms_fusion_process_frame_end(dms_fusion* f, const float* graph_host, int gra
   }
   // finalPredict (ElasticFusion.cpp:586); its fill-in kernel mirrors the result block to the host slot
   const int k4 = (int)(f->frames % 4);
-  if ((rc = predict(f, f->p.confidence, s, f->h_state_dev + k4, false, 1))) return rc;
+  if ((rc = predict(f, f->p.confidence, s, f->h_state_dev + k4, false, 1, false, nullptr, nullptr, one_call))) return rc;
   f->last_slot = k4;
   DMS_HIP(hipEventRecord(f->ev_main_done[k4], s));  // (also without the pipeline: it gates the reading of this frame's result slot)
   f->fused_last = fused;
@@ -1442,7 +1536,20 @@ int dms_fusion_process_frame(dms_fusion* f, const void* rgb_dev, int rgb_channel
                              float weightMultiplier, dms_stream st) {
   int rc = dms_fusion_process_frame_begin(f, rgb_dev, rgb_channels, depth_dev, inPose16, weightMultiplier, st);
   if (rc) return rc;
-  return dms_fusion_process_frame_end(f, nullptr, 0, nullptr, st);
+  return process_frame_end(f, nullptr, 0, nullptr, st, true);
+}
+
+int dms_fusion_process_frame_end(dms_fusion* f, const float* graph_host, int graph_nodes, const float* newPose16, dms_stream st) {
+  return process_frame_end(f, graph_host, graph_nodes, newPose16, st, false);
+}
+
+int dms_fusion_get_lazy_stats(dms_fusion* f, int* eager, long* deferred, long* materialised, long* stale) {
+  DMS_REQUIRE(f, "null argument");
+  if (eager) *eager = (f->p.lazy_final_prediction && !f->lazy_observed) ? 0 : 1;
+  if (deferred) *deferred = f->lazy_deferred;
+  if (materialised) *materialised = f->lazy_materialised;
+  if (stale) *stale = f->lazy_stale;
+  return DMS_OK;
 }
 
 // Sticky tracker-timeout report: FrameState::track_timeouts counts the frames whose resident tracker kernels gave up at
@@ -1552,6 +1659,7 @@ int dms_fusion_thumbnails(dms_fusion* f, void* block_dev, dms_stream st) {
   DMS_REQUIRE(f && block_dev, "null argument");
   DMS_REQUIRE(((uintptr_t)block_dev & 15) == 0, "thumbnail block must be 16-byte aligned");
   const int tw = f->p.width / 8, th = f->p.height / 8;
+  if (int rc = materialise_final_prediction(f, (hipStream_t)st, true)) return rc;
   hipLaunchKernelGGL(k_thumbnails, dim3((tw * th + 255) / 256), dim3(256), 0, (hipStream_t)st, (const uchar4*)f->fill.image.data,
                      (const float4*)f->fill.vertex.data, (const float4*)f->fill.normal.data, f->p.width, f->p.height, tw, th,
                      (unsigned char*)block_dev, (const float*)nullptr, (float*)nullptr, (int*)nullptr, 0);
@@ -1563,6 +1671,7 @@ int dms_fusion_frame_block(dms_fusion* f, void* block_dev, float* pose16_dst_dev
   DMS_REQUIRE(f && block_dev, "null argument");
   DMS_REQUIRE(((uintptr_t)block_dev & 15) == 0, "thumbnail block must be 16-byte aligned");
   const int tw = f->p.width / 8, th = f->p.height / 8;
+  if (int rc = materialise_final_prediction(f, (hipStream_t)st, true)) return rc;
   hipLaunchKernelGGL(k_thumbnails, dim3((tw * th + 255) / 256), dim3(256), 0, (hipStream_t)st, (const uchar4*)f->fill.image.data,
                      (const float4*)f->fill.vertex.data, (const float4*)f->fill.normal.data, f->p.width, f->p.height, tw, th,
                      (unsigned char*)block_dev, (const float*)f->state->cur.pose, pose16_dst_dev, tick_dst_dev, tick);
@@ -1690,6 +1799,10 @@ int dms_fusion_join_map(dms_fusion* f, dms_fusion* owner, const float* relativeT
   int rc = share_model(f, owner);
   if (rc) return rc;
   const bool founder = f->model == f->own_model;
+  // (a skipped final prediction is of the maps as they are now: this camera's is rendered before it moves, the owner's before the
+  // consume changes its map - which only a founder's join does)
+  if ((rc = materialise_final_prediction(f, (hipStream_t)st, true))) return rc;
+  if (founder && (rc = materialise_final_prediction(owner, (hipStream_t)st, true))) return rc;
   DMS_REQUIRE(relativeTransform16, "join_map: the transform into the consuming map");
   DMS_REQUIRE(!founder || f->map_initialised, "join_map: a camera with a map of its own");
   DMS_REQUIRE(!f->adopting, "join_map: an imported camera's seeding frame is still pending");
@@ -1726,6 +1839,8 @@ int dms_fusion_import_camera(dms_fusion* f, dms_fusion* owner, const float* pose
   if (rc) return rc;
   DMS_REQUIRE(pose16 && last_rgb_dev && last_depth_dev && tick >= 2, "null argument / a camera that has not processed a frame");
   DMS_REQUIRE(!f->map_initialised && f->frames == 0, "import_camera: a context that has not processed a frame");
+  // (the seeding frame below fuses into the owner's map: a final prediction the owner skipped is rendered of the map as it is now)
+  if ((rc = materialise_final_prediction(owner, (hipStream_t)st, true))) return rc;
   f->model = owner->model;
   f->model->sharers += 1;
   f->model->count_hold = 3;
@@ -1751,6 +1866,8 @@ int dms_fusion_get_image(dms_fusion* f, int which, dms_image2d* view) {
                             &f->fill.normal,   &f->pred_old.image, &f->pred_old.vertex, &f->pred_old.normal, &f->pred_old.time};
   DMS_REQUIRE(which >= 0 && which < 20, "bad image id");
   DMS_REQUIRE(which < 16 || f->p.local_loop_closure || f->p.hybrid_loops, "the INACTIVE view exists only with local_loop_closure or hybrid_loops");
+  if (which >= 9 && which <= 15)
+    if (int rc = materialise_final_prediction(f, nullptr, false)) return rc;
   *view = *t[which];
   if (which >= 5 && which <= 8) {
     // the frame step keeps the index-map images column-major; hand out a row-major copy

@@ -15,6 +15,7 @@
 #include "smallmath.hpp"
 #include "surfel.hpp"
 #include "fill.hpp"
+#include "internal.hpp"
 #include "track_init.hpp"
 
 namespace dms {
@@ -942,7 +943,13 @@ __device__ __forceinline__ void sprite_range(float c, float size, int n, int& lo
 template <bool DUAL>
 __global__ __launch_bounds__(256) void k_splat_project(ProjArgs a, SurfelPlanes sp, size_t cap, const unsigned* __restrict__ d_count,
                                                        unsigned long long* __restrict__ zbuf, SplatSecond b2,
-                                                       unsigned long long* __restrict__ zbuf2) {
+                                                       unsigned long long* __restrict__ zbuf2, ProjectRider rd) {
+  // (a project pass that no resolve follows - the deferred final prediction of fusion_frame.hip - is the frame's last kernel:
+  // its block 0 carries what the resolve's block 0 would have, before anything else; both counts are 0 otherwise)
+  if (blockIdx.x == 0) {
+    if ((int)threadIdx.x < rd.mirror_words) rd.mirror_dst[threadIdx.x] = rd.mirror_src[threadIdx.x];
+    if ((int)threadIdx.x < rd.copy_words) rd.copy_dst[threadIdx.x] = rd.copy_src[threadIdx.x];
+  }
   __shared__ float s_par[10][256];  // pos.xyz, nrm.xyz, rad, window x / y of the centre, squared reach (below)
   __shared__ int s_box[4][256];     // x0, width, y0, cull survivors (DUAL)
   __shared__ unsigned s_off[257];   // exclusive prefix of the row counts
@@ -1226,6 +1233,7 @@ int splat_predict(dms_model* m, const dms_pose_block* pose, const dms_camera* ca
     DMS_CHECK_LAUNCH();
   }
   SplatSecond b2 = {0.f, 0, 0};
+  const ProjectRider no_rider = {nullptr, nullptr, 0, nullptr, nullptr, 0};
   if (resolve_only) {
     // the z-buffer was filled by an earlier dual pass with exactly these parameters
   } else if (second_conf_time_maxtime && zbuf2) {
@@ -1233,10 +1241,10 @@ int splat_predict(dms_model* m, const dms_pose_block* pose, const dms_camera* ca
     b2.time = (int)second_conf_time_maxtime[1];
     b2.maxTime = (int)second_conf_time_maxtime[2];
     hipLaunchKernelGGL(k_splat_project<true>, dim3(surfel_grid(m->count_upper)), dim3(256), 0, s, a, m->buf[m->cur], m->cap, m->d_count, zbuf, b2,
-                       zbuf2);
+                       zbuf2, no_rider);
   } else {
     hipLaunchKernelGGL(k_splat_project<false>, dim3(surfel_grid(m->count_upper)), dim3(256), 0, s, a, m->buf[m->cur], m->cap, m->d_count, zbuf,
-                       b2, (unsigned long long*)nullptr);
+                       b2, (unsigned long long*)nullptr, no_rider);
   }
   DMS_CHECK_LAUNCH();
   const FillArgs no_fill = {};
@@ -1258,6 +1266,33 @@ int splat_predict(dms_model* m, const dms_pose_block* pose, const dms_camera* ca
     hipLaunchKernelGGL((k_splat_resolve<false, false>), rg, dim3(256), 0, s, a, m->buf[m->cur], m->cap, zbuf, (uchar4*)out->image.data,
                        (float4*)out->vertex.data, (float4*)out->normal.data, (unsigned short*)out->time.data, (float*)nullptr, zclean, no_fill, no_init);
   }
+  DMS_CHECK_LAUNCH();
+  return DMS_OK;
+}
+
+// The project pass of splat_predict alone, into a CLEAN `zbuf` that a later splat_predict(..., resolve_only = 1) with the same
+// arguments resolves (and cleans): the same keys as a dual pass leaves in its second z-buffer for that cull - a cell's winner is
+// the minimum over the fragments that survive the cull, whatever else the pass feeds.  `rider`: see ProjectRider.
+int splat_project_only(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, float maxDepth, float confThreshold, int time,
+                       int timeIdx, int maxTime, int timeDelta, int active, unsigned long long* zbuf, hipStream_t s, const ProjectRider* rider) {
+  DMS_REQUIRE(m && pose && cam && zbuf, "null argument");
+  DMS_REQUIRE(!m->pending_update, "a deferred update pass is still pending (index_map applies it)");
+  DMS_REQUIRE(timeIdx >= 0 && timeIdx < DMS_MAX_SENSORS, "timeIdx out of range");
+  DMS_REQUIRE(fabsf(cam->fx) > 1e-18f && fabsf(cam->fx) < 1e18f && fabsf(cam->fy) > 1e-18f && fabsf(cam->fy) < 1e18f && maxDepth > 1e-18f && maxDepth < 1e18f,
+              "focal lengths and depth cut-off must be finite, non-zero and within 1e-18 .. 1e18");
+  DMS_REQUIRE(!rider || (rider->mirror_words >= 0 && rider->mirror_words <= 256 && rider->copy_words >= 0 && rider->copy_words <= 256 &&
+                         (rider->mirror_words == 0 || (rider->mirror_src && rider->mirror_dst)) &&
+                         (rider->copy_words == 0 || (rider->copy_src && rider->copy_dst))),
+              "a rider copies at most 256 dwords (one block)");
+  ProjArgs a;
+  fill_proj(a, m, pose, cam, maxDepth, time, timeIdx, timeDelta);
+  a.confThreshold = confThreshold;
+  a.maxTime = maxTime;
+  a.actv = active ? 1 : 0;
+  const SplatSecond b2 = {0.f, 0, 0};
+  const ProjectRider no_rider = {nullptr, nullptr, 0, nullptr, nullptr, 0};
+  hipLaunchKernelGGL(k_splat_project<false>, dim3(surfel_grid(m->count_upper)), dim3(256), 0, s, a, m->buf[m->cur], m->cap, m->d_count, zbuf,
+                     b2, (unsigned long long*)nullptr, rider ? *rider : no_rider);
   DMS_CHECK_LAUNCH();
   return DMS_OK;
 }

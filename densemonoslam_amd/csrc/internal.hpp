@@ -9,6 +9,18 @@ namespace dms {
 
 struct TrackInitArgs;  // track_init.hpp
 
+// fusion_map.hip: small copies that ride on block 0 of a splat project launch (at most 256 dwords each) - what block 0 of the
+// resolve pass carries when a resolve follows.  `mirror`: the frame's result block into its pinned host slot; `copy`: the pose
+// block the projection was rendered from, kept for a prediction that is resolved later (fusion_frame.hip, lazy_final_prediction).
+struct ProjectRider {
+  const unsigned* mirror_src;
+  unsigned* mirror_dst;
+  int mirror_words;
+  const unsigned* copy_src;
+  unsigned* copy_dst;
+  int copy_words;
+};
+
 // prep.hip
 int pyrDown(const dms_image2d* src, dms_image2d* dst, hipStream_t s);
 int createVMap(const dms_camera* intr, const dms_image2d* depth, dms_image2d* vmap, float cutoff, hipStream_t s);

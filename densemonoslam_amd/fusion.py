@@ -40,7 +40,7 @@ class FusionParams(C.Structure):
         ("nid_keyframing", C.c_int), ("nid_threshold", C.c_float), ("nid_depth_lambda", C.c_float), ("nid_bins_img", C.c_int),
         ("nid_bins_depth", C.c_int), ("nid_pyramid_level", C.c_int),
         ("local_loop_closure", C.c_int), ("reloc", C.c_int), ("num_sensors", C.c_int), ("share_projection", C.c_int),
-        ("fused_fill_in", C.c_int), ("hybrid_loops", C.c_int),
+        ("fused_fill_in", C.c_int), ("hybrid_loops", C.c_int), ("lazy_final_prediction", C.c_int),
     ]
 
 
@@ -120,6 +120,7 @@ lib.dms_fusion_import_camera.argtypes = [_P, _P, C.POINTER(C.c_float), _I, _P, _
 lib.dms_relative_transform.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
 lib.dms_pose_compose.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
 lib.dms_fusion_set_profiling.argtypes = [_P, _I]
+lib.dms_fusion_get_lazy_stats.argtypes = [_P, C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]
 
 
 class InterMapResult(C.Structure):
@@ -677,6 +678,12 @@ class ElasticFusion:
 
     def frameBlockWritten(self):
         return bool(lib.dms_fusion_frame_block_written(self.h))
+
+    def lazyStats(self):
+        """lazy_final_prediction: {eager, deferred, materialised, stale} (dms_fusion_get_lazy_stats)"""
+        e, d, m, st = C.c_int(0), C.c_long(0), C.c_long(0), C.c_long(0)
+        check(lib.dms_fusion_get_lazy_stats(self.h, C.byref(e), C.byref(d), C.byref(m), C.byref(st)), "dms_fusion_get_lazy_stats")
+        return {"eager": bool(e.value), "deferred": int(d.value), "materialised": int(m.value), "stale": int(st.value)}
 
     def loopConstraints(self):
         """Surface constraints of the last fetched frame's loop candidate: n x 7 float32

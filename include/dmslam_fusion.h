@@ -230,6 +230,23 @@ typedef struct dms_fusion_params {
    * (ElasticFusion.cpp:292-350) or through applyGlobalLoop (:1148-1240); 1 allocates the INACTIVE-view images and the
    * constraint buffer those blocks need.  Default 0. */
   int hybrid_loops;
+  /* 1 (default): a frame whose final prediction (ElasticFusion.cpp:586) nothing reads before the next frame's tracking prediction
+   * overwrites its images does not render it: the project pass fills the z-buffer of that next prediction only, the resolve + fill-in
+   * pass does not run, and the frame's result block reaches its pinned slot from the project launch.  Such a frame: share_projection's
+   * conditions hold (hybrid tracking, a map of the camera's own), fused_fill_in, one dms_fusion_process_frame call (not the _begin /
+   * _end pair), no frame block armed, no NID key-framing, no local_loop_closure, no hybrid_loops, the camera not lost, not the
+   * map's first frame.  The skipped prediction is rendered when somebody asks before the next frame begins - dms_fusion_get_image
+   * 9 - 15, dms_fusion_draw_panels, dms_fusion_thumbnails, dms_fusion_frame_block, dms_fusion_join_map, dms_fusion_import_camera
+   * into this camera's map - with the same bits (the frame's arguments, pose and live images are kept until then).  The first of
+   * these calls, whether it finds a skipped prediction or not, makes the context eager for the rest of its life: a viewer pays one
+   * extra project pass once, and a view obtained from dms_fusion_get_image 9 - 15 may be kept and read after later frames without
+   * asking again, as before: a view is valid for that once the context is eager, which the call that returned it has seen to.  If the map was
+   * changed on its handle between the frame and the request (dms_model_upload / _consume*), the images show the map as it is at the
+   * request, where the eager ones showed it as the frame left it (counted as `stale`); joins and imports render the record before
+   * they change the map, so they are not stale.
+   * Poses, results and the map are the same bits either way.  0: every frame renders its final prediction.
+   * DMS_LAZY_FINAL_PREDICTION=0 / 1 in the environment overrides the field (A/B runs). */
+  int lazy_final_prediction;
 } dms_fusion_params;
 
 void dms_fusion_default_params(dms_fusion_params* p, int width, int height, float fx, float fy, float cx, float cy);
@@ -300,6 +317,10 @@ int dms_fusion_process_frame_begin(dms_fusion* f, const void* rgb_dev, int rgb_c
                                    const float* inPose16, float weightMultiplier, dms_stream s);
 int dms_fusion_fetch_loop(dms_fusion* f, dms_frame_result* r, dms_stream s);
 int dms_fusion_process_frame_end(dms_fusion* f, const float* graph_host, int graph_nodes, const float* newPose16, dms_stream s);
+/* lazy_final_prediction: eager = 1 when the context renders every final prediction (the setting is off, or a skipped prediction has
+ * been asked for); deferred = frames that skipped theirs so far; materialised = skipped predictions rendered on demand; stale = those
+ * of them that found a map changed since the frame.  Any pointer may be NULL. */
+int dms_fusion_get_lazy_stats(dms_fusion* f, int* eager, long* deferred, long* materialised, long* stale);
 
 /* ORB-triggered global loop closure, device half (the block `if (hybrid_loops && orbTcwOld && orbTcwNew)` of
  * ElasticFusion::processFrame, ElasticFusion.cpp:292-350).  dms_fusion_set_orb_loop arms the NEXT
