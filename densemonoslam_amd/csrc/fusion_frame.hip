@@ -1900,6 +1900,11 @@ int dms_fusion_set_tracker_budget(dms_fusion* f, int max_blocks, int unchained) 
   return rc;
 }
 
+int dms_fusion_get_tracker_budget(dms_fusion* f, int* max_blocks, int* unchained) {
+  DMS_REQUIRE(f, "null argument");
+  return dms_odometry_get_resident_budget(f->odom, max_blocks, unchained);
+}
+
 int dms_fusion_set_option(dms_fusion* f, int option, double value) {
   DMS_REQUIRE(f, "null argument");
   DMS_REQUIRE(option >= 0 && option < DMS_OPT_COUNT, "unknown option");

@@ -483,6 +483,9 @@ __device__ __forceinline__ f3 surfel_colour(const RenderArgs& a, const SurfelPla
     const float s = fabsf((nr.x + nr.y) + nr.z) + 0.1f;
     c = mk3(x * s, y * s, z * s);
   } else if (!POINTS && a.colorType == 4) {
+    // The sum runs over the reference's three slots.  A surfel that only slots above 2 have seen has total = 0: every channel is
+    // 0 / 0 * s + 0.1 = NaN, which unorm8 writes as 0 (its isfinite test; no NaN is converted to an integer) - such a surfel is drawn
+    // black, with or without the window tint (tests/test_time_slots_gpu.py pins it, tests/render_ref.py does the same).
     const float4 nr = sp.nrm[i];
     const bool s0 = sp.times[i] != -3.f, s1 = sp.times[cap + i] != -3.f, s2 = sp.times[2 * cap + i] != -3.f;
     const float g = ((s0 ? 0.0f : 0.0f) + (s1 ? 0.8f : 0.0f)) + (s2 ? 0.0f : 0.0f);

@@ -175,6 +175,10 @@ int make_camera(dms_session* s, int c, Camera& cam) {
   fp.timeIdx = c;
   int rc = dms_fusion_create(&cam.f, &fp);
   if (rc) return rc;
+  // a camera created after the first tick (a merge moved it to this rank) carries what apply_tracker_policy has given the others: that
+  // function returns early while the cap is unchanged, and an uncapped, chained handle beside capped, unchained ones oversubscribes the device
+  if (s->late_told != -1 && (rc = dms_fusion_allow_late_frame(cam.f, s->late_told))) return rc;
+  if (s->tracker_cap > 0 && (rc = dms_fusion_set_tracker_budget(cam.f, s->tracker_cap, 1))) return rc;
   const size_t N = (size_t)s->W * s->H;
   if ((rc = dms_device_alloc(&cam.last_rgb, N * 3))) return rc;
   void* d = nullptr;

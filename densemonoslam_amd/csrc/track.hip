@@ -1968,6 +1968,13 @@ int dms_odometry_set_resident_budget(dms_odometry* o, int max_blocks, int unchai
   return DMS_OK;
 }
 
+int dms_odometry_get_resident_budget(dms_odometry* o, int* max_blocks, int* unchained) {
+  DMS_REQUIRE(o, "null argument");
+  if (max_blocks) *max_blocks = o->budget_cap;
+  if (unchained) *unchained = o->unchained_ok ? 1 : 0;
+  return DMS_OK;
+}
+
 int dms_odometry_get_mode(dms_odometry* o, int* resident, int* max_resident_blocks, int* fell_back) {
   DMS_REQUIRE(o, "null argument");
   if (resident) *resident = o->resident ? 1 : 0;
@@ -3233,14 +3240,20 @@ int dms_odometry_getIncrementalTransformation(dms_odometry* o, float* trans, flo
   dms_track_result* r = result ? result : &local;
   const bool was_resident = o->resident;
   rc = dms_odometry_fetch_result(o, r, s);
-  if (rc == DMS_ERR_TIMEOUT && was_resident && !o->resident) {
+  // A resident launch has kArPool spare word sets for repeated reductions, all iterations of its level together: a limit of that
+  // execution mode, not of the input.  An inter-map call (50 iterations per level on thumbnails, free to diverge) can use them up
+  // where launch-per-phase - like the oracle - repeats each reduction up to canon::kMaxRetries times and then goes on with zero
+  // sums.  Such a call is repeated launch-per-phase too; the handle stays resident.
+  const bool pool_out = rc == DMS_ERR_TIMEOUT && was_resident && o->resident && o->host_state->sync_timeout == 2;
+  if ((rc == DMS_ERR_TIMEOUT && was_resident && !o->resident) || pool_out) {
     // The resident kernels could not be co-resident: the same call again, launch-per-phase (the inputs are untouched; the
     // SO3 image swap of the first attempt, RGBDOdometry.cpp:595-601, is undone first).  Same bits as a resident run would give.
     if (so3)
       for (int i = 0; i < DMS_NUM_PYRS; i++) std::swap(o->lastNextImage[i], o->nextImage[i]);
+    o->resident = false;
     rc = dms_odometry_track_async(o, trans, rot, rgbOnly, icpWeight, pyramid, fastOdom, so3, interMap, s);
-    if (rc) return rc;
-    rc = dms_odometry_fetch_result(o, r, s);
+    if (!rc) rc = dms_odometry_fetch_result(o, r, s);
+    if (pool_out) o->resident = true;
   }
   if (rc) return rc;
   memcpy(trans, r->trans, 3 * sizeof(float));

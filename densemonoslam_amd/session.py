@@ -785,6 +785,17 @@ class NativeSession:
     def cams(self):
         return {c: _NativeCamera(self, c) for c in self.hosted()}
 
+    def tracker_budgets(self):
+        """camera -> (max_blocks, unchained) of every hosted camera's tracker (dms_fusion_get_tracker_budget): the session gives all of
+        them the same"""
+        out = {}
+        for c in self.hosted():
+            mb, un = _C.c_int(-1), _C.c_int(-1)
+            self.capi.check(self.lib.dms_fusion_get_tracker_budget(self.lib.dms_session_camera(self.h, c), _C.byref(mb), _C.byref(un)),
+                            "dms_fusion_get_tracker_budget")
+            out[c] = (mb.value, un.value)
+        return out
+
     @property
     def ferns(self):
         return {f: _NativeFerns(self, f) for f in sorted(set(self.frame_of)) if self.lib.dms_session_ferns(self.h, f)}

@@ -254,6 +254,8 @@ int dms_odometry_set_exec(dms_odometry* o, int resident, int early_exit, int coa
  * may track at the same time carry caps whose sum fits the device - their launches then skip the chain and overlap.  0, 0 = the default.
  * Same bits whatever the grid (the sums are order-free).  dms_session sets this for its cameras by itself. */
 int dms_odometry_set_resident_budget(dms_odometry* o, int max_blocks, int unchained);
+/* What the handle carries now (read only; either pointer may be null): the cap (0: none) and whether its launches skip the chain. */
+int dms_odometry_get_resident_budget(dms_odometry* o, int* max_blocks, int* unchained);
 /* DEPRECATED since round 6 (kept for callers built against rounds 1-5): fp64_sums and atomic_reduce have been ignored since round 3;
  * equals dms_odometry_set_exec(o, resident, early_exit, -1). */
 int dms_odometry_set_mode(dms_odometry* o, int resident, int fp64_sums, int early_exit, int atomic_reduce);

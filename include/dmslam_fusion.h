@@ -471,6 +471,8 @@ int dms_fusion_set_option(dms_fusion* f, int option, double value);
 /* dms_odometry_set_resident_budget (dmslam.h) for this context's trackers (frame-to-model and, with local loop closure, model-to-model);
  * between frames only. */
 int dms_fusion_set_tracker_budget(dms_fusion* f, int max_blocks, int unchained);
+/* What this context's frame-to-model tracker carries now (read only, at any time; either pointer may be null). */
+int dms_fusion_get_tracker_budget(dms_fusion* f, int* max_blocks, int* unchained);
 /* The "late frame": a context that is driven ALONE lets the host wait for the live half of a frame (the prep stream's event) and enqueue
  * the frame behind it, instead of a barrier packet on the frame's queue (about 10 us per frame; +1.2 - 1.4 % frame rate) - while the host
  * has the slack, which the context watches.  By default a context takes itself to be alone when it is the only live dms_fusion context

@@ -49,7 +49,9 @@ int dms_render_target_size(const dms_render_target* t, int* width, int* height);
 int dms_render_clear(dms_render_target* t, const float clear_rgba[4], dms_stream s);
 
 /* The uniforms of renderPointCloud.  color_type is the reference's precedence already applied (GlobalModel.cpp:436-440):
- * 4 contributions of cameras 0-2, 1 normals, 2 decoded colour, 3 init-time ramp, 0 shaded grey (points: 1, 2, else grey). */
+ * 4 contributions of cameras 0-2, 1 normals, 2 decoded colour, 3 init-time ramp, 0 shaded grey (points: 1, 2, else grey).
+ * Contributions count the reference's three time slots only: a surfel that none of cameras 0-2 has seen (a map with more cameras)
+ * has the colour 0 / 0 in every channel, which is written as 0 like every channel that is not finite - it is drawn black, alpha 255. */
 typedef struct dms_render_params {
   float mvp[16];          /* clip-from-world, row-major; with pose_dev: the projection only */
   const float* pose_dev;  /* optional: camera-to-world, 16 floats row-major in HBM (e.g. dms_fusion_pose_device); the view is then

@@ -427,6 +427,11 @@ def spawn(world, target, args):
 
 
 FOUR_TICKS, FOUR_TICKS_PIPELINED = 11, 20  # merges at ticks 6, 7, 8 (synchronous tick) / 9, 13, 17 (three ticks after each descriptor hit)
+# Eight cameras, one per time slot (tests/test_session_gpu.py).  Synchronous tick: merges (6,0,1) (6,3,4) (7,2,0) (8,3,2) (9,6,3) (12,5,6).
+# Pipelined: (9,3,0) (9,4,1) (13,4,3) (17,6,4) (22,2,6) - 23 is the smallest tick count at which the oracle session with wake_latency = 3
+# shows at least five merges and a map with at least six live slots (its fifth merge happens in tick 22).
+EIGHT_OFFSETS = (0, 8, 16, 24, 32, 40, 48, 56)
+EIGHT_TICKS, EIGHT_TICKS_PIPELINED = 16, 23
 
 
 @pytest.mark.parametrize("world,wake", [(4, None), (2, 3)])
