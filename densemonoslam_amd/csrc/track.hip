@@ -91,6 +91,8 @@ struct dms_odometry {
   int budget_cap = 0;
   bool unchained_ok = false;
   bool fell_back = false;     // a resident kernel timed out at a grid-wide wait: this handle has switched to launch-per-phase
+  // what persistent_shape() gave each level of the last tracker call (dms_odometry_get_level_shape); 0 blocks: launch-per-phase
+  int last_shape_P[DMS_NUM_PYRS] = {1, 1, 1}, last_shape_nb[DMS_NUM_PYRS] = {0, 0, 0};
   // the model pyramid's last step (level 1 -> 2 of lastDepth / lastImage), left to the next track call's first kernel
   bool deferred_pyr = false;
   // the set-up of the next track call ran inside the model pyramid kernel (odometry_initModel_fused, fold_init): that call then
@@ -913,7 +915,10 @@ __device__ __forceinline__ bool ar_wait(const unsigned long long* w, int slot, b
       return true;
     }
     ++spins;
-    if (spins > kSpinLimit || ((spins & 1023u) == 0u && __hip_atomic_load(timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
+    // (only another block's timeout, 1, ends this wait.  2 = "retry pool exhausted" is stored by blocks that have already seen THESE
+    // totals complete, or by an earlier stage: the words this block polls still fill up, and leaving with fld = 0 would take this
+    // block alone down another path than the rest of the grid)
+    if (spins > kSpinLimit || ((spins & 1023u) == 0u && __hip_atomic_load(timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1)) {
       __hip_atomic_store(timeout, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // never hang the device
       fld_out = 0;
       return false;
@@ -1983,6 +1988,15 @@ int dms_odometry_get_mode(dms_odometry* o, int* resident, int* max_resident_bloc
   return DMS_OK;
 }
 
+int dms_odometry_get_level_shape(dms_odometry* o, int level, int* pixels_per_thread, int* blocks, int* resident) {
+  DMS_REQUIRE(o, "null argument");
+  DMS_REQUIRE(level >= 0 && level < DMS_NUM_PYRS, "bad level");
+  if (pixels_per_thread) *pixels_per_thread = o->last_shape_P[level];
+  if (blocks) *blocks = o->last_shape_nb[level];
+  if (resident) *resident = o->last_shape_nb[level] > 0 ? 1 : 0;
+  return DMS_OK;
+}
+
 int dms_odometry_canon_retries(dms_odometry* o, int* retries) {
   DMS_REQUIRE(o && retries, "null argument");
   *retries = o->host_state->canon_retries;
@@ -2567,6 +2581,8 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
     pnb = 0;
     if (o->resident && (iterations[l] <= kArRing || o->long_levels_resident))  // (more iterations than ring sets: the ring is re-armed in flight)
       persistent_shape(o->vmaps_curr[l].cols * (o->vmaps_curr[l].rows / 3), o->persist_target, budget_of(o), pP, pnb);
+    o->last_shape_P[l] = pP;
+    o->last_shape_nb[l] = pnb;
   };
 
   // SO3 + level 2 + level 1 in one resident launch (k_track_coarse) when all three are resident stages of this call and their shapes

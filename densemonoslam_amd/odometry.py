@@ -266,6 +266,12 @@ class RGBDOdometry:
         check(lib.dms_odometry_get_mode(self.h, C.byref(a), C.byref(b), C.byref(c)), "dms_odometry_get_mode")
         return bool(a.value), b.value, bool(c.value)
 
+    def levelShape(self, level):
+        """(pixels_per_thread, blocks, resident) of pyramid level `level` in the last tracker call; blocks = 0: launch-per-phase"""
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(lib.dms_odometry_get_level_shape(self.h, int(level), C.byref(a), C.byref(b), C.byref(c)), "dms_odometry_get_level_shape")
+        return a.value, b.value, bool(c.value)
+
     def setExpBias(self, bias):
         """test hook: bias of the static exponents of a call's first reductions (csrc/canon.hpp)"""
         check(lib.dms_odometry_debug_set(self.h, b"exp_bias", int(bias)), "dms_odometry_debug_set")

@@ -268,6 +268,16 @@ int dms_odometry_fall_back_to_launches(dms_odometry* o);
  * compute units), the handle switches to launch-per-phase for good (`fell_back`); dms_odometry_getIncrementalTransformation
  * repeats that call at once — same bits either way. */
 int dms_odometry_get_mode(dms_odometry* o, int* resident, int* max_resident_blocks, int* fell_back);
+/* Launch shape of pyramid level `level` in the last tracker call enqueued on this handle: the pixels per thread (1 - 5) and the
+ * block count that the shape rule gave the level from its pixel count and the handle's residency bound.  blocks = 0 /
+ * resident = 0: the level ran (or, with no iterations, would have run) launch-per-phase.  Read-only; any output may be null.
+ * It is the rule's answer for the level, which is the grid of the level's own resident kernel except that
+ *  - with the coarse launch (DMS_TRACK_FUSE=1 / dms_odometry_set_exec) levels 2 and 1 run inside ONE kernel on level 1's grid:
+ *    level 2 then reports the shape it would have on its own, not the larger grid it ran on;
+ *  - a synchronous call that used up a resident launch's retry pool is repeated launch-per-phase, and that repeat is the last
+ *    call enqueued: every level reports 0 blocks although the handle is still resident (dms_odometry_get_mode) and the next
+ *    call runs resident again. */
+int dms_odometry_get_level_shape(dms_odometry* o, int level, int* pixels_per_thread, int* blocks, int* resident);
 /* Fault injection for tests: the next `calls` tracking calls behave as if a resident kernel had timed out at a
  * grid barrier (DMS_ERR_TIMEOUT from dms_odometry_fetch_result; the frame step keeps the prior pose and fuses nothing). */
 int dms_odometry_inject_timeout(dms_odometry* o, int calls);

@@ -40,6 +40,18 @@ def test_version_and_error_text_without_gpu():
     assert rc in (0, -2)
 
 
+def test_level_shape_accessor_validates_its_arguments_without_gpu():
+    """dms_odometry_get_level_shape (the launch shape of a pyramid level in the last tracker call) is declared, exported and
+    rejects a null handle before any device access."""
+    from densemonoslam_amd import capi
+
+    assert "dms_odometry_get_level_shape" in declared_functions()
+    p, nb, res = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+    assert capi.lib.dms_odometry_get_level_shape(None, 0, ctypes.byref(p), ctypes.byref(nb), ctypes.byref(res)) == -1
+    assert b"null" in capi.lib.dms_last_error()
+    assert (p.value, nb.value, res.value) == (-1, -1, -1)
+
+
 def test_struct_sizes_match_reference_types():
     """JtJJtrSE3 = 29 floats, DataTerm = 16 bytes (Cuda/types.cuh:77-83,123-171)."""
     from densemonoslam_amd import capi

@@ -361,15 +361,13 @@ def test_clean_health_rule_counts_the_reference_sensor_slots(fus, orc, boot):
 # whole frame step
 # ------------------------------------------------------------------------------------------
 def test_process_frame_pipeline_parity(fus, orc, synth):
-    """ElasticFusion::processFrame over a short synthetic stream: per-step pose within the
-    north-star bar against the oracle pipeline, and — teacher-forced on the GPU's own state —
-    integer-exact association."""
+    """ElasticFusion::processFrame over a short synthetic stream: per-step pose identical to the
+    oracle pipeline's, and — teacher-forced on the GPU's own state — integer-exact association."""
     from oracle import orc_pipeline
 
     g = fus.ElasticFusion(W, H, K, model_capacity=600000)
     o = orc_pipeline.ElasticFusion(W, H, K, model_capacity=600000)
     n_frames = 6
-    worst_t = worst_r = 0.0
     for k in range(n_frames):
         d, rgb, _ = synth.frame(k, width=W, height=H, K=K, noise=True)
         model_before = o.model.copy()  # == the GPU's map (forced below)
@@ -377,8 +375,7 @@ def test_process_frame_pipeline_parity(fus, orc, synth):
         ro = o.processFrame(rgb, d)
         pose_g = np.array(rg.pose, np.float32).reshape(4, 4)
         # per-step pose parity: both sides started this step from the same map and pose
-        dt, da = helpers.assert_pose_close(pose_g[:3, 3], pose_g[:3, :3], ro.pose[:3, 3], ro.pose[:3, :3], what="frame %d" % k)
-        worst_t, worst_r = max(worst_t, dt), max(worst_r, da)
+        helpers.assert_pose_identical(pose_g[:3, 3], pose_g[:3, :3], ro.pose[:3, 3], ro.pose[:3, :3], what="frame %d" % k)
         assert rg.tick == ro.tick and bool(rg.fused) == ro.fused and bool(rg.fill_in) == ro.fill_in
         assert abs(rg.weighting - ro.weighting) < 0.05
         # pre-processing is input-only: exact
@@ -403,17 +400,12 @@ def test_process_frame_pipeline_parity(fus, orc, synth):
             po = orc.splat_predict(mg, pose_g, K, H, W, 25.0, 10.0, time, 0, time, 200, True)
             assert_bits(g.image(10), po[1], "final predicted vertex, frame %d" % k)
             assert_bits(g.image(9), po[0], "final predicted image, frame %d" % k)
-            # the oracle's own free-running map stays close in size (poses differ by ~1e-6)
-            assert abs(int(rg.surfels) - ro.surfels) <= max(10, 2e-3 * ro.surfels), (rg.surfels, ro.surfels)
+            # the oracle's own step from the same map and pose ends on the same map size
+            assert int(rg.surfels) == ro.surfels, (rg.surfels, ro.surfels)
         # teacher forcing: the next step starts from the GPU's state on both sides
         o.model = mg.copy()
         o.currPose = pose_g.copy()
     assert rg.surfels > 100000
-    # per-step differences come from the fp32 tree sums (GPU) vs fp64 sums (oracle) of the same
-    # products, amplified by 29 Gauss-Newton iterations on a near-planar scene; observed on
-    # MI355X: 8e-5 m, 2e-3 deg.  Half the north-star bar (1 mm, 0.01 deg) is required here.
-    print("worst per-step pose difference vs oracle: %.3e m, %.3e deg" % (worst_t, worst_r))
-    assert worst_t < 5e-4 and worst_r < 5e-3, (worst_t, worst_r)
 
 
 def test_process_frame_pipelined_equals_serial(fus, synth, monkeypatch):
@@ -461,9 +453,12 @@ def test_process_frame_pipelined_equals_serial(fus, synth, monkeypatch):
 
 
 def test_frame_step_tracker_modes_agree(fus, synth, monkeypatch):
-    """The frame step with the launch-per-phase tracker (DMS_TRACK_MODE=launches, the fallback) and
-    with the resident level kernels stays on the same trajectory (free-running drift bound) with the
-    same iteration counts; each mode is checked against the oracle per step in test_tracking_gpu."""
+    """The frame step with the launch-per-phase tracker (DMS_TRACK_MODE=launches, the fallback) and with the resident level
+    kernels: both sum the same integers (csrc/canon.hpp), so five free-running frames give the same pose bytes, tracker side
+    outputs and surfel count after every frame and the same map at the end - and the launch-per-phase run, the one the other
+    frame-step tests do not take, equals the oracle's free run as well."""
+    from oracle import orc_pipeline
+
     frames = [synth.frame(k, width=W, height=H, K=K, noise=True) for k in range(5)]
     res = {}
     for mode in ("persistent", "launches"):
@@ -472,20 +467,21 @@ def test_frame_step_tracker_modes_agree(fus, synth, monkeypatch):
         else:
             monkeypatch.delenv("DMS_TRACK_MODE", raising=False)
         g = fus.ElasticFusion(W, H, K, model_capacity=600000)
-        poses = []
+        steps = []
         for d, rgb, _ in frames:
             r = g.processFrame(rgb, d)
-            poses.append(np.array(r.pose, np.float32).reshape(4, 4))
-        res[mode] = (poses, int(r.surfels), r.track)
-    monkeypatch.delenv("DMS_TRACK_MODE", raising=False)
-    for k, (pa, pb) in enumerate(zip(*[res[m][0] for m in ("persistent", "launches")])):
-        # free-running: 1e-8-level differences of the sums flip correspondences on this noisy, mostly planar
-        # scene, so the two trajectories drift apart like the GPU and the oracle do (same bound as
-        # test_process_frame_free_running_drift_is_bounded)
-        assert np.linalg.norm(pa[:3, 3] - pb[:3, 3]) < 5e-3, k
-        assert helpers.rot_angle_deg(pa[:3, :3], pb[:3, :3]) < 0.2, k
-    assert abs(res["persistent"][1] - res["launches"][1]) <= 0.01 * res["launches"][1]
-    assert list(res["persistent"][2].iterations_run) == list(res["launches"][2].iterations_run) == [10, 5, 4]
+            t = r.track
+            steps.append((np.array(r.pose, np.float32).tobytes(), int(r.surfels), list(t.iterations_run), t.so3_iterations_run,
+                          np.array([t.lastICPError, t.lastICPCount, t.lastRGBError, t.lastRGBCount, t.lastSO3Error, t.lastSO3Count], np.float32).tobytes(),
+                          np.array(t.lastA).tobytes(), np.array(t.lastb).tobytes()))
+        res[mode] = (steps, g.globalModel().downloadMap())
+        g.close()
+    for k, (a, b) in enumerate(zip(res["persistent"][0], res["launches"][0])):
+        for what, x, y in zip(("pose", "surfels", "iterations", "SO3 iterations", "errors and counts", "lastA", "lastb"), a, b):
+            assert x == y, "frame %d: %s differs between the resident and the launch-per-phase tracker" % (k, what)
+    surfels_equal(res["persistent"][1], res["launches"][1], "map, resident against launch-per-phase")
+    assert res["persistent"][0][-1][2] == [10, 5, 4]
+    _free_run_identical(fus, synth, orc_pipeline, W, H, K, 5, {})  # (DMS_TRACK_MODE=launches is still set: read when the tracker is created)
 
 
 def test_two_cameras_on_two_streams(fus, synth):
@@ -743,7 +739,6 @@ def test_local_loop_closure_candidate(fus, orc, synth):
     g = fus.ElasticFusion(W6, H6, K6, **opts)
     o = orc_pipeline.ElasticFusion(W6, H6, K6, **opts)
     accepted = 0
-    worst_t = worst_r = 0.0
     for k in range(7):
         d, rgb, _ = synth.frame(k, width=W6, height=H6, K=K6, noise=True)
         if 2 <= k <= 4:
@@ -752,10 +747,10 @@ def test_local_loop_closure_candidate(fus, orc, synth):
         rg = g.processFrame(rgb, d)
         ro = o.processFrame(rgb, d)
         pose_g = np.array(rg.pose, np.float32).reshape(4, 4)
-        helpers.assert_pose_close(pose_g[:3, 3], pose_g[:3, :3], ro.pose[:3, 3], ro.pose[:3, :3], what="frame %d" % k)
+        helpers.assert_pose_identical(pose_g[:3, 3], pose_g[:3, :3], ro.pose[:3, 3], ro.pose[:3, :3], what="frame %d" % k)
         if k > 0:
-            # the oracle tracked to a pose ~1e-5 away, which moves splat edges by whole pixels: replay its loop
-            # block from the GPU's post-tracking pose and the pre-fusion map both sides share
+            # the loop block replayed by the oracle from the post-tracking pose and the pre-fusion map both sides share
+            # (the poses are the same bits, above; the replay is kept because it isolates the block from the rest of the frame)
             time = rg.tick - 1
             o.model, o.currPose, o.tick = model_before, pose_g.copy(), time
             o.predict(o.confidence)
@@ -770,8 +765,7 @@ def test_local_loop_closure_candidate(fus, orc, synth):
             if L.track.lastICPCount > 0:
                 assert rg.loop_icp_error == pytest.approx(L.track.lastICPError, rel=2e-2), k
                 lp = np.array(rg.loop_pose, np.float32).reshape(4, 4)
-                dt, da = helpers.assert_pose_close(lp[:3, 3], lp[:3, :3], L.estPose[:3, 3], L.estPose[:3, :3], what="loop pose, frame %d" % k)
-                worst_t, worst_r = max(worst_t, dt), max(worst_r, da)
+                helpers.assert_pose_identical(lp[:3, 3], lp[:3, :3], L.estPose[:3, 3], L.estPose[:3, :3], what="loop pose, frame %d" % k)
                 assert np.allclose(np.array(rg.loop_cov_diag), np.diag(L.covar), rtol=2e-2), k
             assert bool(rg.loop_ok) == L.ok, k
             cg = g.loopConstraints()
@@ -789,7 +783,6 @@ def test_local_loop_closure_candidate(fus, orc, synth):
         o.currPose = pose_g.copy()
         model_before = mg
     assert accepted >= 3, accepted
-    print("loop candidate: %d accepted, worst loop-pose difference %.3e m, %.3e deg" % (accepted, worst_t, worst_r))
 
 
 def _fake_graph(rng, nn, tmax):
@@ -857,9 +850,8 @@ def test_two_phase_frame_step_with_deformation(fus, orc, synth):
                                  cap=2500000)
             surfels_equal(mg, m3, "map after frame %d (deformed=%s)" % (k, graph is not None))
             assert bool(rg.fused)
-            # the free-running oracle pipeline (its own tracking, same callback) stays within the usual bound
-            helpers.assert_pose_close(pose_g[:3, 3], pose_g[:3, :3], ro.pose[:3, 3], ro.pose[:3, :3], tol_m=1e-3, tol_deg=0.01,
-                                      what="frame %d" % k)
+            # the oracle pipeline (its own tracking from the state both sides share, same callback) ends on the same pose
+            helpers.assert_pose_identical(pose_g[:3, 3], pose_g[:3, :3], ro.pose[:3, 3], ro.pose[:3, :3], what="frame %d" % k)
         o.model = mg.copy()
         o.currPose = pose_g.copy()
         model_before = mg
@@ -891,7 +883,7 @@ def test_tracking_failure_detection(fus, orc, synth):
         assert bool(rg.fused) == ro.fused and rg.tick == ro.tick and rg.surfels == ro.surfels, what
         pose_g = np.array(rg.pose, np.float32).reshape(4, 4)
         if k > 0 and ro.track.lastICPCount > 10000:  # (a handful of correspondences on garbage depth is not a conditioned problem)
-            helpers.assert_pose_close(pose_g[:3, 3], pose_g[:3, :3], ro.pose[:3, 3], ro.pose[:3, :3], what=what)
+            helpers.assert_pose_identical(pose_g[:3, 3], pose_g[:3, :3], ro.pose[:3, 3], ro.pose[:3, :3], what=what)
             assert rg.track.lastICPCount == pytest.approx(ro.track.lastICPCount, rel=2e-3), what
         if ro.lost and not seen_lost:
             seen_lost = True
@@ -922,20 +914,12 @@ def test_global_predict_is_dead_work(fus, synth):
 
 
 def test_process_frame_free_running_drift_is_bounded(fus, orc, synth):
-    """Without teacher forcing the two float implementations drift apart slowly (correspondences
-    flip under 1e-6 pose differences); the drift stays far below the scene scale."""
+    """Without teacher forcing the two implementations do not drift apart at all: canonical sums and a canonical scalar section
+    make every pose a pure function of the inputs, so five free-running frames hold the same bits after every step.  (The name is
+    from the time the bound was 5 mm / 0.2 degree; the bound is zero.)"""
     from oracle import orc_pipeline
 
-    g = fus.ElasticFusion(W, H, K, model_capacity=600000)
-    o = orc_pipeline.ElasticFusion(W, H, K, model_capacity=600000)
-    for k in range(5):
-        d, rgb, _ = synth.frame(k, width=W, height=H, K=K, noise=True)
-        rg = g.processFrame(rgb, d)
-        ro = o.processFrame(rgb, d)
-    pose_g = np.array(rg.pose, np.float32).reshape(4, 4)
-    assert np.linalg.norm(pose_g[:3, 3] - ro.pose[:3, 3]) < 5e-3
-    assert helpers.rot_angle_deg(pose_g[:3, :3], ro.pose[:3, :3]) < 0.2
-    assert abs(int(rg.surfels) - ro.surfels) <= 0.01 * ro.surfels
+    _free_run_identical(fus, synth, orc_pipeline, W, H, K, 5, {})
 
 
 def test_process_frame_with_pose_prior_and_no_tracking(fus, orc, synth):
@@ -963,8 +947,8 @@ def test_process_frame_with_pose_prior_and_no_tracking(fus, orc, synth):
 
 def test_process_frame_kitti_resolution_1241x376(fus, orc, synth):
     """BASELINE config 4 geometry: odd width, 620x188 / 310x94 pyramid levels, KITTI intrinsics,
-    40 m depth cut-off.  Pose prior taken as is for two frames (exact map parity), then one tracked
-    frame (pose within the bar)."""
+    40 m depth cut-off.  Pose prior taken as is for three frames (exact map parity), then two free-running
+    frames, one of them tracked: the same bits."""
     from oracle import orc_pipeline
 
     Wk, Hk = 1241, 376
@@ -984,22 +968,22 @@ def test_process_frame_kitti_resolution_1241x376(fus, orc, synth):
         surfels_equal(g.globalModel().downloadMap(), o.model, "1241x376 map after frame %d" % k)
         assert_bits(g.image(10), o.pred[1], "predicted vertex")
     # tracked frame from the same state
-    g2 = fus.ElasticFusion(Wk, Hk, Kk, **opts)
-    o2 = orc_pipeline.ElasticFusion(Wk, Hk, Kk, **opts)
-    for k in range(2):
-        d, rgb, T = synth.frame(k, width=Wk, height=Hk, K=Kk, noise=True)
-        rg = g2.processFrame(rgb, d)
-        ro = o2.processFrame(rgb, d)
-        pose_g = np.array(rg.pose, np.float32).reshape(4, 4)
-        helpers.assert_pose_close(pose_g[:3, 3], pose_g[:3, :3], ro.pose[:3, 3], ro.pose[:3, :3], what="1241x376 frame %d" % k)
+    g.close()
+    rg, _ = _free_run_identical(fus, synth, orc_pipeline, Wk, Hk, Kk, 2, dict(depthCut=40.0), retries_per_frame=0.05)
     assert rg.track.iterations_run[0] == 10 and rg.track.iterations_run[1] == 5 and rg.track.iterations_run[2] == 4
 
 
-@pytest.mark.parametrize("size", [(333, 251), (164, 126), (646, 486)])
+# repeated reductions of the ORACLE over the 5 tracked frames of a 6-frame free run (the cap of _free_run_identical counts them):
+# none at the other sizes, 2 + 2 + 0 + 1 + 0 = 5 at 40x40 (a 10x10 top level: the static first-iteration exponents do not fit)
+RAGGED_RETRIES_PER_FRAME = {(40, 40): 0.84}
+
+
+@pytest.mark.parametrize("size", [(333, 251), (164, 126), (646, 486), (40, 40), (77, 47)])
 def test_process_frame_ragged_resolutions(fus, orc, synth, size):
     """Resolutions that are not multiples of the 8 x 8 wave tiles, the 64 x 4 pixel blocks, the 2 x 2
-    candidate grid or the /2 pyramid steps: with the pose prior taken as is the map, the filtered depth
-    and the predictions must equal the oracle's byte for byte; one tracked frame stays within the bar."""
+    candidate grid or the /2 pyramid steps (40x40 is the frame step's minimum): with the pose prior taken as is the map, the
+    filtered depth and the predictions must equal the oracle's byte for byte; six free-running frames - five tracked on pyramid
+    levels that end in partial blocks - hold the same bits after every step, and the same map at the end."""
     from oracle import orc_pipeline
 
     Wr, Hr = size
@@ -1021,16 +1005,9 @@ def test_process_frame_ragged_resolutions(fus, orc, synth, size):
         assert_bits(g.image(10), o.pred[1], "predicted vertex")
         assert_bits(g.image(9), o.pred[0], "predicted image")
         assert_bits(g.image(14), o.fill[1], "fill-in vertex")
-    g2 = fus.ElasticFusion(Wr, Hr, Kr, **opts)
-    o2 = orc_pipeline.ElasticFusion(Wr, Hr, Kr, **opts)
-    for k in range(2):
-        d, rgb, T = synth.frame(k, width=Wr, height=Hr, K=Kr, noise=True)
-        rg = g2.processFrame(rgb, d)
-        ro = o2.processFrame(rgb, d)
-        pose_g = np.array(rg.pose, np.float32).reshape(4, 4)
-        helpers.assert_pose_close(pose_g[:3, 3], pose_g[:3, :3], ro.pose[:3, 3], ro.pose[:3, :3], what="%dx%d frame %d" % (Wr, Hr, k))
     g.close()
-    g2.close()
+    # (646x486 needs more than 600 000 surfels after six frames - 641 805: the helper's capacity of 4 000 000)
+    _free_run_identical(fus, synth, orc_pipeline, Wr, Hr, Kr, 6, {}, retries_per_frame=RAGGED_RETRIES_PER_FRAME.get(size, 0.1))
 
 
 def test_frame_step_reproduces_fusion_golden(fus):
@@ -1102,33 +1079,38 @@ FRAME_CONFIGS = {
 }
 
 
+# repeated reductions of the ORACLE over the 5 tracked frames of the 6-frame runs below: frameToFrameRGB tracks against the previous
+# live image instead of the model's, and its photometric sums outgrow the static exponents on every frame (1 + 3 + 1 + 1 + 2 = 8, at
+# most 3 in one call: inside the 6 spare word sets of each resident launch); none for the other option sets
+FRAME_CONFIG_RETRIES_PER_FRAME = {"frame_to_frame_rgb": 1.34}
+
+
+def _oracle_options(cfg):
+    return {k: (bool(v) if k in ("fastOdom", "pyramid", "so3", "frameToFrameRGB", "rgbOnly") else v) for k, v in cfg.items()}
+
+
 @pytest.mark.parametrize("name", list(FRAME_CONFIGS))
 def test_process_frame_option_matrix(fus, orc, synth, name):
-    """The frame step under the tracker / fusion options of dms_fusion_params, teacher-forced per step
-    against the oracle pipeline: pose within the bar, identical decisions, identical map size."""
+    """The frame step under the tracker / fusion options of dms_fusion_params, free-running beside the oracle pipeline for six
+    frames: the same pose bytes, decisions and tracker side outputs after every frame, the same map at the end."""
     from oracle import orc_pipeline
 
     cfg = FRAME_CONFIGS[name]
-    ocfg = {k: (bool(v) if k in ("fastOdom", "pyramid", "so3", "frameToFrameRGB", "rgbOnly") else v) for k, v in cfg.items()}
-    g = fus.ElasticFusion(W, H, K, model_capacity=600000, **cfg)
-    o = orc_pipeline.ElasticFusion(W, H, K, model_capacity=600000, **ocfg)
-    for k in range(4):
-        d, rgb, _ = synth.frame(k, width=W, height=H, K=K, noise=True)
-        rg = g.processFrame(rgb, d)
-        ro = o.processFrame(rgb, d)
-        pose_g = np.array(rg.pose, np.float32).reshape(4, 4)
-        helpers.assert_pose_close(pose_g[:3, 3], pose_g[:3, :3], ro.pose[:3, 3], ro.pose[:3, :3], what="%s frame %d" % (name, k))
-        assert bool(rg.fused) == ro.fused and bool(rg.fill_in) == ro.fill_in and rg.tick == ro.tick, (name, k)
-        if k > 0:
-            assert list(rg.track.iterations_run) == list(ro.track.iterations_run), (name, k)
-            assert rg.track.so3_iterations_run == ro.track.so3_iterations_run, (name, k)
-        mg = g.globalModel().downloadMap()
-        assert abs(len(mg) - ro.surfels) <= max(10, 2e-3 * ro.surfels), (name, k, len(mg), ro.surfels)
-        o.model = mg.copy()
-        o.currPose = pose_g.copy()
+    rg, ro = _free_run_identical(fus, synth, orc_pipeline, W, H, K, 6, _oracle_options(cfg), gopts=cfg,
+                                 retries_per_frame=FRAME_CONFIG_RETRIES_PER_FRAME.get(name, 0.1))
     if cfg.get("rgbOnly"):
         assert not rg.fused and rg.track.lastICPCount == 0
-    g.close()
+    if name == "frame_to_frame_rgb":
+        assert ro.track.canon_retries > 0  # (the one option set that repeats reductions inside the frame step)
+
+
+def test_process_frame_option_matrix_c2_at_640x480(fus, orc, synth):
+    """BASELINE config 2 (ICP only, fast odometry, one pyramid level) at the headline resolution, free-running for four frames."""
+    from oracle import orc_pipeline
+
+    cfg = FRAME_CONFIGS["C2_icp_fast_single_level"]
+    rg, _ = _free_run_identical(fus, synth, orc_pipeline, 640, 480, synth.K_640, 4, _oracle_options(cfg), gopts=cfg)
+    assert list(rg.track.iterations_run) == [3, 0, 0]
 
 
 def test_nid_gate_with_inactive_view(fus, orc, synth):
@@ -1242,8 +1224,15 @@ def _free_run_identical(fus, synth, orc_pipeline, W2, H2, K2, n, opts, gopts=Non
         assert int(rg.surfels) == ro.surfels, (k, rg.surfels, ro.surfels)
         if k > 0:
             assert list(rg.track.iterations_run) == list(ro.track.iterations_run), k
+            assert rg.track.so3_iterations_run == ro.track.so3_iterations_run, k
             for f in ("lastICPError", "lastICPCount", "lastRGBError", "lastRGBCount", "lastSO3Error", "lastSO3Count"):
-                assert np.float32(getattr(rg.track, f)).tobytes() == np.float32(getattr(ro.track, f)).tobytes(), (k, f)
+                a, b = np.float32(getattr(rg.track, f)), np.float32(getattr(ro.track, f))
+                # The same bytes - but for the one value whose bits no rule fixes: the error of a term without a single correspondence
+                # (switched off, or nothing matched) is 0 / 0, a NaN whose sign bit is the dividing unit's choice (set on the host,
+                # clear on the device).  Only an error field, only beside a count of exactly zero on both sides.
+                cnt = f.replace("Error", "Count")
+                empty = f.endswith("Error") and np.float32(getattr(rg.track, cnt)) == 0 and np.float32(getattr(ro.track, cnt)) == 0
+                assert a.tobytes() == b.tobytes() or (empty and np.isnan(a) and np.isnan(b)), (k, f, a, b)
             assert np.array(rg.track.lastA).tobytes() == np.array(ro.track.lastA).tobytes(), k
             retries += ro.track.canon_retries
     surfels_equal(g.globalModel().downloadMap(), o.model, "map after %d free-running frames" % n)
@@ -1251,6 +1240,7 @@ def _free_run_identical(fus, synth, orc_pipeline, W2, H2, K2, n, opts, gopts=Non
     # exception where the static first-iteration exponents fit the stream
     assert retries <= max(2, int(n * retries_per_frame)), retries
     g.close()
+    return rg, ro
 
 
 def test_free_run_identical_at_kitti_size_1241x376(fus, orc, synth):

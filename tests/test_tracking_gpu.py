@@ -311,6 +311,174 @@ def test_so3Step_parity(dms, orc, tracker_pair):
         _sum_close(rg[0], ro[0], what="so3 residual")
 
 
+# ---- the same operators on the three levels of ragged synthetic pairs ----
+# 77x47 (38x23, 19x11): odd in both directions at every level, `py = i / cols` with odd cols, odd halves.
+# 333x251 (166x125, 83x62): no level is a multiple of the 512-pixel chunks the launch-per-phase kernels hand out
+# (83583 = 163 * 512 + 127, 20750 = 40 * 512 + 270, 5146 = 10 * 512 + 26), and level 1's last chunk reaches 103 valid pixels
+# above the invalid last row.
+RAGGED_OP_SIZES = [(77, 47), (333, 251)]
+
+
+def _synth_K(W, H):
+    return (0.825 * W, 0.825 * W, W / 2.0 - 0.25, H / 2.0 + 0.25)
+
+
+@pytest.fixture(scope="module")
+def synth_inputs(orc):
+    """synth_inputs(W, H): noise-free synthetic frames 10 / 11 at W x H and the model maps of frame 10, as
+    test_track_recovers_known_motion_synthetic builds them.  Rendered once per size and module."""
+    cache = {}
+
+    def get(W, H):
+        if (W, H) not in cache:
+            from densemonoslam_amd import synth
+
+            K = _synth_K(W, H)
+            d1, rgb1, T1 = synth.frame(10, width=W, height=H, K=K, noise=False)
+            d2, rgb2, _ = synth.frame(11, width=W, height=H, K=K, noise=False)
+            vo = orc.createVMap(K, d1, 20.0)
+            no = orc.createNMap(vo)
+            verts = np.zeros((H, W, 4), np.float32)
+            norms = np.zeros((H, W, 4), np.float32)
+            ok = ~np.isnan(vo[:H]) & ~np.isnan(no[:H])
+            for c in range(3):
+                verts[..., c] = np.where(ok, vo[c * H:(c + 1) * H], 0)
+                norms[..., c] = np.where(ok, no[c * H:(c + 1) * H], 0)
+            cache[(W, H)] = dict(K=K, verts=verts, norms=norms, rgba1=synth.rgba(rgb1), rgba2=synth.rgba(rgb2), d2=d2, P1=T1.astype(np.float32))
+        return cache[(W, H)]
+
+    return get
+
+
+def _init_synth(trk, inp, pose=None):
+    trk.initICPModel(inp["verts"], inp["norms"], 20.0, inp["P1"] if pose is None else pose)
+    trk.initRGBModel(inp["rgba1"])
+    trk.initICP(inp["d2"], 20.0)
+    trk.initRGB(inp["rgba2"])
+    trk.initFirstRGB(inp["rgba1"])
+    return trk
+
+
+class _Pyramids:
+    """Snapshot of an initialised oracle tracker's buffers; buffer() hands out copies, so no test can change what the next one reads."""
+
+    def __init__(self, trk, whichs):
+        self._b = {(w, l): trk.buffer(w, l) for w in whichs for l in range(3)}
+
+    def buffer(self, which, level):
+        return self._b[(which, level)].copy()
+
+
+@pytest.fixture(scope="module")
+def synth_pyramids(orc, synth_inputs):
+    """synth_pyramids(W, H): the oracle's pyramids of the synthetic pair at that size, taken once from a tracker that is then dropped."""
+    cache = {}
+
+    def get(W, H):
+        if (W, H) not in cache:
+            inp = synth_inputs(W, H)
+            K = inp["K"]
+            cache[(W, H)] = _Pyramids(_init_synth(orc.Odometry(W, H, K[2], K[3], K[0], K[1]), inp), (0, 1, 2, 3, 4, 5, 6, 7, 8, 12))
+        return cache[(W, H)]
+
+    return get
+
+
+@pytest.mark.parametrize("size", RAGGED_OP_SIZES, ids=lambda s: "%dx%d" % s)
+def test_odometry_pyramids_exact_ragged(dms, orc, synth_inputs, synth_pyramids, size):
+    W, H = size
+    inp = synth_inputs(W, H)
+    K = inp["K"]
+    o = synth_pyramids(W, H)
+    g = _init_synth(dms.RGBDOdometry(W, H, K[2], K[3], K[0], K[1]), inp)
+    for lvl in range(3):
+        for which in (0, 1, 2, 3):
+            assert helpers.planes_equal_where_valid(g.buffer(which, lvl), o.buffer(which, lvl)), (which, lvl)
+        for which in (4, 5):
+            assert helpers.nan_equal(g.buffer(which, lvl), o.buffer(which, lvl)), (which, lvl)
+        for which in (6, 7, 8, 12):
+            assert (g.buffer(which, lvl) == o.buffer(which, lvl)).all(), (which, lvl)
+
+
+@pytest.mark.parametrize("size", RAGGED_OP_SIZES, ids=lambda s: "%dx%d" % s)
+def test_icpStep_parity_ragged(dms, orc, synth_inputs, synth_pyramids, size):
+    W, H = size
+    inp = synth_inputs(W, H)
+    o = synth_pyramids(W, H)
+    # the model maps are in the global frame (pose of frame 10); the live frame is tracked from that pose
+    R = np.ascontiguousarray(inp["P1"][:3, :3])
+    t = np.ascontiguousarray(inp["P1"][:3, 3])
+    Rinv = np.ascontiguousarray(R.T)
+    for lvl in range(3):
+        cam = tuple(np.float32(v) / np.float32(1 << lvl) for v in inp["K"])
+        bufs = [o.buffer(w, lvl) for w in (0, 1, 2, 3)]
+        n = bufs[0].shape[1] * (bufs[0].shape[0] // 3)
+        Ao, bo, ro = orc.icpStep(R, t, bufs[0], bufs[1], Rinv, t, cam, bufs[2], bufs[3], 0.10, float(np.sin(np.radians(20.0))))
+        Ag, bg, rg = dms.ops.icpStep(R, t, bufs[0], bufs[1], Rinv, t, cam, bufs[2], bufs[3], 0.10, float(np.sin(np.radians(20.0))))
+        assert ro[1] > n // 2, "the pair must overlap (level %d): %r of %d" % (lvl, ro[1], n)
+        assert rg[1] == ro[1], "inlier count must be exact (level %d): %r vs %r" % (lvl, rg[1], ro[1])
+        _sum_close(Ag, Ao, what="A level %d" % lvl)
+        _sum_close(bg, bo, rtol=2e-3, what="b level %d" % lvl)
+        _sum_close(rg[0], ro[0], what="residual level %d" % lvl)
+        assert np.allclose(Ag, Ag.T)
+
+
+@pytest.mark.parametrize("size", RAGGED_OP_SIZES, ids=lambda s: "%dx%d" % s)
+def test_rgb_residual_and_step_parity_ragged(dms, orc, synth_inputs, synth_pyramids, size):
+    W, H = size
+    inp = synth_inputs(W, H)
+    o = synth_pyramids(W, H)
+    K = inp["K"]
+    sobelScale = 1.0 / 8.0
+    for lvl, minGrad in ((0, 5.0), (1, 3.0), (2, 1.0)):
+        cam = [np.float32(v) / np.float32(1 << lvl) for v in K]
+        nextImage, lastImage = o.buffer(7, lvl), o.buffer(6, lvl)
+        nextDepth, lastDepth = o.buffer(5, lvl), o.buffer(4, lvl)
+        dx, dy = orc.computeDerivativeImages(nextImage)
+        Km = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float64)
+        ang = 0.01
+        Rm = np.array([[np.cos(ang), 0, np.sin(ang)], [0, 1, 0], [-np.sin(ang), 0, np.cos(ang)]])
+        krkinv = (Km @ Rm @ np.linalg.inv(Km)).astype(np.float32)
+        kt = (Km @ np.array([0.004, -0.002, 0.003])).astype(np.float32)
+        minScale = float(minGrad ** 2 / sobelScale ** 2)
+        co, so, no = orc.computeRgbResidual(minScale, dx, dy, lastDepth, nextDepth, lastImage, nextImage, 0.07, kt, krkinv)
+        cg, sg, ng = dms.ops.computeRgbResidual(minScale, dx, dy, lastDepth, nextDepth, lastImage, nextImage, 0.07, kt, krkinv)
+        assert (sg, ng) == (so, no), "count / sum of diff^2 are integers: exact (level %d)" % lvl
+        cgh = cg.download()
+        for f in ("zero_x", "zero_y", "one_x", "one_y", "diff", "valid"):
+            assert (cgh[f] == co[f]).all(), (f, lvl)
+        assert no > 0, lvl
+        cloud = orc.projectToPointCloud(lastDepth, K, lvl)
+        for sigma in (float(np.sqrt(no)), -1.0):
+            Ao, bo = orc.rgbStep(co, sigma, cloud, float(cam[0]), float(cam[1]), dx, dy, sobelScale)
+            Ag, bg = dms.ops.rgbStep(co, sigma, cloud, float(cam[0]), float(cam[1]), dx, dy, sobelScale)
+            _sum_close(Ag, Ao, what="rgb A level %d" % lvl)
+            _sum_close(bg, bo, rtol=2e-3, what="rgb b level %d" % lvl)
+
+
+@pytest.mark.parametrize("size", RAGGED_OP_SIZES, ids=lambda s: "%dx%d" % s)
+def test_so3Step_parity_ragged(dms, orc, synth_inputs, synth_pyramids, size):
+    W, H = size
+    inp = synth_inputs(W, H)
+    o = synth_pyramids(W, H)
+    for lvl in range(3):
+        K = [float(np.float32(v) / np.float32(1 << lvl)) for v in inp["K"]]
+        Km = np.array([[K[0], 0, K[2]], [0, K[1], K[3]], [0, 0, 1]], np.float64)
+        last, nxt = o.buffer(8, lvl), o.buffer(7, lvl)
+        for ang in (0.0, 0.02):
+            Rm = np.array([[np.cos(ang), 0, np.sin(ang)], [0, 1, 0], [-np.sin(ang), 0, np.cos(ang)]])
+            ib = (Km @ Rm @ np.linalg.inv(Km)).astype(np.float32)
+            ki = np.linalg.inv(Km).astype(np.float32)
+            kr = (Km @ Rm).astype(np.float32)
+            Ao, bo, ro = orc.so3Step(last, nxt, ib, ki, kr)
+            Ag, bg, rg = dms.ops.so3Step(last, nxt, ib, ki, kr)
+            assert ro[1] > 0, lvl
+            assert rg[1] == ro[1], lvl
+            _sum_close(Ag, Ao, what="so3 A level %d" % lvl)
+            _sum_close(bg, bo, rtol=2e-3, what="so3 b level %d" % lvl)
+            _sum_close(rg[0], ro[0], what="so3 residual level %d" % lvl)
+
+
 # ------------------------------------------------------------------------------------------
 # whole tracker: device-resident Gauss-Newton vs the oracle's host loop
 # ------------------------------------------------------------------------------------------
@@ -667,3 +835,169 @@ def test_resident_timeout_repeats_the_call_launch_per_phase(dms, orc, gputest_pa
     tg, Rg, rg = g.getIncrementalTransformation(t0, R0, **cfg)
     to, Ro, ro = o.getIncrementalTransformation(t0, R0, **cfg)
     helpers.assert_pose_identical(tg, Rg, to, Ro, what="next call")
+
+
+# ------------------------------------------------------------------------------------------
+# whole tracker calls at ragged and tiny sizes: the same bits where the last block is partial
+# ------------------------------------------------------------------------------------------
+# Every bit-exact tracker test above runs at 640x480, where each level is a whole number of blocks (307200 = 200 * 512 * 3,
+# 76800 = 150 * 512): the `idx < N` masks, the lanes past the end, `py = i / cols` with odd cols and grids with more threads than
+# pixels are barely executed there.  The sizes below are the smallest that reach each class; the classes are ASSERTED, in
+# `persistent` mode, through dms_odometry_get_level_shape, so that a change of the launch heuristic cannot silently remove the coverage.
+#
+# A resident level of P pixels per thread gives block b the pixels [b * 512 * P, (b + 1) * 512 * P) (gn_level_body: idx[p] =
+# (blockIdx.x * P + p) * kPB + tid), so the last block owns [(blocks - 1) * 512 * P, N).  The launch-per-phase kernels hand out
+# chunks of 512 pixels (icp_accumulate: base + p * 256 + tid, p < 2); the partial one is [floor((N - 1) / 512) * 512, N).
+# createNMap leaves the last row and the last column invalid at every level, so a tail that lies inside the last row adds nothing
+# to any sum and tests nothing: `tail` / `chunk` list the levels whose partial last block / chunk holds at least 64 pixels with a
+# valid live vertex and normal - counted in the test from the oracle's buffers 0 and 1.  Measured (valid pixels of the partial
+# last block, level 0 / 1 / 2; "-" = inside the last row): 164x127: 182 / - / 200; 333x251: 305 / 103 / -; 601x451: 113 / 127 / 264;
+# 648x486: 934 / 71 / -; 701x601: 758 / 201 / -; 77x47: - / 315 / 180 (one block).  (164x126 and 646x486 were candidates: their
+# level-0 tails hold 19 and 0 valid pixels.)
+#   shape: (pixels per thread, blocks) of levels 0, 1, 2 on a whole MI355X (256 compute units; target 160, reserve 56)
+RAGGED_TRACK = {
+    (16, 16): dict(shape=[(1, 1), (1, 1), (1, 1)], tail=(), chunk=()),  # the minimum: 256 / 64 / 16 pixels in one 512-thread block
+    (77, 47): dict(shape=[(1, 8), (1, 2), (1, 1)], tail=(1,), chunk=(1,)),  # odd in both directions, odd halves: 38x23, 19x11
+    (164, 127): dict(shape=[(1, 41), (1, 11), (1, 3)], tail=(0, 2), chunk=(0, 2)),  # P = 1
+    (333, 251): dict(shape=[(2, 82), (1, 41), (1, 11)], tail=(0, 1), chunk=(1,)),  # P = 2
+    (601, 451): dict(shape=[(3, 177), (1, 132), (1, 33)], tail=(0, 1, 2), chunk=(1, 2)),  # P = 3
+    (648, 486): dict(shape=[(4, 154), (1, 154), (1, 39)], tail=(0, 1), chunk=(1,)),  # P = 4
+    (701, 601): dict(shape=[(5, 165), (2, 103), (1, 52)], tail=(0, 1), chunk=()),  # P = 5 (and P = 2 at level 1)
+}
+RAGGED_ALL_CONFIGS = [(77, 47), (333, 251)]  # all five CONFIGS here; C3_full, C2_icp_fast and rgb_only at the other sizes
+RAGGED_SECOND_CALL = (333, 251)  # a second call on the same handles (the SO3 image swap) at this size
+RAGGED_CASES = [(s, n) for s in RAGGED_TRACK for n in CONFIGS if n in ("C3_full", "C2_icp_fast", "rgb_only") or s in RAGGED_ALL_CONFIGS]
+kTrackBlock = 512  # kPB of csrc/track.hip, and kBlock * kPix of its launch-per-phase kernels
+
+
+def _valid_live(o, lvl):
+    """flat mask of the pixels of level `lvl` whose live vertex AND normal are valid (what an ICP term needs on the live side)"""
+    v, n = o.buffer(0, lvl), o.buffer(1, lvl)
+    h = v.shape[0] // 3
+    return (~np.isnan(v[:h]) & ~np.isnan(n[:h])).reshape(-1)
+
+
+@pytest.fixture(scope="module")
+def ragged_oracle(orc, synth_inputs):
+    """ragged_oracle(size, name): the oracle's side of a ragged case, computed once (on a tracker of its own, dropped afterwards) and
+    shared by the three execution modes: the live validity masks of the three levels, and per call (pose, result, nextImage /
+    lastNextImage pyramids after it)."""
+    cache = {}
+
+    def get(size, name):
+        if (size, name) not in cache:
+            W, H = size
+            inp = synth_inputs(W, H)
+            K = inp["K"]
+            o = _init_synth(orc.Odometry(W, H, K[2], K[3], K[0], K[1]), inp)
+            valid = [_valid_live(o, l) for l in range(3)]
+            calls = []
+            for _ in range(2 if (size == RAGGED_SECOND_CALL and name == "C3_full") else 1):
+                to, Ro, ro = o.getIncrementalTransformation(inp["P1"][:3, 3], inp["P1"][:3, :3], **CONFIGS[name])
+                calls.append((to, Ro, ro, [(o.buffer(7, l), o.buffer(8, l)) for l in range(3)]))
+            cache[(size, name)] = (valid, calls)
+        return cache[(size, name)]
+
+    return get
+
+
+@pytest.mark.parametrize("track_mode", ["persistent", "launches", "coarse"], indirect=True)
+@pytest.mark.parametrize("size,name", RAGGED_CASES, ids=["%dx%d-%s" % (s[0], s[1], n) for s, n in RAGGED_CASES])
+def test_track_bits_at_ragged_and_tiny_sizes(dms, orc, synth_inputs, ragged_oracle, size, name, track_mode):
+    """Whole tracker calls on a noise-free synthetic pair at sizes whose levels end in a partial block (or are smaller than one),
+    one size per pixels-per-thread variant of the resident level kernel: pose, counts, errors, the 6x6 system, iteration counts
+    and repeated reductions equal the oracle's bit for bit in the three execution modes, and no call fell back."""
+    W, H = size
+    spec = RAGGED_TRACK[size]
+    inp = synth_inputs(W, H)
+    K = inp["K"]
+    valid, calls = ragged_oracle(size, name)
+    assert not np.array_equal(inp["P1"], np.eye(4, dtype=np.float32))  # (every call here starts from a non-identity prior)
+    g = _init_synth(dms.RGBDOdometry(W, H, K[2], K[3], K[0], K[1]), inp)
+    if track_mode == "coarse":
+        g.set_profiling(True)  # (launch counts by kernel name: which launches the mode really took)
+    for call, (to, Ro, ro, images) in enumerate(calls):
+        what = "%dx%d %s %s call %d" % (W, H, name, track_mode, call)
+        tg, Rg, rg = g.getIncrementalTransformation(inp["P1"][:3, 3], inp["P1"][:3, :3], **CONFIGS[name])
+        helpers.assert_pose_identical(tg, Rg, to, Ro, what=what)
+        _assert_results_identical(rg, ro, g, what)
+        resident, cap, fell_back = g.getMode()
+        assert not fell_back, what
+        assert resident == (track_mode != "launches"), what
+        if track_mode == "coarse":
+            # SO3 + level 2 + level 1 share one launch only in a call that runs all three: C3_full.  There k_track_coarse must have
+            # been taken - level 2 on level 1's grid, whole blocks past its end - and nothing else but level 0; for the other
+            # configurations the mode is `persistent` again, and that is asserted too.
+            fused = name == "C3_full"
+            assert g.kernel_time("track_coarse")[1] == (call + 1 if fused else 0), what
+            assert g.kernel_time("gn_level0")[1] == call + 1, what
+            if fused:
+                assert g.kernel_time("so3_level")[1] == g.kernel_time("gn_level2")[1] == g.kernel_time("gn_level1")[1] == 0, what
+                assert g.levelShape(2)[1] < g.levelShape(1)[1] or size == (16, 16), what
+        for lvl in range(3):
+            assert (g.buffer(7, lvl) == images[lvl][0]).all(), (what, "nextImage", lvl)
+            assert (g.buffer(8, lvl) == images[lvl][1]).all(), (what, "lastNextImage", lvl)
+        # the classes this size is here for
+        for lvl in range(3):
+            n = (W >> lvl) * (H >> lvl)
+            assert valid[lvl].size == n
+            P, nb, res = g.levelShape(lvl)
+            if track_mode == "launches":
+                assert (nb, res) == (0, False), (what, lvl)
+            elif track_mode == "persistent":
+                assert cap == 256, "the shapes below are those of a whole MI355X (256 compute units), this device reports %d" % cap
+                assert (P, nb) == spec["shape"][lvl] and res, (what, lvl, P, nb)
+                assert n % (kTrackBlock * P) != 0, (what, lvl)  # no level of these sizes is a whole number of blocks
+                assert nb == (n + kTrackBlock * P - 1) // (kTrackBlock * P)
+                if lvl in spec["tail"]:
+                    first = (nb - 1) * kTrackBlock * P
+                    assert 0 < n - first < kTrackBlock * P and int(valid[lvl][first:].sum()) >= 64, (what, lvl, int(valid[lvl][first:].sum()))
+            if track_mode == "launches" and lvl in spec["chunk"]:
+                first = ((n - 1) // kTrackBlock) * kTrackBlock
+                assert 0 < n - first < kTrackBlock and int(valid[lvl][first:].sum()) >= 64, (what, lvl, int(valid[lvl][first:].sum()))
+    if size == (16, 16):
+        assert all(valid[l].size < kTrackBlock for l in range(3))  # every level has fewer pixels than one block has threads
+        if name == "rgb_only":  # too few pixels for the photometric term alone: the call ends in the 0.3 m jump rejection
+            assert ro.rejected_jump and rg.rejected_jump and rg.lastRGBCount == ro.lastRGBCount
+    else:
+        assert np.isfinite(tg).all() and np.isfinite(Rg).all()
+        if name in ("C2_icp_fast", "C3_full", "gputest"):
+            assert rg.lastICPCount > 0.85 * valid[0].sum()  # nearly every valid pixel contributes: the tails above are summed
+    g.close()
+
+
+def test_every_pixels_per_thread_variant_is_covered():
+    """The ragged sizes reach k_gn_level's five pixels-per-thread variants at level 0 (asserted per case through the accessor)."""
+    assert sorted(spec["shape"][0][0] for size, spec in RAGGED_TRACK.items() if 0 in spec["tail"]) == [1, 2, 3, 4, 5]
+
+
+@pytest.mark.parametrize("track_mode", ["persistent"], indirect=True)
+def test_retry_pool_exhausted_on_one_call_repeats_it_launch_per_phase(dms, orc, synth_inputs, track_mode):
+    """A resident launch has kArPool = 6 spare word sets for repeated reductions.  With the static exponents biased by -56 the
+    single level-0 launch of a C2_icp_fast call repeats 7: the whole grid leaves on the totals every block read (pool_used is
+    uniform), and the synchronous call runs again launch-per-phase - the oracle's bits and its 7 repeats, the handle still
+    resident, not fallen back, and the next call resident again.  Bias -30 (4 repeats) stays inside the pool."""
+    size = (164, 126)
+    W, H = size
+    inp = synth_inputs(W, H)
+    K = inp["K"]
+    for bias, repeats in ((-30, 4), (-56, 7)):
+        g = _init_synth(dms.RGBDOdometry(W, H, K[2], K[3], K[0], K[1]), inp)
+        o = _init_synth(orc.Odometry(W, H, K[2], K[3], K[0], K[1]), inp)
+        assert g.getMode()[0] and not g.getMode()[2]
+        for b, want in ((bias, repeats), (0, 0)):  # the biased call, then an unbiased one on the same handles
+            g.setExpBias(b)
+            o.setExpBias(b)
+            to, Ro, ro = o.getIncrementalTransformation(inp["P1"][:3, 3], inp["P1"][:3, :3], **CONFIGS["C2_icp_fast"])
+            assert ro.canon_retries == want, (b, ro.canon_retries)
+            tg, Rg, rg = g.getIncrementalTransformation(inp["P1"][:3, 3], inp["P1"][:3, :3], **CONFIGS["C2_icp_fast"])
+            what = "bias %d (after %d)" % (b, bias)
+            helpers.assert_pose_identical(tg, Rg, to, Ro, what=what)
+            _assert_results_identical(rg, ro, g, what)
+            assert g.canonRetries() == want, what
+            resident, _, fell_back = g.getMode()
+            assert resident and not fell_back, what
+            P, nb, res = g.levelShape(0)
+            # (a call that used up the pool reports the launch-per-phase repeat it ended with; every other one its resident level 0)
+            assert ((nb, res) == (0, False)) if want > 6 else ((P, nb, res) == (1, 41, True)), (what, P, nb, res)
+        g.close()
