@@ -42,7 +42,10 @@ int resize_nn(const dms_image2d* src, dms_image2d* dst, int elem, hipStream_t s)
 int model_initialise(dms_model* m, const dms_image2d* rgba, const dms_image2d* dm, const dms_image2d* dmf, const dms_camera* cam, int time,
                      int timeIdx, float maxDepth, hipStream_t s);
 int index_map(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, int time, int timeIdx, float maxDepth, int timeDelta,
-              unsigned long long* zbuf, dms_indexmap_out* out, int transposed, int zclean, hipStream_t s);
+              unsigned long long* zbuf, dms_indexmap_out* out, int transposed, int zclean, hipStream_t s,
+              unsigned long long* zbuf_also = nullptr);
+int index_project(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, int time, int timeIdx, float maxDepth, int timeDelta,
+                  unsigned long long* zbuf, int zclean, hipStream_t s);
 int clear_zbuf(unsigned long long* zbuf, int n, hipStream_t s);
 int untranspose(const void* src, void* dst, int cols, int rows, int elem, hipStream_t s);
 int splat_predict(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, float maxDepth, float confThreshold, int time,
@@ -57,6 +60,11 @@ int model_flush_pending(dms_model* m, hipStream_t s);
 int model_fuse(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_image2d* rgba, const dms_image2d* dr,
                const dms_image2d* drf, const dms_indexmap_out* im, const dms_camera* cam, float depthCutoff, float weighting,
                const float* weighting_dev, int transposed, hipStream_t s, int defer_update = 0);
+int model_fuse_zbuf(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_image2d* rgba, const dms_image2d* dr,
+                    const dms_image2d* drf, const unsigned long long* zbuf, const dms_camera* cam, float depthCutoff, float weighting,
+                    const float* weighting_dev, hipStream_t s, int defer_update = 0);
+int model_fuse_scratch(dms_model* m, float* slot_pos4, float* slot_col4, float* slot_nrm4, unsigned* slot_best, unsigned char* slot_flag,
+                       unsigned* winner, size_t winner_count, hipStream_t s);
 int model_clean(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_indexmap_out* im, const dms_image2d* depth_synth,
                 const dms_camera* cam, float confThreshold, const float* graph_host, int graph_nodes, int timeDelta, float maxDepth,
                 int isFern, int transposed, unsigned* count_out2, hipStream_t s);
@@ -353,6 +361,13 @@ struct dms_fusion {
   // second z-buffer: filled by the final prediction's project pass with the NEXT frame's tracking prediction (same map,
   // same pose unless the caller brings a prior), resolved at that frame's begin instead of projecting the map again
   unsigned long long* zbuf2 = nullptr;
+  // fused_associate: the z-buffer of a fusing frame's first index map, which k_fuse_associate_zbuf reads in place of that index
+  // map's images.  The association must not clear it (a neighbouring block reads the rim of a tile), so the frame's second index
+  // map empties it on the way (index_map's zbuf_also).  zbuf_assoc_dirty: set when the projection is enqueued, dropped when that
+  // clearing resolve is; a frame that finds it set (an error return in between) clears the buffer itself first.
+  unsigned long long* zbuf_assoc = nullptr;
+  bool zbuf_assoc_dirty = false;
+  bool zbuf_assoc_keep_dirty = false;  // test hook (dms_fusion_debug_keep_assoc_zbuf): the second index map leaves the buffer as it is
   unsigned* tickets = nullptr;  // 16 counters, 64 bytes apart (fused fill-in: non-black subsampled pixels of the tracking prediction); subsample masks at word 512
   bool fold_track_init = true;     // the tracker call's set-up as a block group of the model pyramid kernel (DMS_FOLD_TRACK_INIT=0: its own launch)
   bool dense_by_counters = false;  // this frame's denseEnough decision is taken from them by the model pyramid kernel
@@ -481,6 +496,7 @@ void layout(dms_fusion* f, Carve& c) {
   f->untr = c.take(N * 16);
   f->zbuf = (unsigned long long*)c.take(N * 8);
   f->zbuf2 = (unsigned long long*)c.take(N * 8);
+  f->zbuf_assoc = (unsigned long long*)c.take(N * 8);
   f->tickets = (unsigned*)c.take(2048 + 512 + 1024);  // + the subsample masks (128 words at word 512) + the thumbnail masks (256 words at word 640)
   f->state = (FrameState*)c.take(sizeof(FrameState));
   f->lazy_pose = (dms_pose_block*)c.take(sizeof(dms_pose_block));
@@ -751,6 +767,25 @@ int dms_model_fuse(dms_model* m, const dms_pose_block* pose, int time, int timeI
                    const float* weighting_dev, dms_stream s) {
   return model_fuse(m, pose, time, timeIdx, rgba, dr, drf, im, cam, depthCutoff, weighting, weighting_dev, 0, (hipStream_t)s);
 }
+int dms_index_project(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, int time, int timeIdx, float maxDepth, int timeDelta,
+                      unsigned long long* zbuf, dms_stream s) {
+  return index_project(m, pose, cam, time, timeIdx, maxDepth, timeDelta, zbuf, 0, (hipStream_t)s);
+}
+int dms_model_fuse_ex(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_image2d* rgba, const dms_image2d* dr,
+                      const dms_image2d* drf, const dms_indexmap_out* im, const unsigned long long* zbuf, const dms_camera* cam,
+                      float depthCutoff, float weighting, const float* weighting_dev, int defer_update, dms_stream s) {
+  DMS_REQUIRE((im != nullptr) != (zbuf != nullptr), "exactly one of the index map's images and its z-buffer");
+  if (im) return model_fuse(m, pose, time, timeIdx, rgba, dr, drf, im, cam, depthCutoff, weighting, weighting_dev, 0, (hipStream_t)s, defer_update);
+  return model_fuse_zbuf(m, pose, time, timeIdx, rgba, dr, drf, zbuf, cam, depthCutoff, weighting, weighting_dev, (hipStream_t)s, defer_update);
+}
+int dms_model_apply_pending(dms_model* m, dms_stream s) {
+  DMS_REQUIRE(m, "null argument");
+  return model_flush_pending(m, (hipStream_t)s);
+}
+int dms_model_fuse_scratch(dms_model* m, float* slot_pos4, float* slot_col4, float* slot_nrm4, unsigned int* slot_best,
+                           unsigned char* slot_flag, unsigned int* winner, size_t winner_count, dms_stream s) {
+  return model_fuse_scratch(m, slot_pos4, slot_col4, slot_nrm4, slot_best, slot_flag, winner, winner_count, (hipStream_t)s);
+}
 int dms_model_clean(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_indexmap_out* im,
                     const dms_image2d* depth_synth, const dms_camera* cam, float confThreshold, const float* graph_host, int graph_nodes,
                     int timeDelta, float maxDepth, int isFern, dms_stream s) {
@@ -801,6 +836,7 @@ void dms_fusion_default_params(dms_fusion_params* p, int width, int height, floa
   p->fused_fill_in = 1;
   p->hybrid_loops = 0;
   p->lazy_final_prediction = 1;
+  p->fused_associate = 1;
 }
 
 // far depth cut-offs raise the static exponents of the trackers' first reductions (canon.hpp): set at creation and whenever the
@@ -902,6 +938,7 @@ int dms_fusion_create(dms_fusion** out, const dms_fusion_params* p) {
   if (const char* hl = getenv("DMS_HOST_LAG")) f->host_lag = atoi(hl) == 3 ? 3 : 2;
   if (const char* lm = getenv("DMS_LATE_MAIN")) f->late_forced = atoi(lm) != 0 ? 1 : 0;
   if (const char* lz = getenv("DMS_LAZY_FINAL_PREDICTION")) f->p.lazy_final_prediction = atoi(lz) != 0 ? 1 : 0;  // A/B runs
+  if (const char* fa = getenv("DMS_FUSED_ASSOCIATE")) f->p.fused_associate = atoi(fa) != 0 ? 1 : 0;                // A/B runs
   if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_inputs, hipEventDisableTiming);
   if (e == hipSuccess) e = hipMemset(f->arena, 0, f->arena_bytes);
   if (e == hipSuccess) e = hipHostMalloc((void**)&f->h_state, 4 * sizeof(FrameState), hipHostMallocMapped);
@@ -939,6 +976,7 @@ int dms_fusion_create(dms_fusion** out, const dms_fusion_params* p) {
   hipLaunchKernelGGL(k_pose_set, dim3(1), dim3(64), 0, 0, f->state, I);
   (void)clear_zbuf(f->zbuf, p->width * p->height, 0);
   (void)clear_zbuf(f->zbuf2, p->width * p->height, 0);
+  (void)clear_zbuf(f->zbuf_assoc, p->width * p->height, 0);
   for (int l = 0; l < DMS_NUM_PYRS; ++l)  // the INACTIVE ("old") prediction is never rendered with loop closure off: no depth anywhere
     (void)hipMemsetD32((hipDeviceptr_t)f->kf_old_dmap[l].data, 0x7fffffff, (size_t)f->kf_old_dmap[l].rows * f->kf_old_dmap[l].cols);  // kept empty from here on: every resolve pass clears what it reads
   (void)hipDeviceSynchronize();
@@ -1480,23 +1518,41 @@ static int process_frame_end(dms_fusion* f, const float* graph_host, int graph_n
 
     if (!f->p.rgbOnly && f->tracking_ok && !f->lost && fuse_now) {  // fusion (ElasticFusion.cpp:506-564)
       if (!f->clusters.count(f->req_cluster) && (rc = cluster_initialise(f, f->req_cluster, s))) return rc;  // :508-515
+      // fused_associate: the first index map has one reader, the association, and the second one overwrites its images: it is
+      // projected only, into a z-buffer of its own, the association reads that (k_fuse_associate_zbuf), and the second index
+      // map's resolve pass hands it back empty.  Same bits in the slots, the winners and everything after them.
+      const bool fa = f->p.fused_associate != 0;
       {
         FTimer t(f, s, "index_map");
-        if ((rc = index_map(f->model, &f->state->cur, &f->cam, f->tick, f->p.timeIdx, f->p.maxDepthProcessed, timeDeltaEff, f->zbuf,
-                            &f->imap, 1, 1, s)))
-          return rc;
+        if (fa) {
+          const bool stale = f->zbuf_assoc_dirty;  // a frame that set it never reached its clearing resolve: clear here
+          f->zbuf_assoc_dirty = true;
+          rc = index_project(f->model, &f->state->cur, &f->cam, f->tick, f->p.timeIdx, f->p.maxDepthProcessed, timeDeltaEff, f->zbuf_assoc,
+                             stale ? 0 : 1, s);
+        } else {
+          rc = index_map(f->model, &f->state->cur, &f->cam, f->tick, f->p.timeIdx, f->p.maxDepthProcessed, timeDeltaEff, f->zbuf, &f->imap, 1,
+                         1, s);
+        }
+        if (rc) return rc;
       }
       {
         FTimer t(f, s, "fuse");
-        if ((rc = model_fuse(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->rgba, &f->depth_metric, &f->depth_metric_filtered,
-                             &f->imap, &f->cam, f->p.maxDepthProcessed, 1.f, &f->state->weighting, 1, s, 1)))  // (update pass: inside the next index map)
-          return rc;
+        // (update pass: inside the next index map)
+        if (fa)
+          rc = model_fuse_zbuf(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->rgba, &f->depth_metric, &f->depth_metric_filtered,
+                               f->zbuf_assoc, &f->cam, f->p.maxDepthProcessed, 1.f, &f->state->weighting, s, 1);
+        else
+          rc = model_fuse(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->rgba, &f->depth_metric, &f->depth_metric_filtered, &f->imap,
+                          &f->cam, f->p.maxDepthProcessed, 1.f, &f->state->weighting, 1, s, 1);
+        if (rc) return rc;
       }
       {
         FTimer t(f, s, "index_map");
+        const bool hand_back = fa && !f->zbuf_assoc_keep_dirty;
         if ((rc = index_map(f->model, &f->state->cur, &f->cam, f->tick, f->p.timeIdx, f->p.maxDepthProcessed, timeDeltaEff, f->zbuf,
-                            &f->imap, 1, 1, s)))
+                            &f->imap, 1, 1, s, hand_back ? f->zbuf_assoc : nullptr)))
           return rc;
+        if (hand_back) f->zbuf_assoc_dirty = false;
       }
       if (graph_nodes > 0) {
         // a deformation is a second pose update this frame: predict the depth again to decide whose
@@ -1878,6 +1934,12 @@ int dms_fusion_get_image(dms_fusion* f, int which, dms_image2d* view) {
     DMS_HIP(hipDeviceSynchronize());
     view->data = dst;
   }
+  return DMS_OK;
+}
+
+int dms_fusion_debug_keep_assoc_zbuf(dms_fusion* f, int on) {
+  DMS_REQUIRE(f, "null argument");
+  f->zbuf_assoc_keep_dirty = on != 0;
   return DMS_OK;
 }
 

@@ -70,27 +70,27 @@ __device__ __forceinline__ float angle_between(const f3& a, const f3& b) {  // d
   return det_acosf(dot3(a, b) / (length3(a) * length3(b)));
 }
 
-__global__ __launch_bounds__(256) void k_fuse_associate(FuseArgs a, float4* __restrict__ slot_pos, float4* __restrict__ slot_col,
-                                                        float4* __restrict__ slot_nrm, unsigned* __restrict__ slot_best,
-                                                        unsigned char* __restrict__ slot_flag, unsigned* __restrict__ winner, int slot_w) {
+// The measurement of candidate (i, j) (data.vert:76-115) and the texels of its association window: everything the association
+// needs from the live frame, nothing from the index map.  k_fuse_associate has every lane of a candidate's quad work it out;
+// k_fuse_associate_zbuf one lane per candidate, once, while the tile's texels are on their way, and hands it on through LDS
+// (a plain aggregate for that reason).
+struct FuseMeas {
+  int valid;  // the candidate has a slot
+  int ok;     // ... and a measurement (inside the image, the gates of data.vert:112-114 passed)
+  int sx, sy;
+  float x, y, zLocal;
+  f3 vPos, vNormLocal, nG;
+  float rad, conf, colour;
+  AxisTaps tapx, tapy;
+};
+__device__ __forceinline__ FuseMeas fuse_measure(const FuseArgs& a, int i, int j, int slot_w) {
   // candidate (i, j) -> pixel (2i + p, 2j + p), p = time % 2; slot = i * slot_h + j (column-major)
-  // Four lanes per candidate: lane `sub` of a quad evaluates the (up to four) taps of x slot `sub` of the association
-  // window, the quad then agrees on the winner by shuffles and its lane 0 writes the slot.  (One lane per candidate —
-  // 76 800 threads, 48 dependent-latency gathers each — left the kernel latency-bound at about one wave per SIMD: 15.8 us,
-  // of which the evaluation itself was 2.)  One 2 x 8 tile of candidates per wave, quads running down the column first:
-  // the column-major index maps and the row-major live images are both read in runs of 8 neighbouring candidates.
-  const int tiles_j = (a.slot_h + 7) >> 3;
-  const int t = xcd_block(blockIdx.x, gridDim.x, a.xcd) * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const int ti = t / tiles_j, tj = t - ti * tiles_j;
-  const int lane = threadIdx.x & 63, quad = lane >> 2, sub = lane & 3;
-  const int i = ti * 2 + (quad >> 3);
-  const int j = tj * 8 + (quad & 7);
-  if (i >= slot_w || j >= a.slot_h) return;
-  const int slot = i * a.slot_h + j;
+  FuseMeas m;
+  m.valid = i < slot_w && j < a.slot_h;
+  m.ok = 0;
   const int par = ((a.time % 2) + 2) % 2;
   const int px = 2 * i + par, py = 2 * j + par;
-  unsigned char flag = 0;
-  if (px < a.cols && py < a.rows) {
+  if (m.valid && px < a.cols && py < a.rows) {
     const float colsf = (float)a.cols, rowsf = (float)a.rows;
     const float tx = uv_coord(px, a.cols), ty = uv_coord(py, a.rows);
     const float x = tx * colsf, y = ty * rowsf;
@@ -111,98 +111,244 @@ __global__ __launch_bounds__(256) void k_fuse_associate(FuseArgs a, float4* __re
     ok = ok && !(weighting < 0.f);
     if (ok) {
       const float* P = a.pose->pose;
-      const f3 vPos = xform_point(P, vPosLocal);
       const f3 vPos_f = dv_vertex(a.drf, a.cols, sx, sy, x, y, a.cx, a.cy, a.icx, a.icy);
       const uchar4 c = a.rgba[(size_t)sy * a.cols + sx];
-      const f3 vNormLocal = dv_normal(a.drf, a.cols, a.rows, vPos_f, tx, ty, x, y, a.cx, a.cy, a.icx, a.icy);
-      const f3 nG = xform_dir(P, vNormLocal);
-      const float rad = surfel_radius(vPos_f.z, vNormLocal.z, a.icx, a.icy);
-      const float conf = surfel_confidence(x, y, a.cx, a.cy, weighting);
-
-      // 4×4-tap association window in the index map (data.vert:116-160)
-      int counter = 0;
-      unsigned best = 0u;
+      m.ok = 1;
+      m.sx = sx;
+      m.sy = sy;
+      m.x = x;
+      m.y = y;
+      m.zLocal = vPosLocal.z;
+      m.vPos = xform_point(P, vPosLocal);
+      m.colour = encode_color_bytes(c.x, c.y, c.z);
+      m.vNormLocal = dv_normal(a.drf, a.cols, a.rows, vPos_f, tx, ty, x, y, a.cx, a.cy, a.icx, a.icy);
+      m.nG = xform_dir(P, m.vNormLocal);
+      m.rad = surfel_radius(vPos_f.z, m.vNormLocal.z, a.icx, a.icy);
+      m.conf = surfel_confidence(x, y, a.cx, a.cy, weighting);
+      // the 4×4-tap association window in the index map (data.vert:116-134): repeated taps of one texel cannot change
+      // `best` (the distance test is strict) and `counter` only matters as > 0, so each distinct texel is visited once,
+      // in tap order
       const float scale = 1.0f;  // IndexMap::FACTOR
       const float indexXStep = (1.0f / (colsf * scale)) * 0.5f;
       const float indexYStep = (1.0f / (rowsf * scale)) * 0.5f;
-      float bestDist = 1000.f;
       const float windowMultiplier = 2.f;
-      const float xl = (x - a.cx) * a.icx;
-      const float yl = (y - a.cy) * a.icy;
-      const float lambda = sqrtf((xl * xl + yl * yl) + 1.f);
-      const f3 ray = mk3(xl, yl, 1.f);
-      const float ray_len = length3(ray);
       const float x_lo = tx - ((scale * indexXStep) * windowMultiplier), x_hi = tx + ((scale * indexXStep) * windowMultiplier);
       const float y_lo = ty - ((scale * indexYStep) * windowMultiplier), y_hi = ty + ((scale * indexYStep) * windowMultiplier);
-      // repeated taps of one texel cannot change `best` (the distance test is strict) and
-      // `counter` only matters as > 0, so each distinct texel is visited once, in tap order
-      const AxisTaps tx_ = axis_taps(x_lo, x_hi, indexXStep, colsf, a.cols);
-      const AxisTaps ty_ = axis_taps(y_lo, y_hi, indexYStep, rowsf, a.rows);
-      // Sequentially (data.vert:118-160) a tap is accepted when it passes the depth and normal tests and lies strictly closer
-      // to the ray than every tap accepted before it: the winner is the closest tap of those that pass the two tests, the
-      // earliest in tap order (x outer, y inner) among equals — which can be evaluated per tap and reduced.
-      const int txs_s = sub == 0 ? tx_.t0 : sub == 1 ? tx_.t1 : sub == 2 ? tx_.t2 : tx_.t3;
-      const int mxs_s = sub == 0 ? tx_.m0 : sub == 1 ? tx_.m1 : sub == 2 ? tx_.m2 : tx_.m3;
-      const int tys[4] = {ty_.t0, ty_.t1, ty_.t2, ty_.t3}, mys[4] = {ty_.m0, ty_.m1, ty_.m2, ty_.m3};
-      size_t q[4];
-      bool used[4];
-      unsigned cur[4];
-      float4 vcs[4], nrs[4];
+      m.tapx = axis_taps(x_lo, x_hi, indexXStep, colsf, a.cols);
+      m.tapy = axis_taps(y_lo, y_hi, indexYStep, rowsf, a.rows);
+    }
+  }
+  return m;
+}
+
+// Association of candidate (i, j), measured as `m`, by lane `sub` of its quad.  `tap(ux, uy, index, vertConf, normRad)` fetches one
+// index-map texel: from the images (ImageTaps, k_fuse_associate) or from the block's LDS tile (TileTaps, k_fuse_associate_zbuf).
+template <class Tap>
+__device__ __forceinline__ void fuse_associate_body(const FuseArgs& a, const Tap& tap, const FuseMeas& m, int i, int j, int sub,
+                                                    float4* __restrict__ slot_pos, float4* __restrict__ slot_col,
+                                                    float4* __restrict__ slot_nrm, unsigned* __restrict__ slot_best,
+                                                    unsigned char* __restrict__ slot_flag, unsigned* __restrict__ winner) {
+  if (!m.valid) return;
+  const int slot = i * a.slot_h + j;
+  unsigned char flag = 0;
+  if (m.ok) {
+    const float x = m.x, y = m.y, zLocal = m.zLocal;
+    const int sx = m.sx, sy = m.sy;
+    const f3 vNormLocal = m.vNormLocal;
+
+    // the evaluation of the window (data.vert:135-160)
+    int counter = 0;
+    unsigned best = 0u;
+    float bestDist = 1000.f;
+    const float xl = (x - a.cx) * a.icx;
+    const float yl = (y - a.cy) * a.icy;
+    const float lambda = sqrtf((xl * xl + yl * yl) + 1.f);
+    const f3 ray = mk3(xl, yl, 1.f);
+    const float ray_len = length3(ray);
+    const AxisTaps tx_ = m.tapx, ty_ = m.tapy;
+    // Sequentially (data.vert:118-160) a tap is accepted when it passes the depth and normal tests and lies strictly closer
+    // to the ray than every tap accepted before it: the winner is the closest tap of those that pass the two tests, the
+    // earliest in tap order (x outer, y inner) among equals — which can be evaluated per tap and reduced.
+    const int txs_s = sub == 0 ? tx_.t0 : sub == 1 ? tx_.t1 : sub == 2 ? tx_.t2 : tx_.t3;
+    const int mxs_s = sub == 0 ? tx_.m0 : sub == 1 ? tx_.m1 : sub == 2 ? tx_.m2 : tx_.m3;
+    const int tys[4] = {ty_.t0, ty_.t1, ty_.t2, ty_.t3}, mys[4] = {ty_.m0, ty_.m1, ty_.m2, ty_.m3};
+    bool used[4];
+    unsigned cur[4];
+    float4 vcs[4], nrs[4];
 #pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        const bool u = mxs_s != 0 && mys[jj] != 0;
-        const int ux = u ? txs_s : 0, uy = u ? tys[jj] : 0;
-        used[jj] = u;
-        q[jj] = a.transposed ? (size_t)ux * a.rows + uy : (size_t)uy * a.cols + ux;
-      }
+    for (int jj = 0; jj < 4; ++jj) {  // (an unused tap fetches the candidate's own texel: always a legal one, and a near one)
+      const bool u = mxs_s != 0 && mys[jj] != 0;
+      used[jj] = u;
+      tap(u ? txs_s : sx, u ? tys[jj] : sy, cur[jj], vcs[jj], nrs[jj]);
+    }
+    int order = 64;  // tap order of this lane's winner (sub * 4 + jj); 64 = none
 #pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        cur[jj] = a.index[q[jj]];
-        vcs[jj] = a.vertConf[q[jj]];
-        nrs[jj] = a.normRad[q[jj]];
-      }
-      int order = 64;  // tap order of this lane's winner (sub * 4 + jj); 64 = none
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        const unsigned current = cur[jj];
-        if (used[jj] && current > 0u) {
-          const float4 vc = vcs[jj];
-          if (fabsf((vc.z * lambda) - (vPosLocal.z * lambda)) < 0.05f) {
-            const float dist = length3(cross3(ray, mk3(vc.x, vc.y, vc.z))) / ray_len;
-            const float4 nr = nrs[jj];
-            if (dist < bestDist && (fabsf(nr.z) < 0.75f || fabsf(angle_between(mk3(nr.x, nr.y, nr.z), vNormLocal)) < 0.5f)) {
-              counter++;
-              bestDist = dist;
-              best = current;
-              order = sub * 4 + jj;
-            }
+    for (int jj = 0; jj < 4; ++jj) {
+      const unsigned current = cur[jj];
+      if (used[jj] && current > 0u) {
+        const float4 vc = vcs[jj];
+        if (fabsf((vc.z * lambda) - (zLocal * lambda)) < 0.05f) {
+          const float dist = length3(cross3(ray, mk3(vc.x, vc.y, vc.z))) / ray_len;
+          const float4 nr = nrs[jj];
+          if (dist < bestDist && (fabsf(nr.z) < 0.75f || fabsf(angle_between(mk3(nr.x, nr.y, nr.z), vNormLocal)) < 0.5f)) {
+            counter++;
+            bestDist = dist;
+            best = current;
+            order = sub * 4 + jj;
           }
         }
       }
-      // the quad's winner: smaller distance, then earlier tap (a lane without a winner holds distance 1000, order 64)
+    }
+    // the quad's winner: smaller distance, then earlier tap (a lane without a winner holds distance 1000, order 64)
 #pragma unroll
-      for (int m = 1; m < 4; m <<= 1) {
-        const float od = __shfl_xor(bestDist, m, 64);
-        const int oo = __shfl_xor(order, m, 64);
-        const unsigned ob = __shfl_xor(best, m, 64);
-        counter += __shfl_xor(counter, m, 64);
-        if (od < bestDist || (od == bestDist && oo < order)) {
-          bestDist = od;
-          order = oo;
-          best = ob;
-        }
+    for (int xm = 1; xm < 4; xm <<= 1) {
+      const float od = __shfl_xor(bestDist, xm, 64);
+      const int oo = __shfl_xor(order, xm, 64);
+      const unsigned ob = __shfl_xor(best, xm, 64);
+      counter += __shfl_xor(counter, xm, 64);
+      if (od < bestDist || (od == bestDist && oo < order)) {
+        bestDist = od;
+        order = oo;
+        best = ob;
       }
-      flag = counter > 0 ? 1 : 2;
-      if (sub == 0) {
-        slot_pos[slot] = make_float4(vPos.x, vPos.y, vPos.z, conf);
-        slot_col[slot] = make_float4(encode_color_bytes(c.x, c.y, c.z), 0.f, a.timef, flag == 1 ? -1.f : -2.f);
-        slot_nrm[slot] = make_float4(nG.x, nG.y, nG.z, rad);
-        slot_best[slot] = best;
-        if (flag == 1) atomicMin(winner + best, (unsigned)slot);
-      }
+    }
+    flag = counter > 0 ? 1 : 2;
+    if (sub == 0) {
+      slot_pos[slot] = make_float4(m.vPos.x, m.vPos.y, m.vPos.z, m.conf);
+      slot_col[slot] = make_float4(m.colour, 0.f, a.timef, flag == 1 ? -1.f : -2.f);
+      slot_nrm[slot] = make_float4(m.nG.x, m.nG.y, m.nG.z, m.rad);
+      slot_best[slot] = best;
+      if (flag == 1) atomicMin(winner + best, (unsigned)slot);
     }
   }
   if (sub == 0) slot_flag[slot] = flag;
+}
+
+// the index map as images (index_map), row- or column-major
+struct ImageTaps {
+  const unsigned* index;
+  const float4 *vertConf, *normRad;
+  int cols, rows, transposed;
+  __device__ __forceinline__ void operator()(int ux, int uy, unsigned& id, float4& vc, float4& nr) const {
+    const size_t q = transposed ? (size_t)ux * rows + uy : (size_t)uy * cols + ux;
+    id = index[q];
+    vc = vertConf[q];
+    nr = normRad[q];
+  }
+};
+
+__global__ __launch_bounds__(256) void k_fuse_associate(FuseArgs a, float4* __restrict__ slot_pos, float4* __restrict__ slot_col,
+                                                        float4* __restrict__ slot_nrm, unsigned* __restrict__ slot_best,
+                                                        unsigned char* __restrict__ slot_flag, unsigned* __restrict__ winner, int slot_w) {
+  // Four lanes per candidate: lane `sub` of a quad evaluates the (up to four) taps of x slot `sub` of the association
+  // window, the quad then agrees on the winner by shuffles and its lane 0 writes the slot.  (One lane per candidate —
+  // 76 800 threads, 48 dependent-latency gathers each — left the kernel latency-bound at about one wave per SIMD: 15.8 us,
+  // of which the evaluation itself was 2.)  One 2 x 8 tile of candidates per wave, quads running down the column first:
+  // the column-major index maps and the row-major live images are both read in runs of 8 neighbouring candidates.
+  const int tiles_j = (a.slot_h + 7) >> 3;
+  const int t = xcd_block(blockIdx.x, gridDim.x, a.xcd) * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int ti = t / tiles_j, tj = t - ti * tiles_j;
+  const int lane = threadIdx.x & 63, quad = lane >> 2, sub = lane & 3;
+  const ImageTaps tap = {a.index, a.vertConf, a.normRad, a.cols, a.rows, a.transposed};
+  const int i = ti * 2 + (quad >> 3), j = tj * 8 + (quad & 7);
+  fuse_associate_body(a, tap, fuse_measure(a, i, j, slot_w), i, j, sub, slot_pos, slot_col, slot_nrm, slot_best, slot_flag, winner);
+}
+
+// The association straight from the z-buffer of the first index map (index_project): nobody else reads that index map (the second
+// one overwrites all four images two launches later), so its images are never written.  A block owns kTileI x kTileJ candidates =
+// (2 kTileI) x (2 kTileJ) pixels.  Its first two waves measure the candidates, one lane each (fuse_measure: the live images only);
+// the other six resolve every texel the windows of those candidates can reach into LDS (resolve_texel, the texel k_index_resolve
+// would have stored); after the barrier the candidates associate from LDS, four lanes each as in k_fuse_associate.
+// A candidate sits on every other pixel and its window reaches one texel to either side (axis_taps: taps at -1, -1/2, 0, +1/2
+// texels around the pixel centre), so the tile is (2 kTileI + 1) x (2 kTileJ + 1) = 17 x 33 = 561 texels for 512 pixels: 1.10
+// resolves per pixel.  That reach is not assumed: a tap outside the tile (fp32 rounding in axis_taps is the only way there) is
+// resolved from the z-buffer on the spot, by the same function, so the result is the same bits whatever the reach.
+// Against index map + k_fuse_associate: no 52 B per pixel written, no colorTime gathers, 32 B gathered per texel once instead
+// of 36 B per tap sixteen times per candidate, and the measurement (the larger part of k_fuse_associate's instructions) once
+// per candidate instead of once per lane.
+// The z-buffer is only read: a neighbouring block needs the cells of the rim too.  Column-major z-buffer only.
+constexpr int kTileI = 8, kTileJ = 16;
+constexpr int kTileW = 2 * kTileI + 1, kTileH = 2 * kTileJ + 1, kTileN = kTileW * kTileH;
+constexpr int kTileCand = kTileI * kTileJ;                // 128 candidates: waves 0 - 1 measure
+constexpr int kTileThreads = kTileCand * 4;               // 512
+constexpr int kTileResolvers = kTileThreads - kTileCand;  // 384 threads resolve the 561 texels
+
+struct TileTaps {
+  const unsigned* s_id;  // LDS, texel (x0 + lx, y0 + ly) at lx * kTileH + ly
+  const float4 *s_vc, *s_nr;
+  int x0, y0;
+  // outside the tile
+  const unsigned long long* zbuf;
+  const float* Tinv;
+  SurfelPlanes sp;
+  size_t cap;
+  int rows, timeIdx;
+  __device__ __forceinline__ void operator()(int ux, int uy, unsigned& id, float4& vc, float4& nr) const {
+    const int lx = ux - x0, ly = uy - y0;
+    if ((unsigned)lx < (unsigned)kTileW && (unsigned)ly < (unsigned)kTileH) {
+      const int q = lx * kTileH + ly;
+      id = s_id[q];
+      vc = s_vc[q];
+      nr = s_nr[q];
+    } else {
+      float4 ct;
+      resolve_texel<false>(zbuf[(size_t)ux * rows + uy], Tinv, sp, cap, timeIdx, id, vc, ct, nr);
+    }
+  }
+};
+
+__global__ __launch_bounds__(kTileThreads) void k_fuse_associate_zbuf(FuseArgs a, const unsigned long long* __restrict__ zbuf, SurfelPlanes sp,
+                                                                      size_t cap, float4* __restrict__ slot_pos, float4* __restrict__ slot_col,
+                                                                      float4* __restrict__ slot_nrm, unsigned* __restrict__ slot_best,
+                                                                      unsigned char* __restrict__ slot_flag, unsigned* __restrict__ winner,
+                                                                      int slot_w) {
+  __shared__ unsigned s_id[kTileN];
+  __shared__ float4 s_vc[kTileN], s_nr[kTileN];
+  __shared__ FuseMeas s_m[kTileCand];  // candidate (ci, cj) of the tile at ci * kTileJ + cj
+  const int tiles_j = (a.slot_h + kTileJ - 1) / kTileJ;
+  const int b = xcd_block(blockIdx.x, gridDim.x, a.xcd);
+  const int bi = b / tiles_j, bj = b - bi * tiles_j;
+  const int par = ((a.time % 2) + 2) % 2;
+  const int x0 = 2 * bi * kTileI + par - 1, y0 = 2 * bj * kTileJ + par - 1;  // the tile's first texel (may lie outside the image)
+  const float* Tinv = a.pose->t_inv;
+  if (threadIdx.x < kTileCand) {
+    // neighbouring lanes take neighbouring candidates of a row: the live images are row-major
+    const int ci = threadIdx.x % kTileI, cj = threadIdx.x / kTileI;
+    s_m[ci * kTileJ + cj] = fuse_measure(a, bi * kTileI + ci, bj * kTileJ + cj, slot_w);
+  } else {
+    // both rounds' cells, then both rounds' surfels, so the two gather chains overlap
+    constexpr int kRounds = (kTileN + kTileResolvers - 1) / kTileResolvers;
+    const int t = threadIdx.x - kTileCand;
+    unsigned long long key[kRounds];
+    bool in[kRounds];
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+      const int q = r * kTileResolvers + t;
+      const int lx = q / kTileH, ly = q - lx * kTileH;
+      const int ux = x0 + lx, uy = y0 + ly;
+      in[r] = q < kTileN && ux >= 0 && uy >= 0 && ux < a.cols && uy < a.rows;  // (outside the image: no tap goes there, CLAMP_TO_EDGE)
+      key[r] = in[r] ? zbuf[(size_t)ux * a.rows + uy] : kZClear;
+    }
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+      if (!in[r]) continue;
+      const int q = r * kTileResolvers + t;
+      unsigned id;
+      float4 vc, ct, nr;
+      resolve_texel<false>(key[r], Tinv, sp, cap, a.timeIdx, id, vc, ct, nr);
+      s_id[q] = id;
+      s_vc[q] = vc;
+      s_nr[q] = nr;
+    }
+  }
+  __syncthreads();
+  // as in k_fuse_associate: four lanes per candidate, one 2 x 8 tile of candidates per wave, quads running down the column first
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, quad = lane >> 2, sub = lane & 3;
+  constexpr int kWavesJ = kTileJ / 8;
+  const int ci = (w / kWavesJ) * 2 + (quad >> 3), cj = (w % kWavesJ) * 8 + (quad & 7);
+  const FuseMeas m = s_m[ci * kTileJ + cj];
+  const TileTaps tap = {s_id, s_vc, s_nr, x0, y0, zbuf, Tinv, sp, cap, a.rows, a.timeIdx};
+  fuse_associate_body(a, tap, m, bi * kTileI + ci, bj * kTileJ + cj, sub, slot_pos, slot_col, slot_nrm, slot_best, slot_flag, winner);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -659,16 +805,18 @@ static bool dense_img(const dms_image2d& im, size_t elem, int w, int h) {
   return im.data && im.cols == w && im.rows == h && im.pitch == (size_t)w * elem;
 }
 
-int model_fuse(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_image2d* rgba, const dms_image2d* dr,
-               const dms_image2d* drf, const dms_indexmap_out* im, const dms_camera* cam, float depthCutoff, float weighting,
-               const float* weighting_dev, int transposed, hipStream_t s, int defer_update) {
-  DMS_REQUIRE(m && pose && rgba && dr && drf && im && cam, "null argument");
+// im: the index map as images (k_fuse_associate).  zbuf (im null): the column-major z-buffer index_project filled from the map as it is
+// now, at this pose (k_fuse_associate_zbuf); it is left as it was found.
+static int model_fuse_impl(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_image2d* rgba, const dms_image2d* dr,
+                           const dms_image2d* drf, const dms_indexmap_out* im, const unsigned long long* zbuf, const dms_camera* cam,
+                           float depthCutoff, float weighting, const float* weighting_dev, int transposed, hipStream_t s, int defer_update) {
+  DMS_REQUIRE(m && pose && rgba && dr && drf && (im || zbuf) && cam, "null argument");
   DMS_REQUIRE(!m->pending_update, "a deferred update pass is still pending (index_map applies it)");
   DMS_REQUIRE(timeIdx >= 0 && timeIdx < DMS_MAX_SENSORS, "timeIdx out of range");
   if (m->live_planes < timeIdx + 1) m->live_planes = timeIdx + 1;  // (the update pass stamps times[timeIdx])
   const int W = m->width, H = m->height;
-  DMS_REQUIRE(dense_img(*rgba, 4, W, H) && dense_img(*dr, 4, W, H) && dense_img(*drf, 4, W, H) && dense_img(im->index, 4, W, H) &&
-                  dense_img(im->vertConf, 16, W, H) && dense_img(im->normRad, 16, W, H),
+  DMS_REQUIRE(dense_img(*rgba, 4, W, H) && dense_img(*dr, 4, W, H) && dense_img(*drf, 4, W, H), "dense W×H images required");
+  DMS_REQUIRE(!im || (dense_img(im->index, 4, W, H) && dense_img(im->vertConf, 16, W, H) && dense_img(im->normRad, 16, W, H)),
               "dense W×H images required");
   FuseArgs a;
   a.xcd = xcd_remap_enabled();
@@ -676,9 +824,9 @@ int model_fuse(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, 
   a.rgba = (const uchar4*)rgba->data;
   a.dr = (const float*)dr->data;
   a.drf = (const float*)drf->data;
-  a.index = (const unsigned*)im->index.data;
-  a.vertConf = (const float4*)im->vertConf.data;
-  a.normRad = (const float4*)im->normRad.data;
+  a.index = im ? (const unsigned*)im->index.data : nullptr;
+  a.vertConf = im ? (const float4*)im->vertConf.data : nullptr;
+  a.normRad = im ? (const float4*)im->normRad.data : nullptr;
   a.cols = W;
   a.rows = H;
   a.slot_h = m->slot_h;
@@ -694,9 +842,15 @@ int model_fuse(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, 
   a.timeIdx = timeIdx;
   a.transposed = transposed ? 1 : 0;
   const int slot_w = (W + 1) / 2;
-  const int tiles = ((m->slot_h + 7) / 8) * ((slot_w + 1) / 2);  // 2 x 8 candidates per wave, four lanes each
-  dim3 b(256), g((tiles + 3) / 4);
-  hipLaunchKernelGGL(k_fuse_associate, g, b, 0, s, a, m->slot_pos, m->slot_col, m->slot_nrm, m->slot_best, m->slot_flag, m->winner, slot_w);
+  if (im) {
+    const int tiles = ((m->slot_h + 7) / 8) * ((slot_w + 1) / 2);  // 2 x 8 candidates per wave, four lanes each
+    dim3 b(256), g((tiles + 3) / 4);
+    hipLaunchKernelGGL(k_fuse_associate, g, b, 0, s, a, m->slot_pos, m->slot_col, m->slot_nrm, m->slot_best, m->slot_flag, m->winner, slot_w);
+  } else {
+    const int tiles = ((m->slot_h + kTileJ - 1) / kTileJ) * ((slot_w + kTileI - 1) / kTileI);
+    hipLaunchKernelGGL(k_fuse_associate_zbuf, dim3(tiles), dim3(kTileThreads), 0, s, a, zbuf, m->buf[m->cur], m->cap, m->slot_pos, m->slot_col,
+                       m->slot_nrm, m->slot_best, m->slot_flag, m->winner, slot_w);
+  }
   DMS_CHECK_LAUNCH();
   if (defer_update) {  // the caller's next index_map applies the winners while it projects: one pass and one launch less
     m->pending_update = true;
@@ -708,6 +862,36 @@ int model_fuse(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, 
     DMS_CHECK_LAUNCH();
   }
   m->version += 1;
+  return DMS_OK;
+}
+
+int model_fuse(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_image2d* rgba, const dms_image2d* dr,
+               const dms_image2d* drf, const dms_indexmap_out* im, const dms_camera* cam, float depthCutoff, float weighting,
+               const float* weighting_dev, int transposed, hipStream_t s, int defer_update) {
+  DMS_REQUIRE(im, "null argument");
+  return model_fuse_impl(m, pose, time, timeIdx, rgba, dr, drf, im, nullptr, cam, depthCutoff, weighting, weighting_dev, transposed, s,
+                         defer_update);
+}
+
+int model_fuse_zbuf(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_image2d* rgba, const dms_image2d* dr,
+                    const dms_image2d* drf, const unsigned long long* zbuf, const dms_camera* cam, float depthCutoff, float weighting,
+                    const float* weighting_dev, hipStream_t s, int defer_update) {
+  DMS_REQUIRE(zbuf, "null argument");
+  return model_fuse_impl(m, pose, time, timeIdx, rgba, dr, drf, nullptr, zbuf, cam, depthCutoff, weighting, weighting_dev, 1, s, defer_update);
+}
+
+// The association's outputs as the update pass and the clean will read them, for inspection (tests): any pointer may be null
+int model_fuse_scratch(dms_model* m, float* slot_pos4, float* slot_col4, float* slot_nrm4, unsigned* slot_best, unsigned char* slot_flag,
+                       unsigned* winner, size_t winner_count, hipStream_t s) {
+  DMS_REQUIRE(m && winner_count <= m->cap, "bad argument");
+  const size_t n = (size_t)m->slots;
+  if (slot_pos4) DMS_HIP(hipMemcpyAsync(slot_pos4, m->slot_pos, n * 16, hipMemcpyDeviceToHost, s));
+  if (slot_col4) DMS_HIP(hipMemcpyAsync(slot_col4, m->slot_col, n * 16, hipMemcpyDeviceToHost, s));
+  if (slot_nrm4) DMS_HIP(hipMemcpyAsync(slot_nrm4, m->slot_nrm, n * 16, hipMemcpyDeviceToHost, s));
+  if (slot_best) DMS_HIP(hipMemcpyAsync(slot_best, m->slot_best, n * 4, hipMemcpyDeviceToHost, s));
+  if (slot_flag) DMS_HIP(hipMemcpyAsync(slot_flag, m->slot_flag, n, hipMemcpyDeviceToHost, s));
+  if (winner && winner_count) DMS_HIP(hipMemcpyAsync(winner, m->winner, winner_count * 4, hipMemcpyDeviceToHost, s));
+  DMS_HIP(hipStreamSynchronize(s));
   return DMS_OK;
 }
 

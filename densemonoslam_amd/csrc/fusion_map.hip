@@ -452,7 +452,8 @@ __global__ __launch_bounds__(256) void k_index_project(ProjArgs a, SurfelPlanes 
 
 __global__ __launch_bounds__(256) void k_index_resolve(ProjArgs a, SurfelPlanes sp, size_t cap, unsigned long long* __restrict__ zbuf,
                                                        unsigned* __restrict__ index, float4* __restrict__ vertConf,
-                                                       float4* __restrict__ colorTime, float4* __restrict__ normRad, int clear_after) {
+                                                       float4* __restrict__ colorTime, float4* __restrict__ normRad, int clear_after,
+                                                       unsigned long long* __restrict__ zbuf_also) {
   // p runs over the storage order of the images (row-major, or column-major when a.transposed):
   // the z-buffer uses the same order, so reads and writes are coalesced either way
   const int n = a.cols * a.rows;
@@ -460,21 +461,15 @@ __global__ __launch_bounds__(256) void k_index_resolve(ProjArgs a, SurfelPlanes 
   for (int p = xcd_block(blockIdx.x, gridDim.x, a.xcd) * blockDim.x + threadIdx.x; p < n; p += blockDim.x * gridDim.x) {
     const unsigned long long key = zbuf[p];
     if (clear_after) zbuf[p] = kZClear;  // hand the z-buffer back empty: the next draw needs no clear launch
-    if ((unsigned)(key >> 32) >= 0xFFFFFFu) {  // cleared colour (glClearColor 0)
-      index[p] = 0;
-      vertConf[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-      colorTime[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-      normRad[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-      continue;
-    }
-    const unsigned i = (unsigned)(key & 0xFFFFFFFFull);
-    const float4 pc = sp.pos[i], cc = sp.col[i], nr = sp.nrm[i];
-    const f3 ph = xform_point(Tinv, mk3(pc.x, pc.y, pc.z));
-    const f3 nh = normalized3(xform_dir(Tinv, mk3(nr.x, nr.y, nr.z)));
-    index[p] = i;
-    vertConf[p] = make_float4(ph.x, ph.y, ph.z, pc.w);
-    colorTime[p] = make_float4(cc.x, cc.y, cc.z, sp.times[(size_t)a.timeIdx * cap + i]);
-    normRad[p] = make_float4(nh.x, nh.y, nh.z, nr.w);
+    // (the frame step: the z-buffer its fused association read without clearing, index_project / model_fuse_zbuf; null elsewhere)
+    if (zbuf_also) zbuf_also[p] = kZClear;
+    unsigned id;
+    float4 vc, ct, nr;
+    resolve_texel<true>(key, Tinv, sp, cap, a.timeIdx, id, vc, ct, nr);
+    index[p] = id;
+    vertConf[p] = vc;
+    colorTime[p] = ct;
+    normRad[p] = nr;
   }
 }
 
@@ -531,20 +526,9 @@ static void fill_proj(ProjArgs& a, const dms_model* m, const dms_pose_block* pos
   a.xcd = xcd_remap_enabled();
 }
 
-int index_map(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, int time, int timeIdx, float maxDepth, int timeDelta,
-              unsigned long long* zbuf, dms_indexmap_out* out, int transposed, int zclean, hipStream_t s) {
-  // zclean: the caller's z-buffer is empty on entry and must be handed back empty (the resolve pass
-  // clears what it reads), so a chain of draws needs no clear launches
-  DMS_REQUIRE(m && pose && cam && zbuf && out, "null argument");
-  DMS_REQUIRE(timeIdx >= 0 && timeIdx < DMS_MAX_SENSORS, "timeIdx out of range");
-  const int W = m->width, H = m->height;
-  DMS_REQUIRE(dense_img(out->index, 4, W, H) && dense_img(out->vertConf, 16, W, H) && dense_img(out->colorTime, 16, W, H) &&
-                  dense_img(out->normRad, 16, W, H),
-              "index-map targets must be dense W×H");
-  ProjArgs a;
-  fill_proj(a, m, pose, cam, maxDepth, time, timeIdx, timeDelta);
-  a.transposed = transposed ? 1 : 0;
-  const int n = W * H;
+// The projection half of index_map: zbuf (empty on entry when zclean) receives the depth-tested surfel ids
+static int index_project_launch(dms_model* m, const ProjArgs& a, unsigned long long* zbuf, int zclean, hipStream_t s) {
+  const int n = m->width * m->height;
   if (!zclean) {
     hipLaunchKernelGGL(k_clear_zbuf, dim3(min((n + 255) / 256, 2048)), dim3(256), 0, s, zbuf, n);
     DMS_CHECK_LAUNCH();
@@ -557,11 +541,44 @@ int index_map(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, i
     hipLaunchKernelGGL(k_index_project<false>, dim3(surfel_grid(m->count_upper)), dim3(256), 0, s, a, m->buf[m->cur], m->cap, m->d_count, zbuf, u);
   }
   DMS_CHECK_LAUNCH();
+  return DMS_OK;
+}
+
+int index_map(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, int time, int timeIdx, float maxDepth, int timeDelta,
+              unsigned long long* zbuf, dms_indexmap_out* out, int transposed, int zclean, hipStream_t s, unsigned long long* zbuf_also) {
+  // zclean: the caller's z-buffer is empty on entry and must be handed back empty (the resolve pass
+  // clears what it reads), so a chain of draws needs no clear launches.  zbuf_also: a second z-buffer the
+  // resolve pass empties on the way (same size; what index_project filled for model_fuse_zbuf), or null
+  DMS_REQUIRE(m && pose && cam && zbuf && out, "null argument");
+  DMS_REQUIRE(timeIdx >= 0 && timeIdx < DMS_MAX_SENSORS, "timeIdx out of range");
+  const int W = m->width, H = m->height;
+  DMS_REQUIRE(dense_img(out->index, 4, W, H) && dense_img(out->vertConf, 16, W, H) && dense_img(out->colorTime, 16, W, H) &&
+                  dense_img(out->normRad, 16, W, H),
+              "index-map targets must be dense W×H");
+  ProjArgs a;
+  fill_proj(a, m, pose, cam, maxDepth, time, timeIdx, timeDelta);
+  a.transposed = transposed ? 1 : 0;
+  const int n = W * H;
+  int rc = index_project_launch(m, a, zbuf, zclean, s);
+  if (rc) return rc;
   hipLaunchKernelGGL(k_index_resolve, dim3(min((n + 255) / 256, 2048)), dim3(256), 0, s, a, m->buf[m->cur], m->cap, zbuf,
                      (unsigned*)out->index.data, (float4*)out->vertConf.data, (float4*)out->colorTime.data, (float4*)out->normRad.data,
-                     zclean);
+                     zclean, zbuf_also);
   DMS_CHECK_LAUNCH();
   return DMS_OK;
+}
+
+// index_map without its resolve pass: the z-buffer alone, column-major (cell of pixel (x, y) at x * rows + y), for the one reader
+// that needs no images (fusion_fuse.hip model_fuse_zbuf).  Nobody clears it here: the caller hands it to a later index_map as
+// zbuf_also, or clears it itself.
+int index_project(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, int time, int timeIdx, float maxDepth, int timeDelta,
+                  unsigned long long* zbuf, int zclean, hipStream_t s) {
+  DMS_REQUIRE(m && pose && cam && zbuf, "null argument");
+  DMS_REQUIRE(timeIdx >= 0 && timeIdx < DMS_MAX_SENSORS, "timeIdx out of range");
+  ProjArgs a;
+  fill_proj(a, m, pose, cam, maxDepth, time, timeIdx, timeDelta);
+  a.transposed = 1;
+  return index_project_launch(m, a, zbuf, zclean, s);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -153,6 +153,30 @@ __device__ __forceinline__ f3 fb_normal(const float* depth, int cols, int rows, 
   return normalized3(cross3(del_x, del_y));
 }
 
+// G5: one index-map texel from its z-buffer cell (index_map.vert:41-67, index_map.frag:31-37).  The one definition of a texel:
+// k_index_resolve (fusion_map.hip) writes it into the four images, k_fuse_associate_zbuf (fusion_fuse.hip) into LDS, so the two
+// cannot differ in a bit.  A cleared cell gives index 0 and zeros (glClearColor 0); a winner with id 0 also gives index 0, which the
+// consumers' `current > 0u` test reads as "nothing".  Branch-free: a cleared cell reads surfel 0 and selects the zeros, so a caller
+// that resolves several texels has all their gathers in flight together.  COLOR: colorTime is wanted too.
+template <bool COLOR>
+__device__ __forceinline__ void resolve_texel(unsigned long long key, const float* Tinv, const SurfelPlanes& sp, size_t cap, int timeIdx,
+                                              unsigned& index, float4& vertConf, float4& colorTime, float4& normRad) {
+  const bool hit = (unsigned)(key >> 32) < 0xFFFFFFu;
+  const unsigned i = hit ? (unsigned)(key & 0xFFFFFFFFull) : 0u;
+  const float4 pc = sp.pos[i], nr = sp.nrm[i];
+  const f3 ph = xform_point(Tinv, mk3(pc.x, pc.y, pc.z));
+  const f3 nh = normalized3(xform_dir(Tinv, mk3(nr.x, nr.y, nr.z)));
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  index = i;
+  vertConf = hit ? make_float4(ph.x, ph.y, ph.z, pc.w) : zero;
+  normRad = hit ? make_float4(nh.x, nh.y, nh.z, nr.w) : zero;
+  if (COLOR) {
+    const float4 cc = sp.col[i];
+    const float vt = sp.times[(size_t)timeIdx * cap + i];
+    colorTime = hit ? make_float4(cc.x, cc.y, cc.z, vt) : zero;
+  }
+}
+
 // G8: update (update.vert:42-104) of surfel `id` by its winning measurement `slot`, in place
 __device__ __forceinline__ void fuse_update_apply(unsigned id, unsigned slot, const float4* __restrict__ slot_pos, const float4* __restrict__ slot_col,
                                                   const float4* __restrict__ slot_nrm, const SurfelPlanes& sp, size_t cap, int time, int timeIdx) {

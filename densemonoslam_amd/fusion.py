@@ -41,6 +41,7 @@ class FusionParams(C.Structure):
         ("nid_bins_depth", C.c_int), ("nid_pyramid_level", C.c_int),
         ("local_loop_closure", C.c_int), ("reloc", C.c_int), ("num_sensors", C.c_int), ("share_projection", C.c_int),
         ("fused_fill_in", C.c_int), ("hybrid_loops", C.c_int), ("lazy_final_prediction", C.c_int),
+        ("fused_associate", C.c_int),
     ]
 
 
@@ -79,6 +80,11 @@ lib.dms_index_map.argtypes = [_P, _P, _K, _I, _I, _F, _I, _P, C.POINTER(IndexMap
 lib.dms_splat_predict.argtypes = [_P, _P, _K, _F, _F, _I, _I, _I, _I, _I, _P, C.POINTER(PredictOut), _P]
 lib.dms_splat_depth.argtypes = [_P, _P, _K, _F, _F, _I, _I, _I, _I, _P, _I2, _P]
 lib.dms_model_fuse.argtypes = [_P, _P, _I, _I, _I2, _I2, _I2, C.POINTER(IndexMapOut), _K, _F, _F, _P, _P]
+lib.dms_index_project.argtypes = [_P, _P, _K, _I, _I, _F, _I, _P, _P]
+lib.dms_model_fuse_ex.argtypes = [_P, _P, _I, _I, _I2, _I2, _I2, C.POINTER(IndexMapOut), _P, _K, _F, _F, _P, _I, _P]
+lib.dms_model_apply_pending.argtypes = [_P, _P]
+lib.dms_model_fuse_scratch.argtypes = [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]
+lib.dms_fusion_debug_keep_assoc_zbuf.argtypes = [_P, _I]
 lib.dms_model_clean.argtypes = [_P, _P, _I, _I, C.POINTER(IndexMapOut), _I2, _K, _F, C.POINTER(C.c_float), _I, _I, _F, _I, _P]
 lib.dms_fill_in.argtypes = [C.POINTER(PredictOut), _I2, _I2, _K, _I, _I, C.POINTER(PredictOut), _P]
 lib.dms_resize_nn.argtypes = [_I2, _I2, _I, _P]
@@ -347,6 +353,37 @@ class GlobalModel:
         k = _cam(K)
         check(lib.dms_model_fuse(self.h, pose.ptr, time, timeIdx, c.ref, dm.ref, dmf.ref, C.byref(indexmap.c), C.byref(k), depthCutoff,
                                  weighting, None, None), "dms_model_fuse")
+
+    def projectIndices(self, pose, time, timeIdx, K, depthCutoff, timeDelta):
+        """The index map's z-buffer alone (column-major, in self.zbuf): what fuse(zbuf=True) associates from."""
+        k = _cam(K)
+        check(lib.dms_index_project(self.h, pose.ptr, C.byref(k), time, timeIdx, depthCutoff, timeDelta, C.c_void_p(self.zbuf.ptr), None),
+              "dms_index_project")
+
+    def fuseEx(self, pose, time, timeIdx, rgba, depth_metric, depth_metric_filtered, indexmap, K, depthCutoff, weighting, defer_update=False):
+        """fuse() from the index map's images (indexmap) or, with indexmap None, from the z-buffer projectIndices left in self.zbuf.
+        defer_update: the association only; applyPending() runs the update pass."""
+        c, dm, dmf = _img(rgba, np.uint8), _img(depth_metric, np.float32), _img(depth_metric_filtered, np.float32)
+        k = _cam(K)
+        im = C.byref(indexmap.c) if indexmap is not None else None
+        zb = None if indexmap is not None else C.c_void_p(self.zbuf.ptr)
+        check(lib.dms_model_fuse_ex(self.h, pose.ptr, time, timeIdx, c.ref, dm.ref, dmf.ref, im, zb, C.byref(k), depthCutoff, weighting, None,
+                                    int(bool(defer_update)), None), "dms_model_fuse_ex")
+
+    def applyPending(self):
+        check(lib.dms_model_apply_pending(self.h, None), "dms_model_apply_pending")
+
+    def fuseScratch(self, winners):
+        """What the last association left: dict of slot_pos / slot_col / slot_nrm (n x 4 float32), slot_best (uint32), slot_flag
+        (uint8) over the (W+1)//2 x (H+1)//2 candidate slots (column-major) and the first `winners` entries of the winner array."""
+        n = ((self.width + 1) // 2) * ((self.height + 1) // 2)
+        o = {"slot_pos": np.zeros((n, 4), np.float32), "slot_col": np.zeros((n, 4), np.float32), "slot_nrm": np.zeros((n, 4), np.float32),
+             "slot_best": np.zeros(n, np.uint32), "slot_flag": np.zeros(n, np.uint8), "winner": np.zeros(max(int(winners), 1), np.uint32)}
+        check(lib.dms_model_fuse_scratch(self.h, *[o[k].ctypes.data_as(C.c_void_p) for k in
+                                                   ("slot_pos", "slot_col", "slot_nrm", "slot_best", "slot_flag", "winner")],
+                                         int(winners), None), "dms_model_fuse_scratch")
+        o["winner"] = o["winner"][:int(winners)]
+        return o
 
     def clean(self, pose, time, timeIdx, indexmap, K, confThreshold, timeDelta, maxDepth, graph=None, depth_synth=None, isFern=False):
         k = _cam(K)

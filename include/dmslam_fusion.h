@@ -110,6 +110,11 @@ int dms_pose_block_set(dms_pose_block* dev, const float* pose16_host, dms_stream
 int dms_index_map(dms_model* m, const dms_pose_block* pose_dev, const dms_camera* cam, int time, int timeIdx,
                   float maxDepth, int timeDelta, unsigned long long* zbuf, dms_indexmap_out* out, dms_stream s);
 
+/* The projection half of dms_index_map: the depth-tested surfel ids in zbuf (W*H u64, cleared first), column-major (pixel (x, y)
+ * at x * H + y), and no images.  For dms_model_fuse_ex, which resolves the texels it needs itself. */
+int dms_index_project(dms_model* m, const dms_pose_block* pose_dev, const dms_camera* cam, int time, int timeIdx,
+                      float maxDepth, int timeDelta, unsigned long long* zbuf, dms_stream s);
+
 /* splat prediction targets (reference combined / old framebuffers, IndexMap.cpp:59-99) */
 typedef struct dms_predict_out {
   dms_image2d image;  /* rgba8  */
@@ -134,6 +139,20 @@ int dms_model_fuse(dms_model* m, const dms_pose_block* pose_dev, int time, int t
                    const dms_image2d* depth_metric, const dms_image2d* depth_metric_filtered,
                    const dms_indexmap_out* indexmap, const dms_camera* cam, float depthCutoff, float weighting,
                    const float* weighting_dev, dms_stream s);
+/* dms_model_fuse from either form of the index map: its images (`indexmap`, zbuf NULL: dms_model_fuse itself) or the z-buffer of
+ * dms_index_project (`zbuf`, indexmap NULL), rendered from the map as it is now at this pose; the z-buffer is only read.  Same bits.
+ * defer_update: stop after the association (G7); the update pass (G8) runs in dms_model_apply_pending, or inside the next
+ * dms_index_map / dms_index_project of this map.  Until then the map must not be read or changed otherwise. */
+int dms_model_fuse_ex(dms_model* m, const dms_pose_block* pose_dev, int time, int timeIdx, const dms_image2d* rgba,
+                      const dms_image2d* depth_metric, const dms_image2d* depth_metric_filtered,
+                      const dms_indexmap_out* indexmap, const unsigned long long* zbuf, const dms_camera* cam, float depthCutoff,
+                      float weighting, const float* weighting_dev, int defer_update, dms_stream s);
+int dms_model_apply_pending(dms_model* m, dms_stream s);
+/* Inspection (tests): what the last association left for the update pass and the clean - per candidate slot ((W+1)/2 x (H+1)/2,
+ * column-major) the three float4 planes, the associated surfel and the flag (0 none, 1 merge, 2 new), and the first winner_count
+ * entries of the per-surfel winner array (0xFFFFFFFF = none).  Host pointers, any may be NULL; syncs. */
+int dms_model_fuse_scratch(dms_model* m, float* slot_pos4, float* slot_col4, float* slot_nrm4, unsigned int* slot_best,
+                           unsigned char* slot_flag, unsigned int* winner, size_t winner_count, dms_stream s);
 
 /* G9 copy_unstable.{vert,geom} (GlobalModel::clean, GlobalModel.cpp:696-853).
  * graph: host array of 16 floats / node (Deformation.cpp:192-201), may be NULL / 0 nodes.
@@ -247,6 +266,13 @@ typedef struct dms_fusion_params {
    * Poses, results and the map are the same bits either way.  0: every frame renders its final prediction.
    * DMS_LAZY_FINAL_PREDICTION=0 / 1 in the environment overrides the field (A/B runs). */
   int lazy_final_prediction;
+  /* 1 (default): a fusing frame does not render its first index map (ElasticFusion.cpp:518) as images.  Its only reader is the
+   * association of the fuse, and the frame's second index map (:541) overwrites all four images before anything else can look: the
+   * map is projected into a z-buffer of the context's own and the association resolves the texels it needs from there
+   * (k_fuse_associate_zbuf), one launch and the four W x H image writes less.  The second index map hands that z-buffer back empty.
+   * Poses, results, the map and every image a caller can ask for are the same bits either way.  0: index map, then fuse, as
+   * dms_index_map + dms_model_fuse.  DMS_FUSED_ASSOCIATE=0 / 1 in the environment overrides the field (A/B runs). */
+  int fused_associate;
 } dms_fusion_params;
 
 void dms_fusion_default_params(dms_fusion_params* p, int width, int height, float fx, float fy, float cx, float cy);
@@ -321,6 +347,9 @@ int dms_fusion_process_frame_end(dms_fusion* f, const float* graph_host, int gra
  * been asked for); deferred = frames that skipped theirs so far; materialised = skipped predictions rendered on demand; stale = those
  * of them that found a map changed since the frame.  Any pointer may be NULL. */
 int dms_fusion_get_lazy_stats(dms_fusion* f, int* eager, long* deferred, long* materialised, long* stale);
+/* Test hook for fused_associate: on = the frame's second index map does not hand the association's z-buffer back empty, so the next
+ * fusing frame finds it in use and clears it itself - the path an error return between a frame's two index maps leaves behind. */
+int dms_fusion_debug_keep_assoc_zbuf(dms_fusion* f, int on);
 
 /* ORB-triggered global loop closure, device half (the block `if (hybrid_loops && orbTcwOld && orbTcwNew)` of
  * ElasticFusion::processFrame, ElasticFusion.cpp:292-350).  dms_fusion_set_orb_loop arms the NEXT
