@@ -17,6 +17,7 @@
 
 #include "../../include/dmslam_ferns.h"
 #include "internal.hpp"
+#include "host_util.hpp"
 #include "smallmath.hpp"
 #include "surfel.hpp"
 
@@ -551,8 +552,6 @@ struct dms_ferns {
 
 namespace {
 
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
 // After an asynchronous add has been enqueued on `s`: remember what mirror() must wait for, and tighten the host's bound of
 // the frame count from the newest {sequence, stored} pair the decide kernels have written into mapped memory (a rejected
 // frame no longer widens every later search by one frame's worth of blocks until the next synchronisation).
@@ -817,18 +816,12 @@ int dms_ferns_create(dms_ferns** out, int num, int maxDepth_mm, float photoThres
   f->poses.assign((size_t)capacity * 16, 0.f);
   f->times.assign(capacity, 0);
   f->goods.assign(capacity, 0);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    off = up256(off);
-    const size_t at = off;
-    off += bytes;
-    return at;
-  };
-  const size_t o_tab = take(sizeof(FernTable)), o_codes = take((size_t)capacity * kFernPad), o_good = take((size_t)capacity * 4),
-               o_time = take((size_t)capacity * 4), o_blocks = take((size_t)capacity * f->block_bytes), o_cur = take(f->block_bytes),
-               o_cc = take(kFernPad), o_res = take(sizeof(FernHost)), o_n = take(64), o_pose = take((size_t)capacity * 64);
-  hipError_t e = hipMalloc((void**)&f->arena, up256(off));
-  if (e == hipSuccess) e = hipMemset(f->arena, 0, up256(off));
+  Carver carve;
+  const size_t o_tab = carve.reserve(sizeof(FernTable)), o_codes = carve.reserve((size_t)capacity * kFernPad), o_good = carve.reserve((size_t)capacity * 4),
+               o_time = carve.reserve((size_t)capacity * 4), o_blocks = carve.reserve((size_t)capacity * f->block_bytes), o_cur = carve.reserve(f->block_bytes),
+               o_cc = carve.reserve(kFernPad), o_res = carve.reserve(sizeof(FernHost)), o_n = carve.reserve(64), o_pose = carve.reserve((size_t)capacity * 64);
+  hipError_t e = hipMalloc((void**)&f->arena, up256(carve.off));
+  if (e == hipSuccess) e = hipMemset(f->arena, 0, up256(carve.off));
   if (e == hipSuccess) e = hipHostMalloc((void**)&f->h_res, sizeof(FernHost), hipHostMallocDefault);
   if (e == hipSuccess) e = hipHostMalloc((void**)&f->h_rgb, (size_t)f->tw * f->th * 4, hipHostMallocDefault);
   if (e == hipSuccess) e = hipHostMalloc((void**)&f->h_status, 64, hipHostMallocMapped);

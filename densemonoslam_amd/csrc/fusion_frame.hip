@@ -16,6 +16,8 @@
 
 #include "../../include/dmslam_render_cloud.h"
 #include "internal.hpp"
+#include "host_util.hpp"
+#include "late_frame.hpp"
 #include "smallmath.hpp"
 #include "surfel.hpp"
 #include "canon.hpp"
@@ -24,92 +26,7 @@
 #include "fill.hpp"
 #include "track_init.hpp"
 
-struct dms_odometry;
-
 namespace dms {
-// fusion_pre.hip
-int depth_bilateral(const dms_image2d* src, dms_image2d* dst, float maxD, hipStream_t s, int narrow_blocks = 0,
-                    const dms_image2d* metric_filtered = nullptr, const dms_image2d* depth_l0 = nullptr, const dms_image2d* vmap_l0 = nullptr,
-                    const dms_camera* cam_l0 = nullptr, float vmap_cutoff = 0.f);
-int depth_metric(const dms_image2d* src, dms_image2d* dst, float maxD, hipStream_t s);
-int fill_in(const dms_predict_out* ex, const dms_image2d* depth, const dms_image2d* rgba, const dms_camera* cam, int pass_geom,
-            int pass_rgb, dms_predict_out* out, hipStream_t s, const void* mirror_src = nullptr, void* mirror_dst = nullptr,
-            int mirror_bytes = 0, int* dense_flag = nullptr);
-int fill_args(const dms_predict_out* ex, const dms_image2d* depth, const dms_image2d* rgba, const dms_camera* cam, int pass_geom, int pass_rgb,
-              dms_predict_out* out, const void* mirror_src, void* mirror_dst, int mirror_bytes, int* dense_flag, FillArgs* res);
-int resize_nn(const dms_image2d* src, dms_image2d* dst, int elem, hipStream_t s);
-// fusion_map.hip
-int model_initialise(dms_model* m, const dms_image2d* rgba, const dms_image2d* dm, const dms_image2d* dmf, const dms_camera* cam, int time,
-                     int timeIdx, float maxDepth, hipStream_t s);
-int index_map(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, int time, int timeIdx, float maxDepth, int timeDelta,
-              unsigned long long* zbuf, dms_indexmap_out* out, int transposed, int zclean, hipStream_t s,
-              unsigned long long* zbuf_also = nullptr);
-int index_project(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, int time, int timeIdx, float maxDepth, int timeDelta,
-                  unsigned long long* zbuf, int zclean, hipStream_t s);
-int clear_zbuf(unsigned long long* zbuf, int n, hipStream_t s);
-int untranspose(const void* src, void* dst, int cols, int rows, int elem, hipStream_t s);
-int splat_predict(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, float maxDepth, float confThreshold, int time,
-                  int timeIdx, int maxTime, int timeDelta, int active, unsigned long long* zbuf, dms_predict_out* out,
-                  dms_image2d* depth_out, int zclean, hipStream_t s, const float* second_conf_time_maxtime = nullptr,
-                  unsigned long long* zbuf2 = nullptr, int resolve_only = 0, const FillArgs* fill = nullptr, const TrackInitArgs* init = nullptr);
-int splat_project_only(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, float maxDepth, float confThreshold, int time,
-                       int timeIdx, int maxTime, int timeDelta, int active, unsigned long long* zbuf, hipStream_t s, const ProjectRider* rider);
-int model_sample_graph(dms_model* m, int sampleRate, float* rows4_host, int max_rows, int* n_host, hipStream_t s);
-int model_flush_pending(dms_model* m, hipStream_t s);
-// fusion_fuse.hip
-int model_fuse(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_image2d* rgba, const dms_image2d* dr,
-               const dms_image2d* drf, const dms_indexmap_out* im, const dms_camera* cam, float depthCutoff, float weighting,
-               const float* weighting_dev, int transposed, hipStream_t s, int defer_update = 0);
-int model_fuse_zbuf(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_image2d* rgba, const dms_image2d* dr,
-                    const dms_image2d* drf, const unsigned long long* zbuf, const dms_camera* cam, float depthCutoff, float weighting,
-                    const float* weighting_dev, hipStream_t s, int defer_update = 0);
-int model_fuse_scratch(dms_model* m, float* slot_pos4, float* slot_col4, float* slot_nrm4, unsigned* slot_best, unsigned char* slot_flag,
-                       unsigned* winner, size_t winner_count, hipStream_t s);
-int model_clean(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_indexmap_out* im, const dms_image2d* depth_synth,
-                const dms_camera* cam, float confThreshold, const float* graph_host, int graph_nodes, int timeDelta, float maxDepth,
-                int isFern, int transposed, unsigned* count_out2, hipStream_t s);
-// track.hip
-struct FrameState;
-int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot, const float* prior_pose16_dev, int rgbOnly,
-                           float icpWeight, int pyramid, int fastOdom, int so3, int interMap, hipStream_t s, FrameState* frame,
-                           float weightMultiplier);
-int odometry_result_pose(dms_odometry* o, float* pose16_dev, hipStream_t s);
-int odometry_initICPModel_sel(dms_odometry* o, const float* vA, const float* nA, const float* vB, const float* nB, const int* flag_dev,
-                              const float* pose16_dev, hipStream_t s);
-int odometry_initRGBModel_sel(dms_odometry* o, const void* rgbaA, const void* rgbaB, const int* flag_dev, int force_b, void* rgba_tmp,
-                              hipStream_t s);
-struct TrackFold {  // the track call a model pyramid launch prepares (track.hip)
-  const float* prior_pose16;
-  int pyramid, fastOdom, so3, interMap;
-};
-int odometry_early_init_args(dms_odometry* o, const TrackFold* fold, TrackInitArgs* ti);
-int odometry_initModel_fused(dms_odometry* o, const void* vA, const void* nA, const void* iA, const void* vB, const void* nB,
-                             const void* iB, const int* flag_dev, int force_b_img, const float* pose16_dev, hipStream_t s,
-                             int defer_last_step = 0, unsigned* dense_cnt = nullptr, int dense_samples = 0, const TrackFold* fold = nullptr);
-int odometry_initLive_fused(dms_odometry* o, const void* verts, const void* norms, const void* rgba, const int* any_flag_dev,
-                            hipStream_t s);
-int odometry_enable_ring(dms_odometry* o);
-int odometry_free_cus(const dms_odometry* o);
-void odometry_set_early_exit(dms_odometry* o, int on);
-int odometry_next_buffers(dms_odometry* o, int level, dms_image2d* nextImage, dms_image2d* nextDepth);
-struct LoopState;
-int odometry_loop_candidate(dms_odometry* o, FrameState* frame, const dms_image2d* vertex, const dms_image2d* oldTime, float maxDepth,
-                            LoopState* out, float* cons, hipStream_t s);
-// nid.hip
-size_t nid_workspace_bytes(int num_bins);
-int computeNIDImg(const dms_image2d* img_kf, const dms_image2d* img_kf_old, const dms_image2d* dmap_kf, const dms_image2d* dmap_kf_old,
-                  const dms_image2d* img_curr, int num_bins, void* workspace, size_t workspace_bytes, float* nid_host, float* nid_dev,
-                  hipStream_t s);
-int computeNIDDepth(const dms_image2d* dmap_kf, const dms_image2d* dmap_kf_old, const dms_image2d* dmap_curr, int num_bins, float max_depth,
-                    void* workspace, size_t workspace_bytes, float* nid_host, float* nid_dev, hipStream_t s);
-void odometry_bind_live(dms_odometry* o, int k);
-void odometry_bind_lastnext(dms_odometry* o, int k);
-int odometry_initRGB_image(dms_odometry* o, const dms_image2d* rgba, hipStream_t s);
-int odometry_live_views(dms_odometry* o, dms_image2d* depth, dms_image2d* vmap, dms_image2d* nmap, dms_image2d* image, dms_image2d* dx,
-                        dms_image2d* dy, dms_image2d* gate, float* minScale, bool mark_derivatives);
-int liveLevelsFused(const dms_image2d* depth, const dms_image2d* vmap, const dms_image2d* nmap, const dms_image2d* image, const dms_image2d* dx,
-                    const dms_image2d* dy, const dms_image2d* gate, const dms_camera* cam0, float cutoff, const float* minScale, hipStream_t s);
-void odometry_alias_next_depth(dms_odometry* o);
 
 // RGB8 (3 B/px, as the reference uploads, ElasticFusion.cpp:111) -> RGBA8 texture
 __global__ void k_rgb_to_rgba(const unsigned char* __restrict__ rgb, uchar4* __restrict__ rgba, int n) {
@@ -256,11 +173,6 @@ __global__ void k_frame_end(FrameState* st, const unsigned* __restrict__ d_count
   st->surfels = d_count[0];
 }
 
-struct FKernelTime {
-  double ms = 0;
-  int launches = 0;
-};
-
 }  // namespace dms
 
 using namespace dms;
@@ -328,10 +240,8 @@ struct dms_fusion {
   // start of a frame (for frame t - 2) is its remaining slack; three frames in a row under 15 us switch the mode off for a while
   // (64 frames, doubling).  Forced on, the populated full step fell from 1 690 to 1 082 frames/s and two cameras from 3 150 to 2 815 -
   // both are cases the two rules exclude.  DMS_LATE_MAIN=0 / 1 forces it.
-  bool late_main = false;       // this frame
-  int late_forced = -1;         // DMS_LATE_MAIN
+  LateFrame late;               // (late_frame.hpp: the watch of rule (ii))
   int late_owner = -1;          // dms_fusion_allow_late_frame: the owner's word (-1: none - one live context decides)
-  int late_low = 0, late_cool = 0, late_backoff = 64;
   double host_wait_prep_ms = 0.0;
   int host_lag = 2;  // the host enqueues frame t once frame t - host_lag has completed (DMS_HOST_LAG = 2 | 3; 3 measured -2.4 %)
   bool inputs_armed = false;  // ev_inputs was recorded by dms_fusion_inputs_ready for the next frame
@@ -404,25 +314,10 @@ struct dms_fusion {
   bool map_initialised = false;
   int fused_last = 0;
   bool profiling = false;
-  std::map<std::string, FKernelTime> times;
-  std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
-  std::vector<hipEvent_t> pool;
+  StageClock clock;  // stage times while `profiling` (dms_fusion_get_kernel_time)
 };
 
 namespace {
-
-size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-struct Carve {
-  char* base = nullptr;
-  size_t off = 0;
-  void* take(size_t bytes) {
-    off = up256(off);
-    void* p = base ? base + off : nullptr;
-    off += bytes + 16;
-    return p;
-  }
-};
 
 dms_image2d mk_img(void* p, int rows, int cols, size_t elem) {
   dms_image2d i;
@@ -433,7 +328,7 @@ dms_image2d mk_img(void* p, int rows, int cols, size_t elem) {
   return i;
 }
 
-void layout(dms_fusion* f, Carve& c) {
+void layout(dms_fusion* f, Carver& c) {
   const int W = f->p.width, H = f->p.height;
   const size_t N = (size_t)W * H;
   for (int k = 0; k < 2; ++k) {
@@ -502,66 +397,38 @@ void layout(dms_fusion* f, Carve& c) {
   f->lazy_pose = (dms_pose_block*)c.take(sizeof(dms_pose_block));
 }
 
-struct FTimer {
-  dms_fusion* f;
-  hipStream_t s;
-  const char* name;
-  hipEvent_t a = nullptr, b = nullptr;
-  FTimer(dms_fusion* f_, hipStream_t s_, const char* n) : f(f_), s(s_), name(n) {
-    if (!f->profiling) return;
-    auto get = [&]() {
-      hipEvent_t e;
-      if (!f->pool.empty()) {
-        e = f->pool.back();
-        f->pool.pop_back();
-      } else {
-        (void)hipEventCreate(&e);
-      }
-      return e;
-    };
-    a = get();
-    b = get();
-    (void)hipEventRecord(a, s);
-  }
-  ~FTimer() {
-    if (!f->profiling) return;
-    (void)hipEventRecord(b, s);
-    f->pending.push_back({name, {a, b}});
-  }
-};
-
 void drain(dms_fusion* f) {
   // DMS_TIMELINE=1: print every stage's start / end relative to the first stage of the batch
   // (both streams share the clock) — shows whether the prep stream really overlaps the main one
   static const bool timeline = getenv("DMS_TIMELINE") != nullptr;
-  if (timeline && !f->pending.empty()) {
-    hipEvent_t base = f->pending.front().second.first;
-    for (auto& p : f->pending) {
+  if (timeline && !f->clock.pending.empty()) {
+    hipEvent_t base = f->clock.pending.front().start;
+    for (auto& p : f->clock.pending) {
       float a = 0.f, b = 0.f;
-      (void)hipEventElapsedTime(&a, base, p.second.first);
-      (void)hipEventElapsedTime(&b, base, p.second.second);
-      fprintf(stderr, "[timeline] %-14s %9.3f -> %9.3f ms\n", p.first.c_str(), a, b);
+      (void)hipEventElapsedTime(&a, base, p.start);
+      (void)hipEventElapsedTime(&b, base, p.stop);
+      fprintf(stderr, "[timeline] %-14s %9.3f -> %9.3f ms\n", p.name.c_str(), a, b);
     }
   }
-  for (auto& p : f->pending) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, p.second.first, p.second.second) == hipSuccess) {
-      FKernelTime& t = f->times[p.first];
-      t.ms += ms;
-      t.launches += 1;
-    }
-    f->pool.push_back(p.second.first);
-    f->pool.push_back(p.second.second);
-  }
-  f->pending.clear();
+  f->clock.drain();
 }
 
-// ElasticFusion::predict (ElasticFusion.cpp:688-746): ACTIVE splat + fill-in
-// mode 0: plain.  mode 1 (the frame's final prediction): the project pass also fills zbuf2 for the next frame's tracking
-// prediction (confidence 0.7, next tick).  mode 2 (that next frame's begin): resolve zbuf2 if it is still what this
+// ElasticFusion::predict (ElasticFusion.cpp:688-746): ACTIVE splat + fill-in, behind the three entry points below.
+// view: plain.  final (the frame's final prediction): the project pass also fills zbuf2 for the next frame's tracking
+// prediction (confidence 0.7, next tick).  tracking (that next frame's begin): resolve zbuf2 if it is still what this
 // prediction would render — nothing changed the map, the pose comes from the previous frame — else project as usual.
-int predict(dms_fusion* f, float confidence, hipStream_t s, void* state_mirror = nullptr, bool dense_test = false, int mode = 0,
-            bool have_prior = false, const TrackInitArgs* track_init = nullptr, bool* track_init_taken = nullptr, bool one_call = false) {
+enum class Predict { view, final, tracking };
+struct PredictOpts {
+  float confidence;
+  void* state_mirror = nullptr;               // final: the frame's pinned result slot, written by the last kernel
+  bool one_call = false;                      // final: the frame came through dms_fusion_process_frame
+  bool have_prior = false;                    // tracking: the caller brought a pose
+  const TrackInitArgs* track_init = nullptr;  // tracking: the tracker call's set-up, to ride on the resolve pass ...
+  bool* track_init_taken = nullptr;           // ... and whether it did
+};
+
+int predict_body(dms_fusion* f, hipStream_t s, Predict kind, const PredictOpts& o) {
+  const bool dense_test = kind == Predict::tracking;  // ElasticFusion.cpp:165-167
   int rc;
   f->lazy.pending = false;  // (whatever this call renders is newer than a prediction skipped earlier)
   FillArgs fa;
@@ -569,7 +436,7 @@ int predict(dms_fusion* f, float confidence, hipStream_t s, void* state_mirror =
   // passthrough = lost (geometry), lost || frameToFrameRGB (image) (ElasticFusion.cpp:704-712)
   // (the frame's last fill-in also copies the result block into its pinned host slot)
   if ((rc = fill_args(&f->pred, &f->depth_filtered, &f->rgba, &f->cam, f->lost ? 1 : 0, (f->lost || f->p.frameToFrameRGB) ? 1 : 0, &f->fill,
-                      state_mirror ? f->state : nullptr, state_mirror, (int)sizeof(FrameState), dense_test ? &f->state->fill_in : nullptr, &fa)))
+                      o.state_mirror ? f->state : nullptr, o.state_mirror, (int)sizeof(FrameState), dense_test ? &f->state->fill_in : nullptr, &fa)))
     return rc;
   // the denseEnough decision of a fused pass is taken by the tracker's model pyramid kernel from the counters filled here
   // (fill.hpp): only when that kernel follows, i.e. with hybrid tracking
@@ -581,7 +448,7 @@ int predict(dms_fusion* f, float confidence, hipStream_t s, void* state_mirror =
       fa.sample_mask = f->tickets + 512;
       f->dense_by_counters = true;
     }
-    if (mode == 1 && f->armed_now.block && f->thumb_masks_ok) {  // the frame's last kernel also writes the armed frame block
+    if (kind == Predict::final && f->armed_now.block && f->thumb_masks_ok) {  // the frame's last kernel also writes the armed frame block
       fa.thumb_block = f->armed_now.block;
       fa.thumb_mask = f->tickets + 640;
       fa.thumb_w = f->p.width / 8;
@@ -594,13 +461,13 @@ int predict(dms_fusion* f, float confidence, hipStream_t s, void* state_mirror =
     }
   }
   {
-    FTimer t(f, s, "predict");
+    StageTimer t(f->clock, s, "predict", f->profiling);
     const int W = f->p.width, H = f->p.height;
     bool done = false;
-    if (mode == 2 && f->pre_valid) {
-      if (!have_prior && f->pre_tick == f->tick && f->pre_version == f->model->version) {
-        if ((rc = splat_predict(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, confidence, f->tick, f->p.timeIdx, f->tick,
-                                f->p.timeDelta, 1, f->zbuf2, &f->pred, nullptr, 1, s, nullptr, nullptr, 1, fused, fused ? track_init : nullptr)))
+    if (kind == Predict::tracking && f->pre_valid) {
+      if (!o.have_prior && f->pre_tick == f->tick && f->pre_version == f->model->version) {
+        if ((rc = splat_predict(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, o.confidence, f->tick, f->p.timeIdx, f->tick,
+                                f->p.timeDelta, 1, f->zbuf2, &f->pred, nullptr, 1, s, nullptr, nullptr, 1, fused, fused ? o.track_init : nullptr)))
           return rc;
         done = true;
       } else if ((rc = clear_zbuf(f->zbuf2, W * H, s))) {  // stale: the resolve that would have cleaned it never runs
@@ -612,7 +479,7 @@ int predict(dms_fusion* f, float confidence, hipStream_t s, void* state_mirror =
       const int next_tick = f->lost ? f->tick : f->tick + 1;  // (the tick advances at the end of the frame unless the camera is lost)
       const float second[3] = {0.7f, (float)next_tick, (float)next_tick};
       // (a projection rendered ahead for this camera's next frame is stale by then when other cameras fuse into the same map: not rendered)
-      const bool dual = mode == 1 && f->p.share_projection && f->p.hybrid_tracking && f->model->sharers == 1;
+      const bool dual = kind == Predict::final && f->p.share_projection && f->p.hybrid_tracking && f->model->sharers == 1;
       if (dual && f->pre_valid && (rc = clear_zbuf(f->zbuf2, W * H, s))) return rc;  // (never consumed)
       // lazy_final_prediction: this prediction's images (f->pred, f->fill) are overwritten by the next frame's tracking prediction;
       // when nothing can read them before that, only that next prediction is projected.  Their readers, all in this file:
@@ -630,17 +497,17 @@ int predict(dms_fusion* f, float confidence, hipStream_t s, void* state_mirror =
       //     dms_fusion_apply_global_loop_* render the images anew (the record is dropped above);
       //   the result mirror (h_state): written by block 0 of the project launch below instead of the resolve's.
       // dms_fusion_arm_frame_block reads nothing: it makes the NEXT frame eager through armed_now.
-      const bool defer = dual && one_call && fused && state_mirror && f->p.lazy_final_prediction && !f->lazy_observed && !f->armed_now.block &&
+      const bool defer = dual && o.one_call && fused && o.state_mirror && f->p.lazy_final_prediction && !f->lazy_observed && !f->armed_now.block &&
                          !f->p.nid_keyframing && !f->p.local_loop_closure && !f->p.hybrid_loops && !f->lost && !f->cur_bootstrap;
       if (defer) {
-        const ProjectRider rider = {(const unsigned*)f->state, (unsigned*)state_mirror, (int)(sizeof(FrameState) / 4),
+        const ProjectRider rider = {(const unsigned*)f->state, (unsigned*)o.state_mirror, (int)(sizeof(FrameState) / 4),
                                     (const unsigned*)&f->state->cur, (unsigned*)f->lazy_pose, (int)(sizeof(dms_pose_block) / 4)};
         if ((rc = splat_project_only(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, second[0], next_tick, f->p.timeIdx, next_tick,
                                      f->p.timeDelta, 1, f->zbuf2, s, &rider)))
           return rc;
         dms_fusion::LazyRecord& r = f->lazy;
         r.pending = true;
-        r.confidence = confidence;
+        r.confidence = o.confidence;
         r.maxDepth = f->p.maxDepthProcessed;
         r.tick = f->tick;
         r.timeIdx = f->p.timeIdx;
@@ -653,9 +520,9 @@ int predict(dms_fusion* f, float confidence, hipStream_t s, void* state_mirror =
         r.version = f->model->version;
         r.stream = s;
         f->lazy_deferred += 1;
-      } else if ((rc = splat_predict(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, confidence, f->tick, f->p.timeIdx, f->tick,
+      } else if ((rc = splat_predict(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, o.confidence, f->tick, f->p.timeIdx, f->tick,
                               f->p.timeDelta, 1, f->zbuf, &f->pred, nullptr, 1, s, dual ? second : nullptr, dual ? f->zbuf2 : nullptr, 0,
-                              fused, fused ? track_init : nullptr)))
+                              fused, fused ? o.track_init : nullptr)))
         return rc;
       if (dual) {
         f->pre_valid = true;
@@ -664,14 +531,27 @@ int predict(dms_fusion* f, float confidence, hipStream_t s, void* state_mirror =
       }
     }
   }
-  if (track_init_taken) *track_init_taken = fused != nullptr && track_init && track_init->blocks > 0;
+  if (o.track_init_taken) *o.track_init_taken = fused != nullptr && o.track_init && o.track_init->blocks > 0;
   if (!fused) {
-    FTimer t(f, s, "fill_in");
+    StageTimer t(f->clock, s, "fill_in", f->profiling);
     if ((rc = fill_in(&f->pred, &f->depth_filtered, &f->rgba, &f->cam, f->lost ? 1 : 0, (f->lost || f->p.frameToFrameRGB) ? 1 : 0, &f->fill,
-                      s, state_mirror ? f->state : nullptr, state_mirror, (int)sizeof(FrameState), dense_test ? &f->state->fill_in : nullptr)))
+                      s, o.state_mirror ? f->state : nullptr, o.state_mirror, (int)sizeof(FrameState), dense_test ? &f->state->fill_in : nullptr)))
       return rc;
   }
   return DMS_OK;
+}
+
+// the current view at a given threshold ("GlobalPredict", the ORB loop block's restore, dms_fusion_predict, applyGlobalLoop)
+int predict_view(dms_fusion* f, float confidence, hipStream_t s) { return predict_body(f, s, Predict::view, PredictOpts{confidence}); }
+
+// a frame's tracking prediction (ElasticFusion.cpp:165: confidence 0.7) with the denseEnough test
+int predict_tracking(dms_fusion* f, hipStream_t s, bool have_prior, const TrackInitArgs* track_init, bool* track_init_taken) {
+  return predict_body(f, s, Predict::tracking, PredictOpts{0.7f, nullptr, false, have_prior, track_init, track_init_taken});
+}
+
+// finalPredict (ElasticFusion.cpp:586); its last kernel mirrors the result block into the pinned host slot
+int predict_final(dms_fusion* f, hipStream_t s, void* state_mirror, bool one_call) {
+  return predict_body(f, s, Predict::final, PredictOpts{f->p.confidence, state_mirror, one_call});
 }
 
 // The final prediction a deferred frame skipped (lazy_final_prediction), rendered now: the ordinary project + resolve + fill-in
@@ -693,7 +573,7 @@ int materialise_final_prediction(dms_fusion* f, hipStream_t consumer, bool consu
   FillArgs fa;
   if ((rc = fill_args(&f->pred, &r.depth_filtered, &r.rgba, &f->cam, r.pass_geom, r.pass_rgb, &f->fill, nullptr, nullptr, 0, nullptr, &fa))) return rc;
   {
-    FTimer t(f, r.stream, "predict");
+    StageTimer t(f->clock, r.stream, "predict", f->profiling);
     if ((rc = splat_predict(f->model, f->lazy_pose, &f->cam, r.maxDepth, r.confidence, r.tick, r.timeIdx, r.tick, r.timeDelta, 1, f->zbuf, &f->pred,
                             nullptr, 1, r.stream, nullptr, nullptr, 0, &fa, nullptr)))
       return rc;
@@ -714,7 +594,7 @@ int global_loop_device(dms_fusion* f, const float* orbTcwOld, const float* orbTc
   hipLaunchKernelGGL(k_pose_blocks2, dim3(1), dim3(64), 0, s, f->orb_pose, a, b);
   DMS_CHECK_LAUNCH();
   f->lazy.pending = false;  // (f->pred is rendered anew below)
-  FTimer t(f, s, "global_loop");
+  StageTimer t(f->clock, s, "global_loop", f->profiling);
   const int act = active_new ? 1 : 0;
   // predict(context, rf) with currPose = the ACTIVE pose (:294-296 / :1158-1160): only its vertex map is consumed
   if ((rc = splat_predict(f->model, f->orb_pose + act, &f->cam, f->p.maxDepthProcessed, f->p.confidence, f->tick, f->p.timeIdx, f->tick,
@@ -896,7 +776,8 @@ int dms_fusion_create(dms_fusion** out, const dms_fusion_params* p) {
     delete f;
     return rc;
   }
-  Carve sz;
+  Carver sz;
+  sz.pad = 16;
   layout(f, sz);
   f->arena_bytes = up256(sz.off);
   hipError_t e = hipMalloc((void**)&f->arena, f->arena_bytes);
@@ -936,7 +817,7 @@ int dms_fusion_create(dms_fusion** out, const dms_fusion_params* p) {
   if (const char* fl = getenv("DMS_FUSED_LIVE")) f->fused_live = atoi(fl) != 0;
   if (const char* ft = getenv("DMS_FOLD_TRACK_INIT")) f->fold_track_init = atoi(ft) != 0;
   if (const char* hl = getenv("DMS_HOST_LAG")) f->host_lag = atoi(hl) == 3 ? 3 : 2;
-  if (const char* lm = getenv("DMS_LATE_MAIN")) f->late_forced = atoi(lm) != 0 ? 1 : 0;
+  if (const char* lm = getenv("DMS_LATE_MAIN")) f->late.forced = atoi(lm) != 0 ? 1 : 0;
   if (const char* lz = getenv("DMS_LAZY_FINAL_PREDICTION")) f->p.lazy_final_prediction = atoi(lz) != 0 ? 1 : 0;  // A/B runs
   if (const char* fa = getenv("DMS_FUSED_ASSOCIATE")) f->p.fused_associate = atoi(fa) != 0 ? 1 : 0;                // A/B runs
   if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_inputs, hipEventDisableTiming);
@@ -960,8 +841,9 @@ int dms_fusion_create(dms_fusion** out, const dms_fusion_params* p) {
     delete f;
     return hip_fail(e, "dms_fusion_create allocation", __FILE__, __LINE__);
   }
-  Carve c;
+  Carver c;
   c.base = f->arena;
+  c.pad = 16;
   layout(f, c);
   {
     unsigned masks[128];
@@ -991,7 +873,6 @@ int dms_fusion_destroy(dms_fusion* f) {
   g_live_contexts -= 1;
   (void)hipDeviceSynchronize();
   drain(f);
-  for (auto e : f->pool) (void)hipEventDestroy(e);
   for (int k = 0; k < 2; ++k)
     if (f->ev_prep_done[k]) (void)hipEventDestroy(f->ev_prep_done[k]);
   for (int k = 0; k < 4; ++k)
@@ -1120,99 +1001,60 @@ dms_model* dms_fusion_model(dms_fusion* f) { return f ? f->model : nullptr; }
 const float* dms_fusion_pose_device(dms_fusion* f) { return f ? f->state->cur.pose : nullptr; }
 dms_odometry* dms_fusion_odometry(dms_fusion* f) { return f ? f->odom : nullptr; }
 
-int dms_fusion_process_frame_begin(dms_fusion* f, const void* rgb_dev, int rgb_channels, const unsigned short* depth_dev,
-                                   const float* inPose16, float weightMultiplier, dms_stream st) {
-  DMS_REQUIRE(f && rgb_dev && depth_dev, "null argument");
-  DMS_REQUIRE(rgb_channels == 3 || rgb_channels == 4, "rgb_channels must be 3 or 4");
-  DMS_REQUIRE(!f->in_frame, "dms_fusion_process_frame_end has not been called for the previous frame");
-  f->lazy.pending = false;  // the skipped prediction of the previous frame: from here on the images are this frame's, as they always were
-  f->armed_now = f->armed;  // (the arming holds for this frame only, whatever path it takes)
-  f->armed = dms_fusion::ArmedBlock();
-  f->armed_written = false;
-  hipStream_t s = (hipStream_t)st;
-  const int W = f->p.width, H = f->p.height, N = W * H;
-  int rc;
-  // the ORB loop poses armed by dms_fusion_set_orb_loop belong to THIS call only, as the reference's hybrid_loops block uses only the
-  // pointers of the processFrame call it runs in (ElasticFusion.cpp:292-350, inside the not-first-frame branch): a bootstrap
-  // frame or a begin that fails further down must not leave them armed for a later frame
-  const bool orb_now = f->orb_armed;
-  f->orb_armed = false;
-  f->gloop_ran = false;
-  // a previous frame that failed between its fuse and the index map that applies the fuse's update left the map with a pending
-  // pass: apply it now instead of failing every later frame
-  if ((rc = model_flush_pending(f->model, s))) return rc;
+// ---- the frame step's first half, stage by stage (called by dms_fusion_process_frame_begin, in this order) ----------------------
 
-  // ---- live half: everything that depends on the incoming frame only -------------------------
-  // Runs on the prep stream into image set frames%2 and odometry ring set frames%3, so it
-  // overlaps the previous frame's tracking / fusion on the caller's stream.  Hazards: these sets
-  // were last read by frame-2 (image set; ring set as lastNextImage), hence the wait on its
-  // completion event.  With pipeline_ingest = 0 the same work is issued on the caller's stream.
-  // Which ring set holds lastNextImage: the reference hands this frame's intensity pyramid on to the next call only when the
-  // tracker ran with so3 (`if (so3) swap(lastNextImage[i], nextImage[i])`, RGBDOdometry.cpp:594-600; the first frame's comes
-  // from initFirstRGB, ElasticFusion.cpp:151) — with the GUI's so3 switch off for a while (dms_fusion_set_option) the SO3
-  // pre-alignment of the frame that turns it on again compares against the last pyramid that WAS handed on.  In flight are the
-  // previous frame's live set and its lastNextImage set; this frame takes the third.  With so3 always on: sets t % 3.
-  const int k2 = (int)(f->frames % 2);
-  int k3 = 0, k3prev = 0;
+struct RingSets {
+  int k2, k3, k3prev;  // image set of this frame's live half, odometry ring set of its live pyramids, the set that holds lastNextImage
+};
+
+// Which ring set holds lastNextImage: the reference hands this frame's intensity pyramid on to the next call only when the
+// tracker ran with so3 (`if (so3) swap(lastNextImage[i], nextImage[i])`, RGBDOdometry.cpp:594-600; the first frame's comes
+// from initFirstRGB, ElasticFusion.cpp:151) — with the GUI's so3 switch off for a while (dms_fusion_set_option) the SO3
+// pre-alignment of the frame that turns it on again compares against the last pyramid that WAS handed on.  In flight are the
+// previous frame's live set and its lastNextImage set; this frame takes the third.  With so3 always on: sets t % 3.
+static RingSets choose_ring_sets(dms_fusion* f) {
+  RingSets r = {(int)(f->frames % 2), 0, 0};
   if (f->frames > 0) {
-    k3prev = f->prev_handed_on ? f->live_set : f->lastnext_set;
-    k3 = 0;
-    while (k3 == f->live_set || k3 == f->lastnext_set) ++k3;
+    r.k3prev = f->prev_handed_on ? f->live_set : f->lastnext_set;
+    while (r.k3 == f->live_set || r.k3 == f->lastnext_set) ++r.k3;
   }
-  f->live_set = k3;
-  f->lastnext_set = k3prev;
+  f->live_set = r.k3;
+  f->lastnext_set = r.k3prev;
   f->prev_handed_on = false;  // set where the tracker is enqueued / the first frame is initialised
-  hipStream_t sp = f->p.pipeline_ingest ? f->s_prep : s;
-  if (f->p.pipeline_ingest) {
-    // The ingest below reads rgb_dev / depth_dev on the prep stream.  Inputs produced asynchronously (an async upload, a
-    // decode kernel) are declared with dms_fusion_inputs_ready(f, producer_stream): the prep stream then waits for that
-    // point of the producer stream.  (Waiting on the caller's stream `s` unconditionally would put this frame's ingest
-    // behind the previous frame's tracking and fusion, which is exactly the overlap the prep stream exists for.)
-    if (f->inputs_armed) {
-      DMS_HIP(hipStreamWaitEvent(sp, f->ev_inputs, 0));
-      f->inputs_armed = false;
-    }
-    // Bounded run-ahead: the host blocks here until frame t - host_lag has finished.  This keeps the HIP command queues
-    // short (with the host many frames ahead the runtime's queue-full handling was measured to cost ~10 % throughput,
-    // DESIGN.md §6).  The buffers themselves are protected on the device: this frame's live half reuses the image set and
-    // the tracker ring set that frame t-2 read, so the prep stream waits for THAT frame's completion event.  (host_lag = 3
-    // has the live half enqueued before frame t-2 ends, so that it starts at once instead of ~60 us into frame t-1:
-    // measured 2.4 % slower — the deeper queues cost more than the earlier start returns; default 2.)
-    {
-      const auto t0 = std::chrono::steady_clock::now();
-      DMS_HIP(hipEventSynchronize(f->ev_main_done[(f->frames + 4 - f->host_lag) % 4]));  // (never recorded: returns at once)
-      const double waited_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      f->host_wait_ms += waited_ms;
-      // the late frame's two rules (see `late_main`)
-      const bool alone = f->late_owner >= 0 ? f->late_owner != 0 : g_live_contexts.load() == 1;
-      const bool may = alone && f->model->sharers == 1 && f->map_initialised && f->frames >= 2;
-      if (f->late_forced >= 0) {
-        f->late_main = f->late_forced != 0;
-      } else if (!may) {
-        f->late_main = false;
-        f->late_low = 0;
-      } else if (f->late_cool > 0) {
-        f->late_cool -= 1;
-        f->late_main = false;
-      } else {
-        if (f->late_main && waited_ms < 0.015) {
-          if (++f->late_low >= 3) {  // the host has no slack left: back to the barrier for a while
-            f->late_main = false;
-            f->late_low = 0;
-            f->late_cool = f->late_backoff;
-            if (f->late_backoff < 4096) f->late_backoff *= 2;
-          }
-        } else {
-          f->late_low = 0;
-          f->late_main = true;
-        }
-      }
-    }
-    DMS_HIP(hipStreamWaitEvent(sp, f->ev_main_done[(f->frames + 2) % 4], 0));  // frame t-2
+  return r;
+}
+
+// pipeline_ingest only: what the prep stream and the host wait for before this frame's live half is enqueued
+static int throttle_host(dms_fusion* f, hipStream_t sp) {
+  // The ingest below reads rgb_dev / depth_dev on the prep stream.  Inputs produced asynchronously (an async upload, a
+  // decode kernel) are declared with dms_fusion_inputs_ready(f, producer_stream): the prep stream then waits for that
+  // point of the producer stream.  (Waiting on the caller's stream `s` unconditionally would put this frame's ingest
+  // behind the previous frame's tracking and fusion, which is exactly the overlap the prep stream exists for.)
+  if (f->inputs_armed) {
+    DMS_HIP(hipStreamWaitEvent(sp, f->ev_inputs, 0));
+    f->inputs_armed = false;
   }
-  // A completed frame's result block (pinned ring slot) tightens the host-side bound of the surfel count that launch grids
-  // are sized from; every clean since then adds at most `slots` surfels.  Without this the bound grows by `slots` per
-  // frame until it reaches the capacity.
+  // Bounded run-ahead: the host blocks here until frame t - host_lag has finished.  This keeps the HIP command queues
+  // short (with the host many frames ahead the runtime's queue-full handling was measured to cost ~10 % throughput,
+  // DESIGN.md §6).  The buffers themselves are protected on the device: this frame's live half reuses the image set and
+  // the tracker ring set that frame t-2 read, so the prep stream waits for THAT frame's completion event.  (host_lag = 3
+  // has the live half enqueued before frame t-2 ends, so that it starts at once instead of ~60 us into frame t-1:
+  // measured 2.4 % slower — the deeper queues cost more than the earlier start returns; default 2.)
+  const auto t0 = std::chrono::steady_clock::now();
+  DMS_HIP(hipEventSynchronize(f->ev_main_done[(f->frames + 4 - f->host_lag) % 4]));  // (never recorded: returns at once)
+  const double waited_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  f->host_wait_ms += waited_ms;
+  // the late frame's two rules (see `late`)
+  const bool alone = f->late_owner >= 0 ? f->late_owner != 0 : g_live_contexts.load() == 1;
+  f->late.update(alone && f->model->sharers == 1 && f->map_initialised && f->frames >= 2, waited_ms);
+  DMS_HIP(hipStreamWaitEvent(sp, f->ev_main_done[(f->frames + 2) % 4], 0));  // frame t-2
+  return DMS_OK;
+}
+
+// A completed frame's result block (pinned ring slot) tightens the host-side bound of the surfel count that launch grids
+// are sized from; every clean since then adds at most `slots` surfels.  Without this the bound grows by `slots` per
+// frame until it reaches the capacity.
+static void bound_surfel_count(dms_fusion* f) {
   f->model->last_writer = f;
   if (f->model->count_hold > 0) {
     f->model->count_hold -= 1;
@@ -1225,262 +1067,335 @@ int dms_fusion_process_frame_begin(dms_fusion* f, const void* rgb_dev, int rgb_c
       if (known < f->model->count_upper) f->model->count_upper = known;
     }
   }
-  f->rgba = f->live[k2].rgba;
-  f->depth_raw = f->live[k2].depth_raw;
-  f->depth_filtered = f->live[k2].depth_filtered;
-  f->depth_metric = f->live[k2].depth_metric;
-  f->depth_metric_filtered = f->live[k2].depth_metric_filtered;
-  odometry_bind_live(f->odom, k3);
-  odometry_bind_lastnext(f->odom, k3prev);
-  const bool want_live = f->p.hybrid_tracking || f->frames == 0;  // the tracker's live pyramids (at the first frame: what initFirstRGB computes, :151)
-  if (f->fused_live) {
-    // The live half in three launches (prep.hip "Fused live half"): ingest (+ raw metric depth + level-0 intensity), the depth
-    // filter (+ filtered metric depth + level-0 depth and vertex map in its epilogue), and one kernel for everything else of the
-    // three pyramid levels.  Same bits as the operator chain below (GPU test).
-    dms_image2d ld[3], lv[3], ln[3], li[3], ldx[3], ldy[3], lg[3];
-    float minScale[3];
-    odometry_live_views(f->odom, ld, lv, ln, li, ldx, ldy, lg, minScale, want_live);
-    {
-      FTimer t(f, sp, "ingest");
-      hipLaunchKernelGGL(k_live_ingest, dim3(min((N + 255) / 256, 2048)), dim3(256), 0, sp, (const unsigned char*)rgb_dev, rgb_channels,
-                         depth_dev, (uchar4*)f->rgba.data, (unsigned short*)f->depth_raw.data, (float*)f->depth_metric.data,
-                         want_live ? (unsigned char*)li[0].data : (unsigned char*)nullptr, N, f->p.depthCut);
-      DMS_CHECK_LAUNCH();
-    }
-    {  // filterDepth + metriciseDepth (ElasticFusion.cpp:118-119)
-      FTimer t(f, sp, "preprocess");
-      bool beside_tracker = f->p.pipeline_ingest != 0;
-      if (beside_tracker && hipStreamQuery(s) == hipSuccess) beside_tracker = false;  // (see the operator chain below)
-      (void)hipGetLastError();
-      if ((rc = depth_bilateral(&f->depth_raw, &f->depth_filtered, f->p.depthCut, sp, beside_tracker ? f->prep_blocks : 0, &f->depth_metric_filtered,
-                                want_live ? &ld[0] : nullptr, want_live ? &lv[0] : nullptr, &f->cam, f->p.maxDepthProcessed)))
-        return rc;
-    }
+}
+
+// The live half in three launches (prep.hip "Fused live half"): ingest (+ raw metric depth + level-0 intensity), the depth
+// filter (+ filtered metric depth + level-0 depth and vertex map in its epilogue), and one kernel for everything else of the
+// three pyramid levels.  Same bits as the operator chain below (GPU test).
+static int live_half_fused(dms_fusion* f, const void* rgb, int channels, const unsigned short* depth, bool want_live, bool beside_tracker, hipStream_t sp) {
+  const int N = f->p.width * f->p.height;
+  int rc;
+  dms_image2d ld[3], lv[3], ln[3], li[3], ldx[3], ldy[3], lg[3];
+  float minScale[3];
+  odometry_live_views(f->odom, ld, lv, ln, li, ldx, ldy, lg, minScale, want_live);
+  {
+    StageTimer t(f->clock, sp, "ingest", f->profiling);
+    hipLaunchKernelGGL(k_live_ingest, dim3(min((N + 255) / 256, 2048)), dim3(256), 0, sp, (const unsigned char*)rgb, channels, depth,
+                       (uchar4*)f->rgba.data, (unsigned short*)f->depth_raw.data, (float*)f->depth_metric.data,
+                       want_live ? (unsigned char*)li[0].data : (unsigned char*)nullptr, N, f->p.depthCut);
+    DMS_CHECK_LAUNCH();
+  }
+  {  // filterDepth + metriciseDepth (ElasticFusion.cpp:118-119)
+    StageTimer t(f->clock, sp, "preprocess", f->profiling);
+    if ((rc = depth_bilateral(&f->depth_raw, &f->depth_filtered, f->p.depthCut, sp, beside_tracker ? f->prep_blocks : 0, &f->depth_metric_filtered,
+                              want_live ? &ld[0] : nullptr, want_live ? &lv[0] : nullptr, &f->cam, f->p.maxDepthProcessed)))
+      return rc;
+  }
+  if (want_live) {
+    StageTimer t(f->clock, sp, "live_pyramids", f->profiling);
+    if ((rc = liveLevelsFused(ld, lv, ln, li, ldx, ldy, lg, &f->cam, f->p.maxDepthProcessed, minScale, sp))) return rc;
+  }
+  return DMS_OK;
+}
+
+// the same as the reference's operator chain, fifteen launches (DMS_FUSED_LIVE=0)
+static int live_half_chain(dms_fusion* f, const void* rgb, int channels, const unsigned short* depth, bool want_live, bool beside_tracker, hipStream_t sp) {
+  const int N = f->p.width * f->p.height;
+  int rc;
+  // "upload": the frame is already in HBM; bring it into the context's textures (ElasticFusion.cpp:111-114)
+  {
+    StageTimer t(f->clock, sp, "ingest", f->profiling);
+    if (channels == 3)
+      hipLaunchKernelGGL(k_rgb_to_rgba, dim3(min((N + 255) / 256, 2048)), dim3(256), 0, sp, (const unsigned char*)rgb, (uchar4*)f->rgba.data, N);
+    else
+      DMS_HIP(hipMemcpyAsync(f->rgba.data, rgb, (size_t)N * 4, hipMemcpyDeviceToDevice, sp));
+    DMS_CHECK_LAUNCH();
+    DMS_HIP(hipMemcpyAsync(f->depth_raw.data, depth, (size_t)N * 2, hipMemcpyDeviceToDevice, sp));
+  }
+  {  // filterDepth + metriciseDepth (ElasticFusion.cpp:118-119)
+    StageTimer t(f->clock, sp, "preprocess", f->profiling);
+    if ((rc = depth_bilateral(&f->depth_raw, &f->depth_filtered, f->p.depthCut, sp, beside_tracker ? f->prep_blocks : 0))) return rc;
+    if ((rc = depth_metric(&f->depth_raw, &f->depth_metric, f->p.depthCut, sp))) return rc;
+    if ((rc = depth_metric(&f->depth_filtered, &f->depth_metric_filtered, f->p.depthCut, sp))) return rc;
+  }
+  {  // live half of frameToModel.initICP / initRGB (ElasticFusion.cpp:190-194): depth pyramid, vertex / normal
+     // maps, intensity pyramid and its derivatives.  At the first frame the intensity pyramid is
+     // what initFirstRGB computes (ElasticFusion.cpp:151); it becomes lastNextImage of frame 1.
+    StageTimer t(f->clock, sp, "live_pyramids", f->profiling);
     if (want_live) {
-      FTimer t(f, sp, "live_pyramids");
-      if ((rc = liveLevelsFused(ld, lv, ln, li, ldx, ldy, lg, &f->cam, f->p.maxDepthProcessed, minScale, sp))) return rc;
+      if ((rc = dms_odometry_initICP_depth(f->odom, &f->depth_filtered, f->p.maxDepthProcessed, sp))) return rc;
+      if ((rc = odometry_initRGB_image(f->odom, &f->rgba, sp))) return rc;
     }
+  }
+  return DMS_OK;
+}
+
+// ---- live half: everything that depends on the incoming frame only -------------------------
+// Runs on the prep stream into image set frames%2 and odometry ring set frames%3, so it
+// overlaps the previous frame's tracking / fusion on the caller's stream.  Hazards: these sets
+// were last read by frame-2 (image set; ring set as lastNextImage), hence the wait on its
+// completion event.  With pipeline_ingest = 0 the same work is issued on the caller's stream.
+static int live_half(dms_fusion* f, const RingSets& r, const void* rgb, int channels, const unsigned short* depth, hipStream_t s, hipStream_t sp) {
+  f->rgba = f->live[r.k2].rgba;
+  f->depth_raw = f->live[r.k2].depth_raw;
+  f->depth_filtered = f->live[r.k2].depth_filtered;
+  f->depth_metric = f->live[r.k2].depth_metric;
+  f->depth_metric_filtered = f->live[r.k2].depth_metric_filtered;
+  odometry_bind_live(f->odom, r.k3);
+  odometry_bind_lastnext(f->odom, r.k3prev);
+  const bool want_live = f->p.hybrid_tracking || f->frames == 0;  // the tracker's live pyramids (at the first frame: what initFirstRGB computes, :151)
+  // (fat blocks of the depth filter only while the caller's stream is busy: they exist to leave the previous frame's tracker its
+  // compute units; when nothing is running there — the first frame after a pause — the whole-chip form is 2.5x shorter and this
+  // frame's tracker is waiting for it)
+  bool beside_tracker = f->p.pipeline_ingest != 0;
+  if (beside_tracker && hipStreamQuery(s) == hipSuccess) beside_tracker = false;
+  (void)hipGetLastError();  // (hipErrorNotReady is the expected answer)
+  return f->fused_live ? live_half_fused(f, rgb, channels, depth, want_live, beside_tracker, sp)
+                       : live_half_chain(f, rgb, channels, depth, want_live, beside_tracker, sp);
+}
+
+// pipeline_ingest only: the frame's stream continues behind the live half
+static int join_prep_stream(dms_fusion* f, int k2, hipStream_t s, hipStream_t sp) {
+  DMS_HIP(hipEventRecord(f->ev_prep_done[k2], sp));
+  if (f->late.on) {
+    // the HOST waits for the live half and enqueues the frame behind it: no barrier packet on the frame's queue
+    const auto t0 = std::chrono::steady_clock::now();
+    DMS_HIP(hipEventSynchronize(f->ev_prep_done[k2]));
+    f->host_wait_prep_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   } else {
-    // "upload": the frame is already in HBM; bring it into the context's textures (ElasticFusion.cpp:111-114)
-    {
-      FTimer t(f, sp, "ingest");
-      if (rgb_channels == 3)
-        hipLaunchKernelGGL(k_rgb_to_rgba, dim3(min((N + 255) / 256, 2048)), dim3(256), 0, sp, (const unsigned char*)rgb_dev,
-                           (uchar4*)f->rgba.data, N);
-      else
-        DMS_HIP(hipMemcpyAsync(f->rgba.data, rgb_dev, (size_t)N * 4, hipMemcpyDeviceToDevice, sp));
-      DMS_CHECK_LAUNCH();
-      DMS_HIP(hipMemcpyAsync(f->depth_raw.data, depth_dev, (size_t)N * 2, hipMemcpyDeviceToDevice, sp));
-    }
-    {  // filterDepth + metriciseDepth (ElasticFusion.cpp:118-119)
-      FTimer t(f, sp, "preprocess");
-      // (fat blocks only while the caller's stream is busy: they exist to leave the previous frame's tracker its compute
-      // units; when nothing is running there — the first frame after a pause — the whole-chip form is 2.5x shorter and this
-      // frame's tracker is waiting for it)
-      bool beside_tracker = f->p.pipeline_ingest != 0;
-      if (beside_tracker && hipStreamQuery(s) == hipSuccess) beside_tracker = false;
-      (void)hipGetLastError();  // (hipErrorNotReady is the expected answer)
-      if ((rc = depth_bilateral(&f->depth_raw, &f->depth_filtered, f->p.depthCut, sp, beside_tracker ? f->prep_blocks : 0))) return rc;
-      if ((rc = depth_metric(&f->depth_raw, &f->depth_metric, f->p.depthCut, sp))) return rc;
-      if ((rc = depth_metric(&f->depth_filtered, &f->depth_metric_filtered, f->p.depthCut, sp))) return rc;
-    }
-    {  // live half of frameToModel.initICP / initRGB (ElasticFusion.cpp:190-194): depth pyramid, vertex / normal
-       // maps, intensity pyramid and its derivatives.  At the first frame the intensity pyramid is
-       // what initFirstRGB computes (ElasticFusion.cpp:151); it becomes lastNextImage of frame 1.
-      FTimer t(f, sp, "live_pyramids");
-      if (f->p.hybrid_tracking || f->frames == 0) {
-        if ((rc = dms_odometry_initICP_depth(f->odom, &f->depth_filtered, f->p.maxDepthProcessed, sp))) return rc;
-        if ((rc = odometry_initRGB_image(f->odom, &f->rgba, sp))) return rc;
-      }
-    }
+    DMS_HIP(hipStreamWaitEvent(s, f->ev_prep_done[k2], 0));
   }
-  if (f->p.pipeline_ingest) {
-    DMS_HIP(hipEventRecord(f->ev_prep_done[k2], sp));
-    if (f->late_main) {
-      // the HOST waits for the live half and enqueues the frame behind it: no barrier packet on the frame's queue
-      const auto t0 = std::chrono::steady_clock::now();
-      DMS_HIP(hipEventSynchronize(f->ev_prep_done[k2]));
-      f->host_wait_prep_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    } else {
-      DMS_HIP(hipStreamWaitEvent(s, f->ev_prep_done[k2], 0));
-    }
-    f->last_prep = k2;
-  }
+  f->last_prep = k2;
+  return DMS_OK;
+}
 
+// first run (ElasticFusion.cpp:132-152): surfels from this frame, pose = inPose or identity
+static int bootstrap_frame(dms_fusion* f, const float* inPose16, hipStream_t s) {
+  int rc;
   Pose16 prior;
-  memset(&prior, 0, sizeof(prior));
-  if (inPose16) memcpy(prior.v, inPose16, sizeof(prior.v));
+  if (inPose16)
+    memcpy(prior.v, inPose16, sizeof(prior.v));
+  else
+    for (int i = 0; i < 16; ++i) prior.v[i] = (i % 5 == 0) ? 1.f : 0.f;
+  hipLaunchKernelGGL(k_pose_set, dim3(1), dim3(64), 0, s, f->state, prior);
+  DMS_CHECK_LAUNCH();
+  if (!f->adopting) {  // (an imported camera joins a map that exists: this frame only seeds its live state)
+    StageTimer t(f->clock, s, "initialise", f->profiling);
+    // computeFeedbackBuffers takes `const int& maxDepthProcessed` (Context.h:211): 25.0f -> 25
+    if ((rc = model_initialise(f->model, &f->rgba, &f->depth_metric, &f->depth_metric_filtered, &f->cam, f->tick, f->p.timeIdx,
+                               (float)(int)f->p.maxDepthProcessed, s)))
+      return rc;
+    if ((rc = snapshot_feedback(f, s))) return rc;
+    if (f->req_cluster != f->cur_cluster && !f->clusters.count(f->req_cluster) && f->model == f->own_model) {
+      // initialise(..., cluster, pose) of the first frame under another id: the surfels go into buffers of their own and the
+      // constructor's cluster stays behind, empty
+      f->clusters[f->cur_cluster] = nullptr;
+      f->clusters[f->req_cluster] = f->model;
+      f->cur_cluster = f->req_cluster;
+    }
+  }
+  // initFirstRGB (ElasticFusion.cpp:151): the intensity pyramid of this frame already sits in ring set 0
+  f->map_initialised = true;
+  f->prev_handed_on = true;
+  return DMS_OK;
+}
 
-  f->cur_k2 = k2;
+// the tracking prediction, the tracker's model pyramids and the track itself (ElasticFusion.cpp:158-200, 252-268)
+static int track_frame(dms_fusion* f, const float* inPose16, float weightMultiplier, hipStream_t s) {
+  int rc;
+  if (inPose16) {  // without a prior the pose block is already consistent: the previous frame left lastPose = pose and its inverse
+    Pose16 prior;
+    memcpy(prior.v, inPose16, sizeof(prior.v));
+    hipLaunchKernelGGL(k_frame_begin, dim3(1), dim3(64), 0, s, f->state, prior, 1);
+    DMS_CHECK_LAUNCH();
+  }
+  // ElasticFusion.cpp:165-167: an extra block of this predict's fill-in launch takes the denseEnough decision
+  // (round 6) the set-up of this frame's tracker call rides on the prediction's resolve pass - a kernel boundary before the model
+  // pyramid launch, which can then run the tracker's SO3 stage beside the pyramid (track.hip: k_so3_model)
+  const TrackFold fold = {f->state->cur.pose, f->p.pyramid, f->p.fastOdom, f->p.so3, 0};
+  TrackInitArgs early;
+  memset(&early, 0, sizeof(early));
+  bool early_taken = false;
+  const bool want_early = f->p.hybrid_tracking && f->fold_track_init && !f->lost && odometry_early_init_args(f->odom, &fold, &early) != 0;
+  if ((rc = predict_tracking(f, s, inPose16 != nullptr, want_early ? &early : nullptr, &early_taken))) return rc;
+  if (want_early && !early_taken) odometry_early_init_args(f->odom, nullptr, &early);  // (no fused resolve pass this frame: the set-up folds into the pyramid kernel as before)
+  if (!f->p.hybrid_tracking) {  // with tracking on, the tracker's last kernel does this
+    hipLaunchKernelGGL(k_frame_after_track, dim3(1), dim3(64), 0, s, f->state, weightMultiplier);
+    DMS_CHECK_LAUNCH();
+    return DMS_OK;
+  }
+  {
+    StageTimer t(f->clock, s, "odom_init", f->profiling);
+    // WARNING (reference): initICP* must be called before initRGB* (ElasticFusion.cpp:172)
+    // (the set-up of the tracker call below rides on the pyramid kernel: no launch of its own, DMS_FOLD_TRACK_INIT=0 to compare)
+    if ((rc = odometry_initModel_fused(f->odom, f->pred.vertex.data, f->pred.normal.data, f->pred.image.data, f->fill.vertex.data,
+                                       f->fill.normal.data, f->fill.image.data, &f->state->fill_in, f->p.frameToFrameRGB ? 1 : 0,
+                                       f->state->cur.pose, s, 1,  // (last pyramid step: inside the tracker's first kernel, below)
+                                       f->dense_by_counters ? f->tickets : nullptr, (f->p.width / 20) * (f->p.height / 20),
+                                       f->fold_track_init ? &fold : nullptr)))
+      return rc;
+    // initICP / initRGB: the live half ran on the prep stream; nextDepth = lastDepth (same source)
+    odometry_alias_next_depth(f->odom);
+  }
+  {
+    StageTimer t(f->clock, s, "track", f->profiling);
+    if ((rc = odometry_track_enqueue(f->odom, nullptr, nullptr, f->state->cur.pose, f->p.rgbOnly, f->p.icpWeight, f->p.pyramid,
+                                     f->p.fastOdom, f->p.so3, 0, s, f->state, weightMultiplier)))
+      return rc;
+    f->prev_handed_on = f->p.so3 != 0;
+    // (the tracker's finalize kernel writes the new pose straight back into f->state->cur.pose)
+  }
+  return DMS_OK;
+}
+
+// --rl (ElasticFusion.cpp:204-244); lastFrameRecovery is only ever set by the compiled-out fern block
+static int check_relocalisation(dms_fusion* f, hipStream_t s) {
+  int rc;
+  dms_track_result tr;
+  if ((rc = dms_odometry_fetch_result(f->odom, &tr, s))) return rc;  // synchronises
+  f->tracking_ok = (double)tr.lastICPError < 1e-04;
+  if (f->lost) return DMS_OK;
+  double cov[36];
+  if ((rc = dms_odometry_getCovariance(f->odom, cov))) return rc;
+  for (int i = 0; i < 6; ++i)
+    if (cov[i * 7] > 1e-04) {
+      f->tracking_ok = false;
+      break;
+    }
+  if (!f->tracking_ok) {
+    f->tracking_count += 1;
+    if (f->tracking_count > 10) f->lost = true;
+  } else {
+    f->tracking_count = 0;
+  }
+  return DMS_OK;
+}
+
+// closeLoops without a fern match (ElasticFusion.cpp:399-497): the camera is never lost and
+// rawGraph is empty (nothing deforms the map inside this library)
+static int local_loop_candidate(dms_fusion* f, hipStream_t s) {
+  int rc;
+  {
+    StageTimer t(f->clock, s, "predict_old", f->profiling);  // combinedPredict(..., 0, id, tick - timeDelta, timeDelta, INACTIVE) (:403-406)
+    if ((rc = splat_predict(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, f->p.confidence, 0, f->p.timeIdx,
+                            f->tick - f->p.timeDelta, f->p.timeDelta, 0, f->zbuf, &f->pred_old, nullptr, 1, s)))
+      return rc;
+  }
+  {
+    StageTimer t(f->clock, s, "loop_init", f->profiling);  // modelToModel().initICPModel / initRGBModel / initICP / initRGB (:409-418)
+    if ((rc = odometry_initModel_fused(f->odom_m2m, f->pred_old.vertex.data, f->pred_old.normal.data, f->pred_old.image.data,
+                                       f->pred_old.vertex.data, f->pred_old.normal.data, f->pred_old.image.data, &f->state->fill_in, 0,
+                                       f->state->cur.pose, s)))
+      return rc;
+    if ((rc = odometry_initLive_fused(f->odom_m2m, f->pred.vertex.data, f->pred.normal.data, f->pred.image.data, &f->state->fill_in, s)))
+      return rc;
+  }
+  {
+    StageTimer t(f->clock, s, "loop_track", f->profiling);  // getIncrementalTransformation(trans, rot, false, 10, pyramid, fastOdom, false) (:424-425)
+    if ((rc = odometry_track_enqueue(f->odom_m2m, nullptr, nullptr, f->state->cur.pose, 0, 10.f, f->p.pyramid, f->p.fastOdom, 0, 0, s,
+                                     nullptr, 1.f)))
+      return rc;
+  }
+  // covariance + acceptance test + constraint sampling (:427-474), all on device
+  return odometry_loop_candidate(f->odom_m2m, f->state, &f->pred.vertex, &f->pred_old.time, f->p.maxDepthProcessed, f->loop,
+                                 (float*)((char*)f->loop + up256(sizeof(LoopState))), s);
+}
+
+// ElasticFusion::fuseFrame (ElasticFusion.cpp:639-677): candidate key frame = this prediction
+// (KeyFrame.h:83-172: intensity of the image, verticesToDepth of the vertex map), reduced
+// nid_pyramid_level times (MutualInformation.cpp:169-174), scored against the live pyramids
+static int nid_gate(dms_fusion* f, hipStream_t s, bool* fuse_now) {
+  int rc;
+  StageTimer t(f->clock, s, "nid", f->profiling);
+  const int L = f->p.nid_pyramid_level;
+  if (f->p.local_loop_closure) {
+    // with a rendered INACTIVE view the key frame's "old" half is real (KeyFrame.h:139-166; the
+    // reference copies the old vertex texture with the byte count of a released array, :147-150,
+    // so its old depth map is undefined — the evident intent is implemented)
+    if ((rc = imageToIntensity(&f->pred_old.image, &f->kf_old_img[0], s))) return rc;
+    if ((rc = verticesToDepth((const float*)f->pred_old.vertex.data, &f->kf_old_dmap[0], f->p.maxDepthProcessed, s))) return rc;
+    for (int l = 1; l <= L; ++l) {
+      if ((rc = pyrDownUcharGauss(&f->kf_old_img[l - 1], &f->kf_old_img[l], s))) return rc;
+      if ((rc = pyrDownGaussF(&f->kf_old_dmap[l - 1], &f->kf_old_dmap[l], s))) return rc;
+    }
+  }
+  if ((rc = imageToIntensity(&f->pred.image, &f->kf_img[0], s))) return rc;
+  if ((rc = verticesToDepth((const float*)f->pred.vertex.data, &f->kf_dmap[0], f->p.maxDepthProcessed, s))) return rc;
+  for (int l = 1; l <= L; ++l) {
+    if ((rc = pyrDownUcharGauss(&f->kf_img[l - 1], &f->kf_img[l], s))) return rc;
+    if ((rc = pyrDownGaussF(&f->kf_dmap[l - 1], &f->kf_dmap[l], s))) return rc;
+  }
+  dms_image2d nextImg, nextD;
+  if ((rc = odometry_next_buffers(f->odom, L, &nextImg, &nextD))) return rc;
+  if ((rc = computeNIDImg(&f->kf_img[L], &f->kf_old_img[L], &f->kf_dmap[L], &f->kf_old_dmap[L], &nextImg, f->p.nid_bins_img, f->nid_ws,
+                          f->nid_ws_bytes, f->nid_host, nullptr, s)))
+    return rc;
+  if ((rc = computeNIDDepth(&f->kf_dmap[L], &f->kf_old_dmap[L], &nextD, f->p.nid_bins_depth, f->p.maxDepthProcessed * 1000.0f, f->nid_ws,
+                            f->nid_ws_bytes, f->nid_host + 1, nullptr, s)))
+    return rc;  // (both calls synchronise: the decision is taken on the host, as in the reference)
+  f->last_nid = (f->p.nid_depth_lambda * f->nid_host[1]) + ((1.0f - f->p.nid_depth_lambda) * f->nid_host[0]);
+  *fuse_now = f->last_nid > f->p.nid_threshold;
+  return DMS_OK;
+}
+
+int dms_fusion_process_frame_begin(dms_fusion* f, const void* rgb_dev, int rgb_channels, const unsigned short* depth_dev,
+                                   const float* inPose16, float weightMultiplier, dms_stream st) {
+  DMS_REQUIRE(f && rgb_dev && depth_dev, "null argument");
+  DMS_REQUIRE(rgb_channels == 3 || rgb_channels == 4, "rgb_channels must be 3 or 4");
+  DMS_REQUIRE(!f->in_frame, "dms_fusion_process_frame_end has not been called for the previous frame");
+  f->lazy.pending = false;  // the skipped prediction of the previous frame: from here on the images are this frame's, as they always were
+  f->armed_now = f->armed;  // (the arming holds for this frame only, whatever path it takes)
+  f->armed = dms_fusion::ArmedBlock();
+  f->armed_written = false;
+  hipStream_t s = (hipStream_t)st;
+  int rc;
+  // the ORB loop poses armed by dms_fusion_set_orb_loop belong to THIS call only, as the reference's hybrid_loops block uses only the
+  // pointers of the processFrame call it runs in (ElasticFusion.cpp:292-350, inside the not-first-frame branch): a bootstrap
+  // frame or a begin that fails further down must not leave them armed for a later frame
+  const bool orb_now = f->orb_armed;
+  f->orb_armed = false;
+  f->gloop_ran = false;
+  // a previous frame that failed between its fuse and the index map that applies the fuse's update left the map with a pending
+  // pass: apply it now instead of failing every later frame
+  if ((rc = model_flush_pending(f->model, s))) return rc;
+
+  const RingSets ring = choose_ring_sets(f);
+  hipStream_t sp = f->p.pipeline_ingest ? f->s_prep : s;
+  if (f->p.pipeline_ingest && (rc = throttle_host(f, sp))) return rc;
+  bound_surfel_count(f);
+  if ((rc = live_half(f, ring, rgb_dev, rgb_channels, depth_dev, s, sp))) return rc;
+  if (f->p.pipeline_ingest && (rc = join_prep_stream(f, ring.k2, s, sp))) return rc;
+
+  f->cur_k2 = ring.k2;
   f->cur_bootstrap = !f->map_initialised;
   f->cur_fuse_now = true;
   f->tracking_ok = true;
-  if (!f->map_initialised) {
-    // first run (ElasticFusion.cpp:132-152): surfels from this frame, pose = inPose or identity
-    if (!inPose16)
-      for (int i = 0; i < 16; ++i) prior.v[i] = (i % 5 == 0) ? 1.f : 0.f;
-    hipLaunchKernelGGL(k_pose_set, dim3(1), dim3(64), 0, s, f->state, prior);
-    DMS_CHECK_LAUNCH();
-    if (!f->adopting) {  // (an imported camera joins a map that exists: this frame only seeds its live state)
-      FTimer t(f, s, "initialise");
-      // computeFeedbackBuffers takes `const int& maxDepthProcessed` (Context.h:211): 25.0f -> 25
-      if ((rc = model_initialise(f->model, &f->rgba, &f->depth_metric, &f->depth_metric_filtered, &f->cam, f->tick, f->p.timeIdx,
-                                 (float)(int)f->p.maxDepthProcessed, s)))
-        return rc;
-      if ((rc = snapshot_feedback(f, s))) return rc;
-      if (f->req_cluster != f->cur_cluster && !f->clusters.count(f->req_cluster) && f->model == f->own_model) {
-        // initialise(..., cluster, pose) of the first frame under another id: the surfels go into buffers of their own and the
-        // constructor's cluster stays behind, empty
-        f->clusters[f->cur_cluster] = nullptr;
-        f->clusters[f->req_cluster] = f->model;
-        f->cur_cluster = f->req_cluster;
-      }
-    }
-    // initFirstRGB (ElasticFusion.cpp:151): the intensity pyramid of this frame already sits in ring set 0
-    f->map_initialised = true;
-    f->prev_handed_on = true;
+  if (f->cur_bootstrap) {
+    if ((rc = bootstrap_frame(f, inPose16, s))) return rc;
   } else {
-    if (inPose16) {  // without a prior the pose block is already consistent: the previous frame left lastPose = pose and its inverse
-      hipLaunchKernelGGL(k_frame_begin, dim3(1), dim3(64), 0, s, f->state, prior, 1);
-      DMS_CHECK_LAUNCH();
-    }
-    // ElasticFusion.cpp:165-167: an extra block of this predict's fill-in launch takes the denseEnough decision
-    // (round 6) the set-up of this frame's tracker call rides on the prediction's resolve pass - a kernel boundary before the model
-    // pyramid launch, which can then run the tracker's SO3 stage beside the pyramid (track.hip: k_so3_model)
-    const TrackFold fold = {f->state->cur.pose, f->p.pyramid, f->p.fastOdom, f->p.so3, 0};
-    TrackInitArgs early;
-    memset(&early, 0, sizeof(early));
-    bool early_taken = false;
-    const bool want_early = f->p.hybrid_tracking && f->fold_track_init && !f->lost && odometry_early_init_args(f->odom, &fold, &early) != 0;
-    if ((rc = predict(f, 0.7f, s, nullptr, true, 2, inPose16 != nullptr, want_early ? &early : nullptr, &early_taken))) return rc;
-    if (want_early && !early_taken) odometry_early_init_args(f->odom, nullptr, &early);  // (no fused resolve pass this frame: the set-up folds into the pyramid kernel as before)
-    if (f->p.hybrid_tracking) {
-      {
-        FTimer t(f, s, "odom_init");
-        // WARNING (reference): initICP* must be called before initRGB* (ElasticFusion.cpp:172)
-        // (the set-up of the tracker call below rides on the pyramid kernel: no launch of its own, DMS_FOLD_TRACK_INIT=0 to compare)
-        if ((rc = odometry_initModel_fused(f->odom, f->pred.vertex.data, f->pred.normal.data, f->pred.image.data, f->fill.vertex.data,
-                                           f->fill.normal.data, f->fill.image.data, &f->state->fill_in, f->p.frameToFrameRGB ? 1 : 0,
-                                           f->state->cur.pose, s, 1,  // (last pyramid step: inside the tracker's first kernel, below)
-                                           f->dense_by_counters ? f->tickets : nullptr, (f->p.width / 20) * (f->p.height / 20),
-                                           f->fold_track_init ? &fold : nullptr)))
-          return rc;
-        // initICP / initRGB: the live half ran on the prep stream; nextDepth = lastDepth (same source)
-        odometry_alias_next_depth(f->odom);
-      }
-      {
-        FTimer t(f, s, "track");
-        if ((rc = odometry_track_enqueue(f->odom, nullptr, nullptr, f->state->cur.pose, f->p.rgbOnly, f->p.icpWeight, f->p.pyramid,
-                                         f->p.fastOdom, f->p.so3, 0, s, f->state, weightMultiplier)))
-          return rc;
-        f->prev_handed_on = f->p.so3 != 0;
-        // (the tracker's finalize kernel writes the new pose straight back into f->state->cur.pose)
-      }
-      if (f->p.reloc) {  // ElasticFusion.cpp:204-244; lastFrameRecovery is only ever set by the compiled-out fern block
-        dms_track_result tr;
-        if ((rc = dms_odometry_fetch_result(f->odom, &tr, s))) return rc;  // synchronises
-        f->tracking_ok = (double)tr.lastICPError < 1e-04;
-        if (!f->lost) {
-          double cov[36];
-          if ((rc = dms_odometry_getCovariance(f->odom, cov))) return rc;
-          for (int i = 0; i < 6; ++i)
-            if (cov[i * 7] > 1e-04) {
-              f->tracking_ok = false;
-              break;
-            }
-          if (!f->tracking_ok) {
-            f->tracking_count += 1;
-            if (f->tracking_count > 10) f->lost = true;
-          } else {
-            f->tracking_count = 0;
-          }
-        }
-      }
-    }
-    if (!f->p.hybrid_tracking) {  // with tracking on, the tracker's last kernel does this
-      hipLaunchKernelGGL(k_frame_after_track, dim3(1), dim3(64), 0, s, f->state, weightMultiplier);
-      DMS_CHECK_LAUNCH();
-    }
+    if ((rc = track_frame(f, inPose16, weightMultiplier, s))) return rc;
+    if (f->p.hybrid_tracking && f->p.reloc && (rc = check_relocalisation(f, s))) return rc;
     // "GlobalPredict" (ElasticFusion.cpp:273): its consumers are the NID key-framing gate below and the
     // fern / loop-closure blocks, which this reference compiles out with `if (false)` (ElasticFusion.cpp:279,
     // :593); the final predict overwrites every image it writes before the frame returns.
-    bool fuse_now = true;
     if (f->p.global_predict || f->p.nid_keyframing || f->p.local_loop_closure)
-      if ((rc = predict(f, f->p.confidence, s))) return rc;
+      if ((rc = predict_view(f, f->p.confidence, s))) return rc;
     if (orb_now) {
       // hybrid_loops && orbTcwOld && orbTcwNew (ElasticFusion.cpp:292-350): the constraints of the ORB loop closure; the caller's
       // Deformation::constrain (:337) decides between dms_fusion_fetch_loop and _end.  The block ends with predict(context, rf)
       // (:349), which restores the current view for whoever reads it next in this frame
       if ((rc = global_loop_device(f, f->orb_old, f->orb_new, 0, s))) return rc;
-      if ((rc = predict(f, f->p.confidence, s))) return rc;  // unconditional, as :349
+      if ((rc = predict_view(f, f->p.confidence, s))) return rc;  // unconditional, as :349
     }
-    if (f->p.local_loop_closure && !f->lost) {
-      // closeLoops without a fern match (ElasticFusion.cpp:399-497): the camera is never lost and
-      // rawGraph is empty (nothing deforms the map inside this library)
-      {
-        FTimer t(f, s, "predict_old");  // combinedPredict(..., 0, id, tick - timeDelta, timeDelta, INACTIVE) (:403-406)
-        if ((rc = splat_predict(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, f->p.confidence, 0, f->p.timeIdx,
-                                f->tick - f->p.timeDelta, f->p.timeDelta, 0, f->zbuf, &f->pred_old, nullptr, 1, s)))
-          return rc;
-      }
-      {
-        FTimer t(f, s, "loop_init");  // modelToModel().initICPModel / initRGBModel / initICP / initRGB (:409-418)
-        if ((rc = odometry_initModel_fused(f->odom_m2m, f->pred_old.vertex.data, f->pred_old.normal.data, f->pred_old.image.data,
-                                           f->pred_old.vertex.data, f->pred_old.normal.data, f->pred_old.image.data, &f->state->fill_in, 0,
-                                           f->state->cur.pose, s)))
-          return rc;
-        if ((rc = odometry_initLive_fused(f->odom_m2m, f->pred.vertex.data, f->pred.normal.data, f->pred.image.data, &f->state->fill_in, s)))
-          return rc;
-      }
-      {
-        FTimer t(f, s, "loop_track");  // getIncrementalTransformation(trans, rot, false, 10, pyramid, fastOdom, false) (:424-425)
-        if ((rc = odometry_track_enqueue(f->odom_m2m, nullptr, nullptr, f->state->cur.pose, 0, 10.f, f->p.pyramid, f->p.fastOdom, 0, 0, s,
-                                         nullptr, 1.f)))
-          return rc;
-      }
-      // covariance + acceptance test + constraint sampling (:427-474), all on device
-      if ((rc = odometry_loop_candidate(f->odom_m2m, f->state, &f->pred.vertex, &f->pred_old.time, f->p.maxDepthProcessed, f->loop,
-                                        (float*)((char*)f->loop + up256(sizeof(LoopState))), s)))
-        return rc;
-    }
-    if (f->p.nid_keyframing) {
-      // ElasticFusion::fuseFrame (ElasticFusion.cpp:639-677): candidate key frame = this prediction
-      // (KeyFrame.h:83-172: intensity of the image, verticesToDepth of the vertex map), reduced
-      // nid_pyramid_level times (MutualInformation.cpp:169-174), scored against the live pyramids
-      FTimer t(f, s, "nid");
-      const int L = f->p.nid_pyramid_level;
-      if (f->p.local_loop_closure) {
-        // with a rendered INACTIVE view the key frame's "old" half is real (KeyFrame.h:139-166; the
-        // reference copies the old vertex texture with the byte count of a released array, :147-150,
-        // so its old depth map is undefined — the evident intent is implemented)
-        if ((rc = imageToIntensity(&f->pred_old.image, &f->kf_old_img[0], s))) return rc;
-        if ((rc = verticesToDepth((const float*)f->pred_old.vertex.data, &f->kf_old_dmap[0], f->p.maxDepthProcessed, s))) return rc;
-        for (int l = 1; l <= L; ++l) {
-          if ((rc = pyrDownUcharGauss(&f->kf_old_img[l - 1], &f->kf_old_img[l], s))) return rc;
-          if ((rc = pyrDownGaussF(&f->kf_old_dmap[l - 1], &f->kf_old_dmap[l], s))) return rc;
-        }
-      }
-      if ((rc = imageToIntensity(&f->pred.image, &f->kf_img[0], s))) return rc;
-      if ((rc = verticesToDepth((const float*)f->pred.vertex.data, &f->kf_dmap[0], f->p.maxDepthProcessed, s))) return rc;
-      for (int l = 1; l <= L; ++l) {
-        if ((rc = pyrDownUcharGauss(&f->kf_img[l - 1], &f->kf_img[l], s))) return rc;
-        if ((rc = pyrDownGaussF(&f->kf_dmap[l - 1], &f->kf_dmap[l], s))) return rc;
-      }
-      dms_image2d nextImg, nextD;
-      if ((rc = odometry_next_buffers(f->odom, L, &nextImg, &nextD))) return rc;
-      if ((rc = computeNIDImg(&f->kf_img[L], &f->kf_old_img[L], &f->kf_dmap[L], &f->kf_old_dmap[L], &nextImg, f->p.nid_bins_img, f->nid_ws,
-                              f->nid_ws_bytes, f->nid_host, nullptr, s)))
-        return rc;
-      if ((rc = computeNIDDepth(&f->kf_dmap[L], &f->kf_old_dmap[L], &nextD, f->p.nid_bins_depth, f->p.maxDepthProcessed * 1000.0f, f->nid_ws,
-                                f->nid_ws_bytes, f->nid_host + 1, nullptr, s)))
-        return rc;  // (both calls synchronise: the decision is taken on the host, as in the reference)
-      f->last_nid = (f->p.nid_depth_lambda * f->nid_host[1]) + ((1.0f - f->p.nid_depth_lambda) * f->nid_host[0]);
-      fuse_now = f->last_nid > f->p.nid_threshold;
-    } else {
+    const bool loop_now = f->p.local_loop_closure && !f->lost;
+    if (loop_now && (rc = local_loop_candidate(f, s))) return rc;
+    bool fuse_now = true;
+    if (!f->p.nid_keyframing)
       f->last_nid = 0.f;
-    }
+    else if ((rc = nid_gate(f, s, &fuse_now)))
+      return rc;
     f->cur_fuse_now = fuse_now;
-    if (f->p.local_loop_closure && !f->lost) {
+    if (loop_now) {
       // the candidate is readable (dms_fusion_fetch_loop) before the second half is enqueued
       const int k4 = (int)(f->frames % 4);  // this frame's result slot (the final prediction mirrors into the same one)
       DMS_HIP(hipMemcpyAsync(f->h_state + k4, f->state, sizeof(FrameState), hipMemcpyDeviceToHost, s));
@@ -1490,6 +1405,55 @@ int dms_fusion_process_frame_begin(dms_fusion* f, const void* rgb_dev, int rgb_c
   }
   f->in_frame = true;
   return DMS_OK;
+}
+
+// ---- the fusion block of the second half (ElasticFusion.cpp:506-564), stage by stage ------------------------------------------
+
+// fused_associate: the first index map has one reader, the association, and the second one overwrites its images: it is
+// projected only, into a z-buffer of its own, the association reads that (k_fuse_associate_zbuf), and the second index
+// map's resolve pass hands it back empty.  Same bits in the slots, the winners and everything after them.
+static int index_map_for_fuse(dms_fusion* f, int timeDeltaEff, hipStream_t s) {
+  StageTimer t(f->clock, s, "index_map", f->profiling);
+  if (!f->p.fused_associate)
+    return index_map(f->model, &f->state->cur, &f->cam, f->tick, f->p.timeIdx, f->p.maxDepthProcessed, timeDeltaEff, f->zbuf, &f->imap, 1, 1, s);
+  const bool stale = f->zbuf_assoc_dirty;  // a frame that set it never reached its clearing resolve: clear here
+  f->zbuf_assoc_dirty = true;
+  return index_project(f->model, &f->state->cur, &f->cam, f->tick, f->p.timeIdx, f->p.maxDepthProcessed, timeDeltaEff, f->zbuf_assoc,
+                       stale ? 0 : 1, s);
+}
+
+static int fuse_measurements(dms_fusion* f, hipStream_t s) {
+  StageTimer t(f->clock, s, "fuse", f->profiling);
+  // (update pass: inside the next index map)
+  if (f->p.fused_associate)
+    return model_fuse_zbuf(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->rgba, &f->depth_metric, &f->depth_metric_filtered,
+                           f->zbuf_assoc, &f->cam, f->p.maxDepthProcessed, 1.f, &f->state->weighting, s, 1);
+  return model_fuse(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->rgba, &f->depth_metric, &f->depth_metric_filtered, &f->imap,
+                    &f->cam, f->p.maxDepthProcessed, 1.f, &f->state->weighting, 1, s, 1);
+}
+
+static int index_map_for_clean(dms_fusion* f, int timeDeltaEff, hipStream_t s) {
+  StageTimer t(f->clock, s, "index_map", f->profiling);
+  const bool hand_back = f->p.fused_associate && !f->zbuf_assoc_keep_dirty;
+  if (int rc = index_map(f->model, &f->state->cur, &f->cam, f->tick, f->p.timeIdx, f->p.maxDepthProcessed, timeDeltaEff, f->zbuf, &f->imap, 1,
+                         1, s, hand_back ? f->zbuf_assoc : nullptr))
+    return rc;
+  if (hand_back) f->zbuf_assoc_dirty = false;
+  return DMS_OK;
+}
+
+// a deformation is a second pose update this frame: predict the depth again to decide whose
+// time stamps to refresh (ElasticFusion.cpp:541-553; synthesizeDepth leaves `actv` false)
+static int synthesise_depth(dms_fusion* f, int timeDeltaEff, hipStream_t s) {
+  StageTimer t(f->clock, s, "synth_depth", f->profiling);
+  return splat_predict(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, f->p.confidence, f->tick, f->p.timeIdx,
+                       f->tick - timeDeltaEff, 65535, 0, f->zbuf, nullptr, &f->depth_synth, 1, s);
+}
+
+static int clean_map(dms_fusion* f, const float* graph_host, int graph_nodes, int timeDeltaEff, hipStream_t s) {
+  StageTimer t(f->clock, s, "clean", f->profiling);
+  return model_clean(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->imap, graph_nodes > 0 ? &f->depth_synth : nullptr, &f->cam,
+                     f->p.confidence, graph_host, graph_nodes, timeDeltaEff, f->p.maxDepthProcessed, 0, 1, &f->state->surfels, s);
 }
 
 static int process_frame_end(dms_fusion* f, const float* graph_host, int graph_nodes, const float* newPose16, dms_stream st, bool one_call) {
@@ -1518,57 +1482,12 @@ static int process_frame_end(dms_fusion* f, const float* graph_host, int graph_n
 
     if (!f->p.rgbOnly && f->tracking_ok && !f->lost && fuse_now) {  // fusion (ElasticFusion.cpp:506-564)
       if (!f->clusters.count(f->req_cluster) && (rc = cluster_initialise(f, f->req_cluster, s))) return rc;  // :508-515
-      // fused_associate: the first index map has one reader, the association, and the second one overwrites its images: it is
-      // projected only, into a z-buffer of its own, the association reads that (k_fuse_associate_zbuf), and the second index
-      // map's resolve pass hands it back empty.  Same bits in the slots, the winners and everything after them.
-      const bool fa = f->p.fused_associate != 0;
-      {
-        FTimer t(f, s, "index_map");
-        if (fa) {
-          const bool stale = f->zbuf_assoc_dirty;  // a frame that set it never reached its clearing resolve: clear here
-          f->zbuf_assoc_dirty = true;
-          rc = index_project(f->model, &f->state->cur, &f->cam, f->tick, f->p.timeIdx, f->p.maxDepthProcessed, timeDeltaEff, f->zbuf_assoc,
-                             stale ? 0 : 1, s);
-        } else {
-          rc = index_map(f->model, &f->state->cur, &f->cam, f->tick, f->p.timeIdx, f->p.maxDepthProcessed, timeDeltaEff, f->zbuf, &f->imap, 1,
-                         1, s);
-        }
-        if (rc) return rc;
-      }
-      {
-        FTimer t(f, s, "fuse");
-        // (update pass: inside the next index map)
-        if (fa)
-          rc = model_fuse_zbuf(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->rgba, &f->depth_metric, &f->depth_metric_filtered,
-                               f->zbuf_assoc, &f->cam, f->p.maxDepthProcessed, 1.f, &f->state->weighting, s, 1);
-        else
-          rc = model_fuse(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->rgba, &f->depth_metric, &f->depth_metric_filtered, &f->imap,
-                          &f->cam, f->p.maxDepthProcessed, 1.f, &f->state->weighting, 1, s, 1);
-        if (rc) return rc;
-      }
-      {
-        FTimer t(f, s, "index_map");
-        const bool hand_back = fa && !f->zbuf_assoc_keep_dirty;
-        if ((rc = index_map(f->model, &f->state->cur, &f->cam, f->tick, f->p.timeIdx, f->p.maxDepthProcessed, timeDeltaEff, f->zbuf,
-                            &f->imap, 1, 1, s, hand_back ? f->zbuf_assoc : nullptr)))
-          return rc;
-        if (hand_back) f->zbuf_assoc_dirty = false;
-      }
-      if (graph_nodes > 0) {
-        // a deformation is a second pose update this frame: predict the depth again to decide whose
-        // time stamps to refresh (ElasticFusion.cpp:541-553; synthesizeDepth leaves `actv` false)
-        FTimer t(f, s, "synth_depth");
-        if ((rc = splat_predict(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, f->p.confidence, f->tick, f->p.timeIdx,
-                                f->tick - timeDeltaEff, 65535, 0, f->zbuf, nullptr, &f->depth_synth, 1, s)))
-          return rc;
-      }
-      {
-        FTimer t(f, s, "clean");
-        if ((rc = model_clean(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->imap, graph_nodes > 0 ? &f->depth_synth : nullptr, &f->cam,
-                              f->p.confidence, graph_host, graph_nodes, timeDeltaEff, f->p.maxDepthProcessed, 0, 1, &f->state->surfels, s)))
-          return rc;
-        surfels_written = true;  // the clean's scan also stores the new count into the result block
-      }
+      if ((rc = index_map_for_fuse(f, timeDeltaEff, s))) return rc;
+      if ((rc = fuse_measurements(f, s))) return rc;
+      if ((rc = index_map_for_clean(f, timeDeltaEff, s))) return rc;
+      if (graph_nodes > 0 && (rc = synthesise_depth(f, timeDeltaEff, s))) return rc;
+      if ((rc = clean_map(f, graph_host, graph_nodes, timeDeltaEff, s))) return rc;
+      surfels_written = true;  // the clean's scan also stores the new count into the result block
       fused = 1;
     }
     f->frames_since_fusion = fuse_now ? 0 : f->frames_since_fusion + 1;  // ElasticFusion.cpp:567-568
@@ -1577,9 +1496,8 @@ static int process_frame_end(dms_fusion* f, const float* graph_host, int graph_n
     hipLaunchKernelGGL(k_frame_end, dim3(1), dim3(64), 0, s, f->state, f->model->d_count);
     DMS_CHECK_LAUNCH();
   }
-  // finalPredict (ElasticFusion.cpp:586); its fill-in kernel mirrors the result block to the host slot
   const int k4 = (int)(f->frames % 4);
-  if ((rc = predict(f, f->p.confidence, s, f->h_state_dev + k4, false, 1, false, nullptr, nullptr, one_call))) return rc;
+  if ((rc = predict_final(f, s, f->h_state_dev + k4, one_call))) return rc;
   f->last_slot = k4;
   DMS_HIP(hipEventRecord(f->ev_main_done[k4], s));  // (also without the pipeline: it gates the reading of this frame's result slot)
   f->fused_last = fused;
@@ -1810,9 +1728,9 @@ int dms_fusion_apply_global_loop_end(dms_fusion* f, const float* graph_host, int
   // predict(context, rf); predictIndices(currPose, tick, id, model, maxDepthProcessed, timeDelta + framesSinceLastFusion);
   // clean(..., rawGraph, timeDelta + framesSinceLastFusion, maxDepthProcessed, orbLoopClosureAccepted) (:1222-1239)
   // (the clean changes the map's version: a projection the previous frame left for the next tracking prediction is stale and
-  // that prediction projects afresh, see predict() mode 2)
+  // that prediction projects afresh, see predict_tracking)
   // in the reference's order: the prediction images a caller reads afterwards show the map BEFORE this clean
-  if ((rc = predict(f, f->p.confidence, s))) return rc;
+  if ((rc = predict_view(f, f->p.confidence, s))) return rc;
   const int timeDeltaEff = f->p.timeDelta + f->frames_since_fusion;
   if ((rc = index_map(f->model, &f->state->cur, &f->cam, f->tick, f->p.timeIdx, f->p.maxDepthProcessed, timeDeltaEff, f->zbuf, &f->imap, 1, 1, s)))
     return rc;
@@ -1878,7 +1796,7 @@ int dms_fusion_join_map(dms_fusion* f, dms_fusion* owner, const float* relativeT
   hipLaunchKernelGGL(k_pose_override, dim3(1), dim3(64), 0, s, f->state, np);
   DMS_CHECK_LAUNCH();
   // a projection rendered ahead for the next frame (share_projection) is of the map this camera leaves: its keys are surfel
-  // indices of that map.  predict() only clears zbuf2 while pre_valid is set, so clear it here before dropping the flag.
+  // indices of that map.  predict_body only clears zbuf2 while pre_valid is set, so clear it here before dropping the flag.
   if (f->pre_valid && (rc = clear_zbuf(f->zbuf2, f->p.width * f->p.height, s))) return rc;
   f->pre_valid = false;
   if (!founder) f->model->sharers -= 1;  // leaves the map it had joined (that map's founder carries the surfels)
@@ -1946,7 +1864,7 @@ int dms_fusion_debug_keep_assoc_zbuf(dms_fusion* f, int on) {
 int dms_fusion_set_profiling(dms_fusion* f, int enabled) {
   DMS_REQUIRE(f, "null argument");
   f->profiling = enabled != 0;
-  if (enabled) f->times.clear();
+  if (enabled) f->clock.times.clear();
   return DMS_OK;
 }
 
@@ -2034,7 +1952,7 @@ int dms_fusion_predict(dms_fusion* f, float confidence, dms_stream st) {
   DMS_REQUIRE(f, "null argument");
   DMS_REQUIRE(!f->in_frame && !f->in_global_loop, "inside a frame");
   DMS_REQUIRE(f->map_initialised, "no map yet");
-  return predict(f, confidence < 0.f ? f->p.confidence : confidence, (hipStream_t)st);
+  return predict_view(f, confidence < 0.f ? f->p.confidence : confidence, (hipStream_t)st);
 }
 
 int dms_fusion_get_kernel_time(dms_fusion* f, const char* name, double* total_ms, int* launches) {
@@ -2044,9 +1962,9 @@ int dms_fusion_get_kernel_time(dms_fusion* f, const char* name, double* total_ms
     *launches = (int)f->frames;
     return DMS_OK;
   }
-  auto it = f->times.find(name);
-  *total_ms = it == f->times.end() ? 0.0 : it->second.ms;
-  *launches = it == f->times.end() ? 0 : it->second.launches;
+  auto it = f->clock.times.find(name);
+  *total_ms = it == f->clock.times.end() ? 0.0 : it->second.ms;
+  *launches = it == f->clock.times.end() ? 0 : it->second.launches;
   return DMS_OK;
 }
 

@@ -20,6 +20,7 @@
 #include <utility>
 
 #include "surfel.hpp"
+#include "internal.hpp"
 
 namespace dms {
 

@@ -16,29 +16,15 @@
 #include "surfel.hpp"
 #include "fill.hpp"
 #include "internal.hpp"
+#include "host_util.hpp"
 #include "track_init.hpp"
 
 namespace dms {
-int model_flush_pending(dms_model* m, hipStream_t s);  // fusion_fuse.hip: applies a fuse's deferred update pass
 
 // ---------------------------------------------------------------------------------------
 // storage
 // ---------------------------------------------------------------------------------------
-static size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-struct ModelCarver {
-  char* base = nullptr;
-  size_t off = 0;
-  template <typename T>
-  T* take(size_t n) {
-    off = up256(off);
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += n * sizeof(T);
-    return p;
-  }
-};
-
-static void model_layout(dms_model* m, ModelCarver& c) {
+static void model_layout(dms_model* m, Carver& c) {
   for (int b = 0; b < 2; ++b) {
     m->buf[b].pos = c.take<float4>(m->cap);
     m->buf[b].col = c.take<float4>(m->cap);
@@ -79,7 +65,7 @@ int dms_model_create(dms_model** out, size_t capacity, int width, int height) {
   m->height = height;
   m->slot_h = (height + 1) / 2;
   m->slots = ((width + 1) / 2) * m->slot_h;
-  ModelCarver sz;
+  Carver sz;
   model_layout(m, sz);
   m->arena_bytes = up256(sz.off);
   hipError_t e = hipMalloc((void**)&m->arena, m->arena_bytes);
@@ -87,7 +73,7 @@ int dms_model_create(dms_model** out, size_t capacity, int width, int height) {
     delete m;
     return hip_fail(e, "hipMalloc(model)", __FILE__, __LINE__);
   }
-  ModelCarver c;
+  Carver c;
   c.base = m->arena;
   model_layout(m, c);
   e = hipHostMalloc((void**)&m->h_count, 8 * sizeof(unsigned), hipHostMallocDefault);
@@ -706,7 +692,7 @@ __global__ __launch_bounds__(256) void k_records_live_planes(const float* __rest
   if (live) atomicMax(out, live);
 }
 
-int model_consume(dms_model* dst, const dms_model* src, const float* T16, hipStream_t s) {
+static int model_consume(dms_model* dst, const dms_model* src, const float* T16, hipStream_t s) {
   DMS_REQUIRE(dst && src && T16 && dst != src, "bad argument");
   {
     int rc = model_flush_pending(dst, s);
@@ -733,7 +719,7 @@ int model_consume(dms_model* dst, const dms_model* src, const float* T16, hipStr
   return consume_finish(dst, src->count_upper);
 }
 
-int model_consume_records(dms_model* dst, const float* rec_dev, unsigned n, const float* T16, hipStream_t s) {
+static int model_consume_records(dms_model* dst, const float* rec_dev, unsigned n, const float* T16, hipStream_t s) {
   DMS_REQUIRE(dst && T16 && (rec_dev || n == 0), "bad argument");
   if (int rc0 = model_flush_pending(dst, s)) return rc0;
   DMS_REQUIRE(((uintptr_t)rec_dev & 15) == 0, "record buffer must be 16-byte aligned");
@@ -764,7 +750,7 @@ int model_consume_records(dms_model* dst, const float* rec_dev, unsigned n, cons
   return consume_finish(dst, n);
 }
 
-int model_export_records(dms_model* m, float* rec_dev, unsigned max_count, unsigned* count_host, hipStream_t s) {
+static int model_export_records(dms_model* m, float* rec_dev, unsigned max_count, unsigned* count_host, hipStream_t s) {
   DMS_REQUIRE(m && rec_dev && count_host, "null argument");
   if (int rc0 = model_flush_pending(m, s)) return rc0;
   DMS_REQUIRE(((uintptr_t)rec_dev & 15) == 0, "record buffer must be 16-byte aligned");

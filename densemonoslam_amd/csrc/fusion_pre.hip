@@ -2,6 +2,7 @@
 // hole fill-in of the model prediction (G10) and nearest-neighbour resize (G11).
 // All are one-thread-per-pixel streaming kernels over dense row-major images.
 #include "surfel.hpp"
+#include "internal.hpp"
 #include "fill.hpp"
 #include "live_bodies.hpp"
 

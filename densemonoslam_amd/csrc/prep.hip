@@ -3,6 +3,7 @@
 // kernels: one 64-wide wave covers 64 consecutive pixels of a row (coalesced 4-byte or
 // 16-byte accesses per lane); blocks are 64×4 so a 256-thread block spans 4 rows.
 #include "common.hpp"
+#include "internal.hpp"
 #include "pyr_body.hpp"
 #include "live_bodies.hpp"
 #include "fill.hpp"

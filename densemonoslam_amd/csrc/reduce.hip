@@ -5,6 +5,7 @@
 // block then folds the records in fp64 with batched 16-byte loads (common.hpp).  No float
 // atomics: the summation order is fixed by the launch shape, so results are deterministic.
 #include "pixel_ops.hpp"
+#include "internal.hpp"
 
 namespace dms {
 
@@ -146,7 +147,7 @@ static void unpack_se3(const float* host, float* A, float* b) {
     }
 }
 
-MapPtrs make_map_ptrs(const dms_image2d* vc, const dms_image2d* nc, const dms_image2d* vp, const dms_image2d* np) {
+static MapPtrs make_map_ptrs(const dms_image2d* vc, const dms_image2d* nc, const dms_image2d* vp, const dms_image2d* np) {
   MapPtrs m;
   m.vcurr = (const float*)vc->data;
   m.vcurr_pitch = vc->pitch;
@@ -234,7 +235,7 @@ int rgbStep(const dms_image2d* corresImg, float sigma, const dms_image2d* cloud,
   return DMS_OK;
 }
 
-RgbResPtrs make_rgbres_ptrs(const dms_image2d* dIdx, const dms_image2d* dIdy, const dms_image2d* lastDepth,
+static RgbResPtrs make_rgbres_ptrs(const dms_image2d* dIdx, const dms_image2d* dIdy, const dms_image2d* lastDepth,
                             const dms_image2d* nextDepth, const dms_image2d* lastImage, const dms_image2d* nextImage) {
   RgbResPtrs q;
   q.dIdx = (const short*)dIdx->data;

@@ -133,12 +133,6 @@ struct Trace {
   }
 };
 
-std::vector<int> hosted(const dms_session* s) {
-  std::vector<int> v;
-  for (auto& kv : s->cams) v.push_back(kv.first);
-  return v;  // (std::map: ascending)
-}
-
 int sync(dms_stream st) { return dms_stream_sync(st); }
 
 // ---- transport helpers: the session's own one-rank transport, sized messages ----------------------------------------------------

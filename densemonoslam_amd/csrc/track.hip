@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "internal.hpp"
+#include "host_util.hpp"
 #include "pixel_ops.hpp"
 #include "smallmath.hpp"
 #include "gn_scalar.hpp"
@@ -60,12 +61,6 @@ struct Buf {
     i.cols = cols;
     return i;
   }
-};
-
-struct KernelTime {
-  double ms = 0;
-  int launches = 0;
-  std::vector<float> samples;  // per launch, ms (profiling only; "<name>:slow" / ":max" / ":median" of dms_odometry_get_kernel_time)
 };
 
 }  // namespace dms
@@ -154,9 +149,7 @@ struct dms_odometry {
   TrackState* host_state = nullptr;  // pinned
   bool profiling = false;
   bool profiling_level0_only = false;  // dms_odometry_set_profiling(o, 2): one event pair per call, around the level-0 kernel, nothing else perturbed
-  std::map<std::string, KernelTime> times;
-  std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
-  std::vector<hipEvent_t> event_pool;
+  StageClock clock;  // stage times while `profiling` (dms_odometry_get_kernel_time)
 };
 
 namespace dms {
@@ -1725,27 +1718,16 @@ __global__ void k_track_finalize(TrackState* st, int rgb, float* __restrict__ po
 // ---------------------------------------------------------------------------------------
 namespace {
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-struct Carver {
-  size_t off = 0;
-  char* base = nullptr;
-  void* take(size_t bytes) {
-    off = align_up(off, 256);
-    void* p = base ? base + off : nullptr;
-    off += bytes;
-    return p;
-  }
-};
+void carve_buf(Carver& c, Buf& b, int rows, int cols, size_t elem) {
+  b.rows = rows;
+  b.cols = cols;
+  b.pitch = (size_t)cols * elem;
+  b.p = c.take(b.pitch * rows);
+}
 
 void layout(dms_odometry* o, Carver& c) {
   const int W = o->width, H = o->height;
-  auto mk = [&](Buf& b, int rows, int cols, size_t elem) {
-    b.rows = rows;
-    b.cols = cols;
-    b.pitch = (size_t)cols * elem;
-    b.p = c.take(b.pitch * rows);
-  };
+  auto mk = [&](Buf& b, int rows, int cols, size_t elem) { carve_buf(c, b, rows, cols, elem); };
   for (int i = 0; i < DMS_NUM_PYRS; ++i) {
     const int r = H >> i, w = W >> i;
     mk(o->depth_tmp[i], r, w, 2);
@@ -1777,49 +1759,8 @@ void layout(dms_odometry* o, Carver& c) {
   o->state = (TrackState*)c.take(sizeof(TrackState));
 }
 
-struct Timer {
-  dms_odometry* o;
-  hipStream_t s;
-  const char* name;
-  hipEvent_t a = nullptr, b = nullptr;
-  bool on() const { return o->profiling && (!o->profiling_level0_only || strcmp(name, "gn_level0") == 0); }
-  Timer(dms_odometry* o_, hipStream_t s_, const char* n) : o(o_), s(s_), name(n) {
-    if (!on()) return;
-    auto get = [&]() {
-      hipEvent_t e;
-      if (!o->event_pool.empty()) {
-        e = o->event_pool.back();
-        o->event_pool.pop_back();
-      } else {
-        (void)hipEventCreate(&e);
-      }
-      return e;
-    };
-    a = get();
-    b = get();
-    (void)hipEventRecord(a, s);
-  }
-  ~Timer() {
-    if (!on()) return;
-    (void)hipEventRecord(b, s);
-    o->pending.push_back({name, {a, b}});
-  }
-};
-
-void drain_timers(dms_odometry* o) {
-  for (auto& p : o->pending) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, p.second.first, p.second.second) == hipSuccess) {
-      KernelTime& t = o->times[p.first];
-      t.ms += ms;
-      t.launches += 1;
-      if (t.samples.size() < 100000) t.samples.push_back(ms);
-    }
-    o->event_pool.push_back(p.second.first);
-    o->event_pool.push_back(p.second.second);
-  }
-  o->pending.clear();
-}
+// whether a stage of this call is timed (dms_odometry_set_profiling: 1 = every stage, 2 = the level-0 kernel only)
+bool timed(const dms_odometry* o, bool level0 = false) { return o->profiling && (level0 || !o->profiling_level0_only); }
 
 // minimum squared gradient of level l (RGBDOdometry.cpp:287-291 / :453)
 float rgb_min_scale(const dms_odometry* o, int l) { return (float)(pow((double)o->minGrad[l], 2.0) / pow((double)o->sobelScale, 2.0)); }
@@ -1892,7 +1833,7 @@ int dms_odometry_create(dms_odometry** out, int width, int height, float cx, flo
   o->minGrad[2] = 1;
   Carver sz;
   layout(o, sz);
-  o->arena_bytes = align_up(sz.off, 256);
+  o->arena_bytes = up256(sz.off);
   hipError_t e = hipMalloc((void**)&o->arena, o->arena_bytes);
   if (e != hipSuccess) {
     delete o;
@@ -2088,8 +2029,6 @@ int dms_odometry_fall_back_to_launches(dms_odometry* o) {
 
 int dms_odometry_destroy(dms_odometry* o) {
   if (!o) return DMS_OK;
-  drain_timers(o);
-  for (auto e : o->event_pool) (void)hipEventDestroy(e);
   if (o->arena) (void)hipFree(o->arena);
   if (o->ring_arena) (void)hipFree(o->ring_arena);
   if (o->host_state) (void)hipHostFree(o->host_state);
@@ -2193,20 +2132,6 @@ int dms_odometry_initFirstRGB(dms_odometry* o, const dms_image2d* rgba, dms_stre
   }
   return DMS_OK;
 }
-
-}  // extern "C"
-
-namespace dms {
-struct TrackFold {  // the track call a model pyramid launch prepares (odometry_initModel_fused)
-  const float* prior_pose16;
-  int pyramid, fastOdom, so3, interMap;
-};
-int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot, const float* prior_pose16_dev, int rgbOnly,
-                           float icpWeight, int pyramid, int fastOdom, int so3, int interMap, hipStream_t s, FrameState* frame = nullptr,
-                           float weightMultiplier = 1.f);
-}
-
-extern "C" {
 
 int dms_odometry_track_async(dms_odometry* o, const float* trans, const float* rot, int rgbOnly, float icpWeight, int pyramid,
                              int fastOdom, int so3, int interMap, dms_stream st) {
@@ -2477,7 +2402,7 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
       ex.idst = view<unsigned char>(&i2);
     }
   } else {
-    Timer t(o, s, "track_init");
+    StageTimer t(o->clock, s, "track_init", timed(o));
     // all-reduce words of the call's resident kernels (resident mode only)
     const int zero_pairs = o->resident ? (int)((size_t)kArSets * kArWords / 2) : 0;
     const int ni = o->resident ? 16 : 1;
@@ -2613,7 +2538,7 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
     F.rider_target = o->rider_issued;
     ex.nb_so3 = cnb;
     persist.begin();
-    Timer t(o, s, "track_coarse");
+    StageTimer t(o->clock, s, "track_coarse", timed(o));
     const bool ee = F.L1.early_exit != 0;
     if (icp && rgb)
       launch_track_coarse<true, true>(cP1, ee, cnb + ex.gx * ex.gy, s, o->state, F, ex);
@@ -2630,7 +2555,7 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
     const int nbp = so3_resident_blocks(o);
     if (nbp > 0) {
       persist.begin();
-      Timer t(o, s, "so3_level");
+      StageTimer t(o->clock, s, "so3_level", timed(o));
       SolveCam cam = {o->fx, o->fy, o->cx, o->cy};
       ex.nb_so3 = nbp;
       hipLaunchKernelGGL(k_so3_level, dim3(nbp + ex.gx * ex.gy), dim3(kPB), 0, s, o->state, (const unsigned char*)li.p, li.pitch,
@@ -2639,7 +2564,7 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
     } else
     for (int i = 0; i < 10; ++i) {
       {
-        Timer t(o, s, "so3_pass");
+        StageTimer t(o->clock, s, "so3_pass", timed(o));
         SolveCam cam = {o->fx, o->fy, o->cx, o->cy};
         hipLaunchKernelGGL(k_so3_pass, dim3(nb), dim3(kBlock), 0, s, o->state, (const unsigned char*)li.p, li.pitch,
                            (const unsigned char*)ni.p, ni.pitch, ni.cols, ni.rows, o->part_so3, o->tickets, cam, i, i == 9 ? 1 : 0, first_level,
@@ -2673,7 +2598,7 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
       if (l == 0) finalized_in_kernel = true;
       persist.begin();
       static const char* const kLevelTimer[3] = {"gn_level0", "gn_level1", "gn_level2"};
-      Timer t(o, s, kLevelTimer[l]);
+      StageTimer t(o->clock, s, kLevelTimer[l], timed(o, l == 0));
       hipEvent_t done = (l == 0) ? persist.closing_event() : nullptr;  // level 0 is the section's last resident launch
       if (icp && rgb)
         launch_gn_level<true, true>(pP, pnb, s, o->state, a, L, done);
@@ -2700,7 +2625,7 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
       q.cx = o->cx;
       q.cy = o->cy;
       {
-        Timer t(o, s, "gn_pass1");
+        StageTimer t(o->clock, s, "gn_pass1", timed(o));
         if (icp && rgb)
           hipLaunchKernelGGL((k_gn_pass1<true, true>), dim3(nb), dim3(kBlock), 0, s, o->state, a, o->part_icp, o->part_cnt, kMaxPartialBlocks, j == 0 ? 1 : 0);
         else if (icp)
@@ -2710,12 +2635,12 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
         DMS_CHECK_LAUNCH();
       }
       if (rgb) {
-        Timer t(o, s, "gn_pass2");
+        StageTimer t(o->clock, s, "gn_pass2", timed(o));
         hipLaunchKernelGGL(k_gn_pass2, dim3(nb), dim3(kBlock), 0, s, o->state, a, o->part_cnt, nb, kMaxPartialBlocks, j == 0 ? 1 : 0, o->part_rgb);
         DMS_CHECK_LAUNCH();
       }
       {
-        Timer t(o, s, "gn_solve");
+        StageTimer t(o->clock, s, "gn_solve", timed(o));
         if (icp && rgb)
           hipLaunchKernelGGL((k_gn_solve<true, true>), dim3(1), dim3(kBlock), 0, s, o->state, a, o->part_icp, o->part_rgb, o->part_cnt, kMaxPartialBlocks, nb, q);
         else if (icp)
@@ -2731,7 +2656,7 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
     DMS_HIP(hipMemsetAsync(first_gn_zero16, 0, 16 * 16 * sizeof(unsigned), s));  // (the 16 counters, 64 bytes apart)
   }
   if (!finalized_in_kernel) {
-    Timer t(o, s, "track_finalize");
+    StageTimer t(o->clock, s, "track_finalize", timed(o));
     // frame step (frame state given): the result is written back into the pose block the prior came from;
     // a device prior without frame state (model-to-model tracking) is read-only
     hipLaunchKernelGGL(k_track_finalize, dim3(1), dim3(64), 0, s, o->state, rgb ? 1 : 0,
@@ -2882,9 +2807,6 @@ int odometry_loop_candidate(dms_odometry* o, FrameState* frame, const dms_image2
   return DMS_OK;
 }
 
-int selectCopy16(void* dst, const void* a, const void* b, const int* flag_dev, int force_b, size_t n16, hipStream_t s);
-int transformMapsDev(dms_image2d* v, dms_image2d* n, const float* pose16_dev, hipStream_t s);
-
 // ---- live-frame ring (see dms_odometry::LiveSet) ----
 void odometry_set_early_exit(dms_odometry* o, int on) { o->early_exit = on != 0; }
 
@@ -2919,12 +2841,7 @@ int odometry_enable_ring(dms_odometry* o) {
     Carver c;
     c.base = pass ? o->ring_arena : nullptr;
     const int W = o->width, H = o->height;
-    auto mk = [&](Buf& b, int rows, int cols, size_t elem) {
-      b.rows = rows;
-      b.cols = cols;
-      b.pitch = (size_t)cols * elem;
-      b.p = c.take(b.pitch * rows);
-    };
+    auto mk = [&](Buf& b, int rows, int cols, size_t elem) { carve_buf(c, b, rows, cols, elem); };
     for (int k = 1; k < 3; ++k)
       for (int i = 0; i < DMS_NUM_PYRS; ++i) {
         const int r = H >> i, w = W >> i;
@@ -2937,7 +2854,7 @@ int odometry_enable_ring(dms_odometry* o) {
         mk(o->ring[k].nextGate[i], r, w, 1);
       }
     if (!pass) {
-      const size_t bytes = align_up(c.off, 256);
+      const size_t bytes = up256(c.off);
       hipError_t e = hipMalloc((void**)&o->ring_arena, bytes);
       if (e == hipSuccess) e = hipMemset(o->ring_arena, 0, bytes);
       if (e != hipSuccess) return hip_fail(e, "hipMalloc(live ring)", __FILE__, __LINE__);
@@ -3139,7 +3056,7 @@ int odometry_initModel_fused(dms_odometry* o, const void* vA, const void* nA, co
                        o->folded_first_level, 10, o->exp_bias + o->depth_bias, o->first_delay_for(nbs, 3)};
     PersistSection persist(s, budget_of(o), o->unchained_ok);
     persist.begin();
-    Timer t(o, s, "so3_model");
+    StageTimer t(o->clock, s, "so3_model", timed(o));
     hipLaunchKernelGGL(k_so3_model, dim3(nbs + G.g12x * G.g12y + G.gsx * G.gsy + G.g2x * G.g2y + G.g0x * G.g0y), dim3(kPB), 0, s, o->state, q, nbs, G);
     DMS_CHECK_LAUNCH();
     return DMS_OK;
@@ -3165,42 +3082,6 @@ int odometry_initLive_fused(dms_odometry* o, const void* verts, const void* norm
   return nextDerivatives(o, s);
 }
 
-// initICPModel with the source chosen on device: (*flag ? fill-in maps : predicted maps), pose read from HBM
-int odometry_initICPModel_sel(dms_odometry* o, const float* vA, const float* nA, const float* vB, const float* nB, const int* flag_dev,
-                              const float* pose16_dev, hipStream_t s) {
-  const size_t n16 = (size_t)o->width * o->height;
-  int rc;
-  if ((rc = selectCopy16(o->vmaps_tmp, vA, vB, flag_dev, 0, n16, s))) return rc;
-  if ((rc = selectCopy16(o->nmaps_tmp, nA, nB, flag_dev, 0, n16, s))) return rc;
-  dms_image2d v0 = o->vmaps_g_prev[0].img(), n0 = o->nmaps_g_prev[0].img();
-  if ((rc = copyMaps(o->vmaps_tmp, o->nmaps_tmp, &v0, &n0, s))) return rc;
-  for (int i = 1; i < DMS_NUM_PYRS; ++i) {
-    dms_image2d va = o->vmaps_g_prev[i - 1].img(), vb = o->vmaps_g_prev[i].img();
-    dms_image2d na = o->nmaps_g_prev[i - 1].img(), nb = o->nmaps_g_prev[i].img();
-    if ((rc = resizeMap(&va, &vb, false, s))) return rc;
-    if ((rc = resizeMap(&na, &nb, true, s))) return rc;
-  }
-  for (int i = 0; i < DMS_NUM_PYRS; ++i) {
-    dms_image2d v = o->vmaps_g_prev[i].img(), n = o->nmaps_g_prev[i].img();
-    if ((rc = transformMapsDev(&v, &n, pose16_dev, s))) return rc;
-  }
-  return DMS_OK;
-}
-
-// initRGBModel with the image chosen on device; rgba_tmp: W*H*4-byte scratch
-int odometry_initRGBModel_sel(dms_odometry* o, const void* rgbaA, const void* rgbaB, const int* flag_dev, int force_b, void* rgba_tmp,
-                              hipStream_t s) {
-  const size_t n16 = ((size_t)o->width * o->height + 3) / 4;  // 4 pixels per 16 bytes (buffers are padded to 16 B)
-  int rc;
-  if ((rc = selectCopy16(rgba_tmp, rgbaA, rgbaB, flag_dev, force_b, n16, s))) return rc;
-  dms_image2d img;
-  img.data = rgba_tmp;
-  img.pitch = (size_t)o->width * 4;
-  img.rows = o->height;
-  img.cols = o->width;
-  return populateRGBDData(o, &img, o->lastDepth, o->lastImage, s);
-}
-
 }  // namespace dms
 
 extern "C" {
@@ -3216,7 +3097,7 @@ int dms_odometry_fetch_result(dms_odometry* o, dms_track_result* r, dms_stream s
   DMS_REQUIRE(o && r, "null argument");
   DMS_HIP(hipMemcpyAsync(o->host_state, o->state, sizeof(TrackState), hipMemcpyDeviceToHost, (hipStream_t)st));
   DMS_HIP(hipStreamSynchronize((hipStream_t)st));
-  drain_timers(o);
+  o->clock.drain();
   const TrackState* h = o->host_state;
   memcpy(r->trans, h->out_trans, sizeof(r->trans));
   memcpy(r->rot, h->out_rot, sizeof(r->rot));
@@ -3341,8 +3222,8 @@ int dms_odometry_set_profiling(dms_odometry* o, int enabled) {
   o->profiling = enabled != 0;
   o->profiling_level0_only = enabled == 2;
   if (enabled) {
-    drain_timers(o);
-    o->times.clear();
+    o->clock.drain();
+    o->clock.times.clear();
     DMS_HIP(hipDeviceSynchronize());  // (the phase clocks are accumulated by the resident kernels)
     DMS_HIP(hipMemset(o->prof, 0, (3 * 16 + 256 * 8) * 8));
   }
@@ -3364,10 +3245,10 @@ int dms_odometry_get_kernel_time(dms_odometry* o, const char* name, double* tota
   {  // "<kernel>:median" / ":max" (ms) and ":slow" (launches = how many took more than 1.5 x the median)
     const char* colon = strchr(name, ':');
     if (colon) {
-      auto it2 = o->times.find(std::string(name, colon - name));
+      auto it2 = o->clock.times.find(std::string(name, colon - name));
       *total_ms = 0;
       *launches = 0;
-      if (it2 == o->times.end() || it2->second.samples.empty()) return DMS_OK;
+      if (it2 == o->clock.times.end() || it2->second.samples.empty()) return DMS_OK;
       std::vector<float> v = it2->second.samples;
       std::sort(v.begin(), v.end());
       const float med = v[v.size() / 2];
@@ -3388,8 +3269,8 @@ int dms_odometry_get_kernel_time(dms_odometry* o, const char* name, double* tota
       return DMS_OK;
     }
   }
-  auto it = o->times.find(name);
-  if (it == o->times.end()) {
+  auto it = o->clock.times.find(name);
+  if (it == o->clock.times.end()) {
     *total_ms = 0;
     *launches = 0;
     return DMS_OK;
