@@ -455,6 +455,12 @@ class ElasticFusionT {
   float kFThreshold() { return scheme == NID_KEYFRAMING ? nid_threshold : 0.f; }
   int& numFused(Context& context) { return context.numFused(); }
   const int& getDeforms() { return deforms; }
+  // opt-in: local loops are closed inside the library (Deformation::constrain on the GPU, dmslam_deform.h) instead of by the
+  // `constrain` callback; frames that carry an ORB loop keep the two-phase path.  closeLoops alone keeps the callback's behaviour.
+  void setLoopSolver(bool on = true, int sampleRate = 5000) {
+    loopSolver_ = on;
+    loopSolverRate_ = sampleRate;
+  }
   const int& getFernDeforms() { return fernDeforms; }
   int surfelCount() {  // ElasticFusion.cpp:1107-1116
     int count = 0;
@@ -504,7 +510,14 @@ class ElasticFusionT {
       flat(*orbTcwNew, pn);
       check(dms_fusion_set_orb_loop(context.fusion, po, pn), "set_orb_loop");
     }
-    if (orb || closeLoops) {
+    // Only a caller who opted in ever touches the switch.  A frame that carries an ORB loop keeps the two-phase path: the switch is off
+    // for it.  Mixed use has one caveat: lastDeformTime lives in whichever solver closed the loop - the library's for solver frames,
+    // the caller's for callback frames - and neither learns of the other's deformations.
+    const bool solver = loopSolver_ && closeLoops && !orb;
+    if (loopSolver_ && closeLoops)
+      check(dms_fusion_set_loop_solver(context.fusion, solver ? 1 : 0, loopSolverRate_), "dms_fusion_set_loop_solver");
+    const int libDeformsBefore = solver ? dms_fusion_get_deforms(context.fusion) : 0;
+    if (orb || (closeLoops && !solver)) {
       // the frame step in two halves around the caller's deformation solver (ElasticFusion.cpp:337 / :481)
       check(dms_fusion_process_frame_begin(context.fusion, context.rgb_dev, 3, (const unsigned short*)context.depth_dev, inPose ? prior : nullptr,
                                            weightMultiplier, nullptr),
@@ -548,6 +561,7 @@ class ElasticFusionT {
       check(dms_fusion_process_frame(context.fusion, context.rgb_dev, 3, (const unsigned short*)context.depth_dev, inPose ? prior : nullptr,
                                      weightMultiplier, nullptr),
             "processFrame");
+      if (solver) deforms += dms_fusion_get_deforms(context.fusion) - libDeformsBefore;  // :485, beside the callback frames' count
     }
     refresh(context);
     // :571-574 (the tick the frame was processed at; the pose after tracking / loop closure)
@@ -689,6 +703,8 @@ class ElasticFusionT {
 
   const int timeDelta;
   const bool closeLoops, iclnuim, reloc;
+  bool loopSolver_ = false;
+  int loopSolverRate_ = 5000;
   float confidence, depthCut, icpThresh;  // (changed by the setters below)
   bool fastOdom, so3, frameToFrameRGB;
   bool rgbOnly = false;  // ElasticFusion::setRgbOnly (:1023): every camera tracks photometrically only and fuses nothing

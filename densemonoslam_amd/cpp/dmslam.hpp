@@ -20,9 +20,11 @@
 #include <stdexcept>
 #include <string>
 #include <tuple>
+#include <utility>
 #include <vector>
 
 #include "../../include/dmslam.h"
+#include "../../include/dmslam_deform.h"
 #include "../../include/dmslam_ferns.h"
 #include "../../include/dmslam_fusion.h"
 #include "../../include/dmslam_render.h"
@@ -494,7 +496,66 @@ class ElasticFusion {
     check(dms_fusion_process_frame_end(h, rawGraph, nodes, newPose, s), "processFrameEnd");
   }
   GlobalModel getGlobalModel() { return GlobalModel(dms_fusion_model(h)); }
+  // the frame step closes its local loops itself: Deformation::constrain on the GPU (dmslam_deform.h)
+  void setLoopSolver(bool on = true, int sampleRate = 5000) { check(dms_fusion_set_loop_solver(h, on ? 1 : 0, sampleRate), "setLoopSolver"); }
+  int getDeforms() { return dms_fusion_get_deforms(h); }
+  dms_deform* localDeformation() { return dms_fusion_deformation(h); }
+  std::vector<float> relativeConstraints() {
+    int n = 0;
+    check(dms_fusion_get_relative_constraints(h, nullptr, 0, &n), "relativeConstraints");
+    std::vector<float> rows((size_t)n * 8);
+    check(dms_fusion_get_relative_constraints(h, rows.data(), n, &n), "relativeConstraints");
+    return rows;
+  }
   dms_fusion* h = nullptr;
+};
+
+// Deformation (Core/src/Deformation.h) for absolute and pin constraints, fernMatch = false: the solver of dmslam_deform.h
+class DeformationSolver {
+ public:
+  DeformationSolver(int maxNodes = DMS_DEFORM_MAX_NODES, int maxConstraints = DMS_DEFORM_MAX_CONSTRAINTS) {
+    check(dms_deform_create(&h, maxNodes, maxConstraints), "DeformationSolver");
+  }
+  ~DeformationSolver() { dms_deform_destroy(h); }
+  DeformationSolver(const DeformationSolver&) = delete;
+  DeformationSolver& operator=(const DeformationSolver&) = delete;
+  void setNodes(const float* rows4_dev, int n, dms_stream s = nullptr) { check(dms_deform_set_nodes(h, rows4_dev, n, s), "setNodes"); }
+  void sampleGraphModel(GlobalModel& model, int sampleRate = 5000, dms_stream s = nullptr) {
+    check(dms_deform_sample_model(h, model.h, sampleRate, s), "sampleGraphModel");
+  }
+  void addConstraints(const float* rows7_dev, int n, int srcTime, bool pinConstraints, dms_stream s = nullptr) {
+    check(dms_deform_add_constraints(h, rows7_dev, n, srcTime, pinConstraints ? 1 : 0, 0, s), "addConstraints");
+  }
+  void clearConstraints() { check(dms_deform_clear_constraints(h), "clearConstraints"); }
+  // enqueues the solve; result() waits for it (result().applied = the reference's return value)
+  void constrain(int time, bool relaxGraph = false, dms_stream s = nullptr) { check(dms_deform_constrain(h, time, relaxGraph ? 1 : 0, s), "constrain"); }
+  dms_deform_result result() {
+    dms_deform_result r;
+    check(dms_deform_get_result(h, &r), "result");
+    return r;
+  }
+  // the 16-float node table in device memory and the device word that holds the node count
+  std::pair<const float*, const int*> graphDevice() {
+    const float* t = nullptr;
+    const int* n = nullptr;
+    check(dms_deform_graph_device(h, &t, &n), "graphDevice");
+    return std::make_pair(t, n);
+  }
+  // newRelativeCons of the last applied solve: rows {deformed source xyz, target xyz, source time, target time}
+  std::vector<float> relativeConstraints() {
+    int n = 0;
+    check(dms_deform_get_relative_constraints(h, nullptr, 0, &n), "relativeConstraints");
+    std::vector<float> rows((size_t)n * 8);
+    check(dms_deform_get_relative_constraints(h, rows.data(), n, &n), "relativeConstraints");
+    return rows;
+  }
+  void setLastDeformTime(long long t) { check(dms_deform_set_last_deform_time(h, t), "setLastDeformTime"); }
+  long long lastDeformTime() {
+    long long t = 0;
+    check(dms_deform_last_deform_time(h, &t), "lastDeformTime");
+    return t;
+  }
+  dms_deform* h = nullptr;
 };
 
 }  // namespace dms

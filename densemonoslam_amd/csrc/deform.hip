@@ -1,0 +1,1133 @@
+// The deformation-graph solver of include/dmslam_deform.h: Deformation::constrain with DeformationGraph::optimiseGraphSparse for
+// absolute and pin constraints (fernMatch = false) on the GPU.  Row and weight arithmetic: deform_rows.hpp (shared with the host
+// build the CPU tests compare against tests/deform_ref.py).
+//
+// One solve is a fixed sequence of launches on the caller's stream; the host reads nothing in between.  A status block in device
+// memory carries the loop state: once an exit test of DeformationGraph.cpp:515 fires (or the system is singular) it sets `done`
+// and the kernels of the remaining iterations return at once.
+//
+//   weights    one vertex per lane: node search, 20 distances, stable sort, four weights, the constraint-row coefficients
+//   setup      one block: the enabled suffix, row and non-zero offsets of every edge and constraint (exclusive scan)
+//   residual   one lane per rotation block / edge / constraint, in the reference's row order; the constraint distances
+//   norms      one block: squared residual norm, delta.norm() (256 strided partial sums + pairwise fold: the order the restatement
+//              fixes), meanConsErr (a sequential float sum, as the reference's), the exit tests
+//   jacobian   the first iteration's Jacobian as CSR (for the staged tests; the assembly below never reads it)
+//   assemble   one block per enabled node = block row of A = J^T J in block-band storage (12 x 12 blocks, the diagonal block and the
+//              19 to its left).  The rows of regularisation and constraints never change over the iterations (their entries hold
+//              positions and weights only), so that part is built once; per iteration the rotation rows' 9 x 9 is added and
+//              g = -J^T r formed.  Every entry is one thread's sum in a fixed order: no atomics.
+//   solve      ONE workgroup of 1024 threads: right-looking banded block Cholesky in place (diagonal block and forward substitution
+//              in one wave by lane shuffles, panel of up to 19 blocks one row per thread, trailing update of up to 190 blocks from
+//              the panel held in LDS), then the backward substitution.  The problem is at most 2048 block columns (2047 in the frame step) and strictly
+//              sequential in them; what counts is the latency of a column step, not throughput, so it stays on one CU with block
+//              barriers rather than paying grid barriers.
+//   apply      applyDeltaSparse (float += double), then residual and norms again
+//   finalize   graph reset if singular, node table, newRelativeCons rows, lastDeformTime
+#include "../../include/dmslam_deform.h"
+#include "deform_rows.hpp"
+#include "host_util.hpp"
+#include "internal.hpp"
+#include "surfel.hpp"
+
+namespace dms {
+namespace {
+using namespace dr;
+
+constexpr int BW = HALF_BAND_BLOCKS;   // 19
+constexpr int NBLK = BW + 1;           // blocks stored per block row: columns i-19 .. i
+constexpr int ROWLEN = NBLK * NVAR;    // 240 doubles per scalar row
+constexpr int BLK = NVAR * NVAR;       // 144
+constexpr int NPAIR = BW * (BW + 1) / 2;
+constexpr int GROUPS = 21;             // 21 * 12 = 252 lanes of a 256-block share the constraint sum of g
+
+struct Hdr {
+  int n_nodes, initialised;
+  int e0, E;  // first enabled node, number of enabled nodes
+  int n_rows, nnz;
+  int done, status, iterations, exit_reason, applied, optimised;
+  int n_rel, n_pool;
+  float error, error0, mce_before, mce_after;
+  double last_error;
+  double iter_err[3], iter_dn[3];
+  long long last_deform;
+};
+
+struct Dev {
+  Hdr* h;
+  float *nodes4, *rot, *trans, *table, *raw4;
+  float *src, *tgt, *ttime;
+  int *vtime, *rel_idx;
+  int* ids;
+  double *w, *coef;
+  float *pos, *cnorm;
+  int *edge_row, *edge_nz, *con_row, *con_nz;
+  double *resid, *resid0;
+  int *indptr, *jcols;
+  double* jvals;
+  double *Ac, *Ab, *g, *diag0, *delta, *delta0;
+  float* rel;
+  int capN, capP;
+};
+
+__device__ __forceinline__ void identity_node(const Dev& d, int i) {
+  for (int q = 0; q < 9; ++q) d.rot[9 * i + q] = (q % 4 == 0) ? 1.f : 0.f;
+  for (int q = 0; q < 3; ++q) d.trans[3 * i + q] = 0.f;
+}
+
+__global__ __launch_bounds__(256) void k_set_nodes(Dev d, const float* __restrict__ rows4, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) {
+    d.h->n_nodes = n;
+    d.h->initialised = 1;
+  }
+  if (i >= n) return;
+  for (int q = 0; q < 4; ++q) d.nodes4[4 * i + q] = rows4[4 * i + q];
+  identity_node(d, i);
+}
+
+// Deformation::sampleGraphModel (Deformation.cpp:250-348): every rate-th surfel, at most capN (the buffer's end), then the stable rank
+// sort by init time of fusion_map.hip's k_graph_rank; the graph is replaced only when more than K samples came (:311)
+__device__ __forceinline__ int sample_count(unsigned M, int rate, int cap) {
+  const unsigned n = (M + (unsigned)rate - 1u) / (unsigned)rate;
+  return n < (unsigned)cap ? (int)n : cap;
+}
+__global__ __launch_bounds__(256) void k_sample(SurfelPlanes src, const unsigned* __restrict__ d_count, int rate, Dev d) {
+  const int n = sample_count(d_count[0], rate, d.capN);
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const size_t id = (size_t)i * (size_t)rate;
+  const float4 p = src.pos[id];
+  d.raw4[4 * i] = p.x;
+  d.raw4[4 * i + 1] = p.y;
+  d.raw4[4 * i + 2] = p.z;
+  d.raw4[4 * i + 3] = src.col[id].z;
+}
+__global__ __launch_bounds__(256) void k_rank(const unsigned* __restrict__ d_count, int rate, Dev d) {
+  const int n = sample_count(d_count[0], rate, d.capN);
+  if (n <= K) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) {
+    d.h->n_nodes = n;
+    d.h->initialised = 1;
+  }
+  if (i >= n) return;
+  const float ti = d.raw4[4 * i + 3];
+  int rank = 0;
+  for (int j = 0; j < n; ++j) {
+    const float tj = d.raw4[4 * j + 3];
+    rank += (tj < ti || (tj == ti && j < i)) ? 1 : 0;
+  }
+  for (int q = 0; q < 4; ++q) d.nodes4[4 * rank + q] = d.raw4[4 * i + q];
+  identity_node(d, rank);
+}
+
+// Deformation::addConstraint (Deformation.cpp:76-89): the pool vertex of each row's source and, with pin, of its pin behind it
+__global__ __launch_bounds__(256) void k_add(Dev d, const float* __restrict__ rows, int stride, int n, int base_v, int base_rel, int srcTime, int pin) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= n) return;
+  const float* r = rows + (size_t)stride * c;
+  const int v = base_v + (pin ? 2 * c : c);
+  for (int q = 0; q < 3; ++q) {
+    d.src[3 * v + q] = r[q];
+    d.tgt[3 * v + q] = r[3 + q];
+  }
+  d.vtime[v] = srcTime;
+  d.ttime[v] = r[6];
+  d.rel_idx[v] = base_rel + c;
+  if (pin) {
+    for (int q = 0; q < 3; ++q) {
+      d.src[3 * (v + 1) + q] = r[3 + q];
+      d.tgt[3 * (v + 1) + q] = r[3 + q];
+    }
+    d.vtime[v + 1] = (int)r[6];
+    d.ttime[v + 1] = r[6];
+    d.rel_idx[v + 1] = -1;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_weights(Dev d, int P) {
+  const Hdr* h = d.h;
+  if (!h->initialised) return;
+  const int v = blockIdx.x * 64 + threadIdx.x;
+  if (v >= P) return;
+  int ids[K];
+  double w[K];
+  weigh_vertex(d.nodes4, h->n_nodes, d.src + 3 * v, (long long)d.vtime[v], ids, w);
+  for (int i = 0; i < K; ++i) {
+    d.ids[K * v + i] = ids[i];
+    d.w[K * v + i] = w[i];
+    con_coeffs(d.src + 3 * v, d.nodes4 + 4 * ids[i], w[i], d.coef + 16 * v + 4 * i);
+  }
+}
+
+// rows (high word) and non-zeros (low word) of item idx: the 4 N edges in (node, slot) order, then the P constraints
+__device__ __forceinline__ unsigned long long item_size(const Dev& d, int idx, int N, int e0) {
+  if (idx < 4 * N) {
+    const int j = idx / 4, nb = neighbour(j, N, idx % 4);
+    if (j < e0 && nb < e0) return 0ull;
+    return ((unsigned long long)REG_ROWS << 32) | (unsigned)(REG_ROWS * ((j >= e0 ? 4 : 0) + (nb >= e0 ? 1 : 0)));
+  }
+  const int* id = d.ids + K * (idx - 4 * N);
+  int cnt = 0;
+  for (int i = 0; i < K; ++i) cnt += id[i] >= e0 ? 1 : 0;
+  return cnt ? (((unsigned long long)CON_ROWS << 32) | (unsigned)(CON_ROWS * 4 * cnt)) : 0ull;
+}
+
+__global__ __launch_bounds__(1024) void k_setup(Dev d, int P, int relax) {
+  Hdr* h = d.h;
+  const int t = threadIdx.x;
+  if (!h->initialised) {
+    if (t == 0) {
+      h->done = 1;
+      h->status = DMS_DEFORM_NO_GRAPH;
+      h->applied = h->optimised = h->iterations = h->exit_reason = 0;
+      h->E = h->e0 = h->n_rows = h->nnz = h->n_rel = 0;
+      h->n_pool = P;
+      h->error = h->error0 = h->mce_before = h->mce_after = 0.f;
+    }
+    return;
+  }
+  __shared__ int s_cnt;
+  __shared__ unsigned long long s_scan[1024];
+  const int N = h->n_nodes;
+  const long long ldt = relax ? 0ll : h->last_deform;
+  if (t == 0) s_cnt = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int i = t; i < N; i += 1024) mine += ((long long)d.nodes4[4 * i + 3] > ldt) ? 0 : 1;  // enabled = time > lastDeformTime (:477)
+  if (mine) atomicAdd(&s_cnt, mine);
+  __syncthreads();
+  const int e0 = s_cnt, E = N - e0;  // times ascend: the enabled nodes are the suffix from e0
+  const int total = 4 * N + P, per = (total + 1023) / 1024;
+  const int lo = min(total, t * per), hi = min(total, lo + per);
+  unsigned long long sum = 0;
+  for (int i = lo; i < hi; ++i) sum += item_size(d, i, N, e0);
+  s_scan[t] = sum;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {
+    const unsigned long long x = t >= off ? s_scan[t - off] : 0ull;
+    __syncthreads();
+    s_scan[t] += x;
+    __syncthreads();
+  }
+  unsigned long long at = s_scan[t] - sum + (((unsigned long long)(ROT_ROWS * E) << 32) | (unsigned)(27 * E));
+  for (int i = lo; i < hi; ++i) {
+    const unsigned long long sz = item_size(d, i, N, e0);
+    int* row = i < 4 * N ? d.edge_row + i : d.con_row + (i - 4 * N);
+    int* nz = i < 4 * N ? d.edge_nz + i : d.con_nz + (i - 4 * N);
+    *row = sz ? (int)(at >> 32) : -1;
+    *nz = (int)(at & 0xffffffffu);
+    at += sz;
+  }
+  if (t == 1023) {
+    const unsigned long long all = s_scan[1023] + (((unsigned long long)(ROT_ROWS * E) << 32) | (unsigned)(27 * E));
+    h->n_rows = (int)(all >> 32);
+    h->nnz = (int)(all & 0xffffffffu);
+  }
+  if (t == 0) {
+    h->e0 = e0;
+    h->E = E;
+    h->done = E == 0 ? 1 : 0;
+    h->status = DMS_DEFORM_OK;
+    h->iterations = 0;
+    h->exit_reason = E == 0 ? DMS_DEFORM_EXIT_NO_ENABLED_NODE : DMS_DEFORM_EXIT_ITERATIONS;
+    h->optimised = 1;
+    h->applied = 0;
+    h->n_rel = 0;
+    h->n_pool = P;
+    for (int i = 0; i < 3; ++i) h->iter_err[i] = h->iter_dn[i] = 0.0;
+  }
+}
+
+// sparseResidual (:842-949): thread idx < capN: the rotation rows of enabled node idx; then 4 capN edges; then P constraints
+__global__ __launch_bounds__(256) void k_residual(Dev d, int P, int respect_done) {
+  const Hdr* h = d.h;
+  if (!h->initialised || (respect_done == 1 && h->done)) return;
+  if (respect_done == 2 && h->status != DMS_DEFORM_SINGULAR) return;  // after the reset of a singular exit: positions and distances anew
+  const int N = h->n_nodes, e0 = h->e0, E = h->E;
+  int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx < d.capN) {
+    if (idx < E) rot_residual(d.rot + 9 * (e0 + idx), d.resid + ROT_ROWS * idx);
+    return;
+  }
+  idx -= d.capN;
+  if (idx < 4 * d.capN) {
+    if (idx >= 4 * N || d.edge_row[idx] < 0) return;
+    const int j = idx / 4, nb = neighbour(j, N, idx % 4);
+    reg_residual(d.rot + 9 * j, d.nodes4 + 4 * j, d.trans + 3 * j, d.nodes4 + 4 * nb, d.trans + 3 * nb, d.resid + d.edge_row[idx]);
+    return;
+  }
+  idx -= 4 * d.capN;
+  if (idx >= P) return;
+  int ids[K];
+  double w[K];
+  for (int i = 0; i < K; ++i) {
+    ids[i] = d.ids[K * idx + i];
+    w[i] = d.w[K * idx + i];
+  }
+  float pos[3];
+  vertex_position(d.nodes4, d.rot, d.trans, d.src + 3 * idx, ids, w, pos);
+  const float* tg = d.tgt + 3 * idx;
+  for (int q = 0; q < 3; ++q) d.pos[3 * idx + q] = pos[q];
+  d.cnorm[idx] = norm3(pos[0] - tg[0], pos[1] - tg[1], pos[2] - tg[2]);  // nonRelativeConstraintError's term (:1021)
+  if (d.con_row[idx] >= 0) con_residual(pos, tg, d.resid + d.con_row[idx]);
+}
+
+// sparseJacobian (:537-840) as CSR, same thread layout
+__global__ __launch_bounds__(256) void k_jacobian(Dev d, int P) {
+  const Hdr* h = d.h;
+  if (!h->initialised || h->done) return;
+  const int N = h->n_nodes, e0 = h->e0, E = h->E;
+  int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx == 0) d.indptr[h->n_rows] = h->nnz;
+  if (idx < d.capN) {
+    if (idx >= E) return;
+    int nz = 27 * idx;
+    for (int r = 0; r < ROT_ROWS; ++r) {
+      int c[6];
+      double v[6];
+      const int m = rot_jacobian(d.rot + 9 * (e0 + idx), r, c, v);
+      d.indptr[ROT_ROWS * idx + r] = nz;
+      for (int i = 0; i < m; ++i) {
+        d.jcols[nz] = idx * NVAR + c[i];
+        d.jvals[nz++] = v[i];
+      }
+    }
+    return;
+  }
+  idx -= d.capN;
+  if (idx < 4 * d.capN) {
+    if (idx >= 4 * N || d.edge_row[idx] < 0) return;
+    const int j = idx / 4, nb = neighbour(j, N, idx % 4);
+    double c4[4];
+    reg_coeffs(d.nodes4 + 4 * j, d.nodes4 + 4 * nb, c4);
+    int nz = d.edge_nz[idx];
+    for (int c = 0; c < 3; ++c) {
+      d.indptr[d.edge_row[idx] + c] = nz;
+      if (nb < j && nb >= e0) {
+        d.jcols[nz] = (nb - e0) * NVAR + 9 + c;
+        d.jvals[nz++] = -c4[3];
+      }
+      if (j >= e0)
+        for (int q = 0; q < 4; ++q) {
+          d.jcols[nz] = (j - e0) * NVAR + 3 * q + c;
+          d.jvals[nz++] = c4[q];
+        }
+      if (nb > j && nb >= e0) {
+        d.jcols[nz] = (nb - e0) * NVAR + 9 + c;
+        d.jvals[nz++] = -c4[3];
+      }
+    }
+    return;
+  }
+  idx -= 4 * d.capN;
+  if (idx >= P || d.con_row[idx] < 0) return;
+  int nz = d.con_nz[idx];
+  for (int c = 0; c < 3; ++c) {
+    d.indptr[d.con_row[idx] + c] = nz;
+    for (int i = 0; i < K; ++i) {
+      const int a = d.ids[K * idx + i];
+      if (a < e0) continue;
+      const double* c4 = d.coef + 16 * idx + 4 * i;
+      for (int q = 0; q < 4; ++q) {
+        d.jcols[nz] = (a - e0) * NVAR + 3 * q + c;
+        d.jvals[nz++] = c4[q];
+      }
+    }
+  }
+}
+
+// The pool vertices that touch node i, compacted in pool order into LDS (256 threads): s_l[c] = the vertex, s_pk[c] = one byte per
+// slot of the vertex: 1 + the block column (0..19, 19 = node i itself) of that slot's node in block row i, 0 where the node is
+// disabled or outside the band.  Two passes around a scan of per-wave counts, so the order does not depend on timing.  Returns the count.
+__device__ __forceinline__ int compact_touching(const Dev& d, int P, int i, int e0, int* s_l, unsigned* s_pk, int* s_w) {
+  const int t = threadIdx.x, wave = t >> 6, lane = t & 63, chunks = (P + 255) / 256;  // P <= 4096: at most 16 chunks
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int c = 0; c < chunks; ++c) {
+      const int l = c * 256 + t;
+      bool touches = false;
+      unsigned pk = 0;
+      if (l < P) {
+        const int* id = d.ids + K * l;
+        for (int k = 0; k < K; ++k) {
+          const int a = id[k], col = a - (i - BW);
+          touches = touches || a == i;
+          if (a >= e0 && col >= 0 && col <= BW) pk |= (unsigned)(col + 1) << (8 * k);
+        }
+      }
+      const unsigned long long m = __ballot(touches);
+      if (pass == 0) {
+        if (lane == 0) s_w[c * 4 + wave] = __popcll(m);
+      } else if (touches) {
+        const int pos = s_w[c * 4 + wave] + __popcll(m & ((1ull << lane) - 1ull));
+        s_l[pos] = l;
+        s_pk[pos] = pk;
+      }
+    }
+    __syncthreads();
+    if (pass == 0) {
+      if (t == 0) {
+        int run = 0;
+        for (int k = 0; k < chunks * 4; ++k) {
+          const int v = s_w[k];
+          s_w[k] = run;
+          run += v;
+        }
+        s_w[64] = run;
+      }
+      __syncthreads();
+    }
+  }
+  return s_w[64];
+}
+// the slot whose byte of pk is v, or -1
+__device__ __forceinline__ int slot_with(unsigned pk, unsigned v) {
+  int s = -1;
+  for (int k = 0; k < K; ++k) s = ((pk >> (8 * k)) & 255u) == v ? k : s;
+  return s;
+}
+
+// The part of A = J^T J that the regularisation and constraint rows give: block row b (node i = e0 + b), blocks (i, i-19 .. i).
+// An entry at unknown p of a node lies in the row of component p % 3, so only entries with p % 3 == q % 3 meet in a row.
+__global__ __launch_bounds__(256) void k_assemble_const(Dev d, int P) {
+  const Hdr* h = d.h;
+  if (!h->initialised || h->done) return;
+  const int b = blockIdx.x;
+  if (b >= h->E) return;
+  const int N = h->n_nodes, e0 = h->e0, i = e0 + b;
+  extern __shared__ int s_dyn[];
+  __shared__ int s_w[65];
+  int* s_l = s_dyn;
+  unsigned* s_pk = (unsigned*)(s_dyn + P);
+  const int cnt = compact_touching(d, P, i, e0, s_l, s_pk, s_w);
+  double* out = d.Ac + (size_t)b * NVAR * ROWLEN;
+  const float* gi = d.nodes4 + 4 * i;
+  for (int e = threadIdx.x; e < NVAR * ROWLEN; e += 256) {
+    const int p = e / ROWLEN, cc = e % ROWLEN, jb = cc / NVAR, q = cc % NVAR;
+    const int jn = i - (BW - jb);
+    double acc = 0.0;
+    if (jn >= e0 && (p % 3) == (q % 3)) {
+      if (jn == i) {
+        for (int s = 0; s < K; ++s) {  // the edges i -> its neighbours
+          double c4[4];
+          reg_coeffs(gi, d.nodes4 + 4 * neighbour(i, N, s), c4);
+          acc += coeff_at(c4, p) * coeff_at(c4, q);
+        }
+        if (p >= 9 && q == p)  // the edges of other nodes (enabled or not) that end in i: -sqrt(wReg) each
+          for (int j2 = max(0, i - K); j2 <= min(N - 1, i + K); ++j2)
+            for (int s = 0; s < K; ++s)
+              if (j2 != i && neighbour(j2, N, s) == i) acc += (-SQRT_WREG) * (-SQRT_WREG);
+      } else if (i - jn <= K) {
+        const float* gj = d.nodes4 + 4 * jn;
+        for (int s = 0; s < K; ++s) {
+          if (q >= 9 && neighbour(i, N, s) == jn) {  // edge i -> jn
+            double c4[4];
+            reg_coeffs(gi, gj, c4);
+            acc += coeff_at(c4, p) * (-c4[3]);
+          }
+          if (p >= 9 && neighbour(jn, N, s) == i) {  // edge jn -> i
+            double c4[4];
+            reg_coeffs(gj, gi, c4);
+            acc += (-c4[3]) * coeff_at(c4, q);
+          }
+        }
+      }
+      for (int c = 0; c < cnt; ++c) {  // the constraints that touch i, in pool order
+        const unsigned pk = s_pk[c];
+        const int t = slot_with(pk, (unsigned)jb + 1u);
+        if (t < 0) continue;
+        const double* cf = d.coef + 16 * s_l[c];
+        acc += coeff_at(cf + 4 * slot_with(pk, BW + 1u), p) * coeff_at(cf + 4 * t, q);
+      }
+    }
+    out[e] = acc;
+  }
+}
+
+// Per iteration: A = the constant part + the rotation rows' J^T J on the diagonal block; g = -J^T r
+__global__ __launch_bounds__(256) void k_iter_assemble(Dev d, int P) {
+  const Hdr* h = d.h;
+  if (!h->initialised || h->done) return;
+  const int b = blockIdx.x;
+  if (b >= h->E) return;
+  const int N = h->n_nodes, e0 = h->e0, i = e0 + b, t = threadIdx.x;
+  __shared__ double s_J[ROT_ROWS][9];
+  __shared__ double s_part[GROUPS][NVAR];
+  extern __shared__ int s_dyn[];
+  __shared__ int s_w[65];
+  int* s_l = s_dyn;
+  unsigned* s_pk = (unsigned*)(s_dyn + P);
+  const int cnt = compact_touching(d, P, i, e0, s_l, s_pk, s_w);
+  if (t < ROT_ROWS) {
+    int c[6];
+    double v[6];
+    for (int q = 0; q < 9; ++q) s_J[t][q] = 0.0;
+    const int m = rot_jacobian(d.rot + 9 * i, t, c, v);
+    for (int k = 0; k < m; ++k) s_J[t][c[k]] = v[k];
+  }
+  __syncthreads();
+  const double* in = d.Ac + (size_t)b * NVAR * ROWLEN;
+  double* out = d.Ab + (size_t)b * NVAR * ROWLEN;
+  for (int e = t; e < NVAR * ROWLEN; e += 256) {
+    const int p = e / ROWLEN, cc = e % ROWLEN, jb = cc / NVAR, q = cc % NVAR;
+    double v = in[e];
+    if (jb == BW && p < 9 && q < 9)
+      for (int r = 0; r < ROT_ROWS; ++r) v += s_J[r][p] * s_J[r][q];
+    out[e] = v;
+    if (jb == BW && p == q) d.diag0[b * NVAR + p] = v;
+  }
+  if (t < GROUPS * NVAR) {
+    const int p = t % NVAR, grp = t / NVAR;
+    double acc = 0.0;
+    for (int c = grp; c < cnt; c += GROUPS) {
+      const int l = s_l[c];
+      acc += coeff_at(d.coef + 16 * l + 4 * slot_with(s_pk[c], BW + 1u), p) * d.resid[d.con_row[l] + p % 3];
+    }
+    s_part[grp][p] = acc;
+  }
+  __syncthreads();
+  if (t < NVAR) {
+    const int p = t;
+    double sum = 0.0;
+    if (p < 9)
+      for (int r = 0; r < ROT_ROWS; ++r) sum += s_J[r][p] * d.resid[ROT_ROWS * b + r];
+    for (int s = 0; s < K; ++s) {
+      double c4[4];
+      reg_coeffs(d.nodes4 + 4 * i, d.nodes4 + 4 * neighbour(i, N, s), c4);
+      sum += coeff_at(c4, p) * d.resid[d.edge_row[4 * i + s] + p % 3];
+    }
+    if (p >= 9)
+      for (int j2 = max(0, i - K); j2 <= min(N - 1, i + K); ++j2)
+        for (int s = 0; s < K; ++s)
+          if (j2 != i && neighbour(j2, N, s) == i) sum += (-SQRT_WREG) * d.resid[d.edge_row[4 * j2 + s] + (p - 9)];
+    for (int grp = 0; grp < GROUPS; ++grp) sum += s_part[grp][p];
+    d.g[b * NVAR + p] = -sum;
+  }
+}
+
+__device__ __forceinline__ double shfl_d(double v, int lane) { return __shfl(v, lane); }
+
+// Banded block Cholesky of Ab in place and both substitutions; delta = A^-1 g.  One workgroup.
+__global__ __launch_bounds__(1024) void k_solve(Dev d) {
+  Hdr* h = d.h;
+  if (!h->initialised || h->done) return;
+  const int E = h->E;
+  __shared__ double s_P[BW * NVAR][NVAR];
+  __shared__ double s_L[NVAR][NVAR];
+  __shared__ double s_y[NVAR];
+  __shared__ double s_red[64][NVAR];
+  __shared__ unsigned char s_pi[NPAIR], s_pj[NPAIR];
+  __shared__ int s_bad;
+  const int t = threadIdx.x, lane = t & 63;
+  if (t < NPAIR) {  // the t-th lower pair (bi >= bj) of the trailing window
+    int bi = 0, rem = t;
+    while (rem > bi) {
+      rem -= bi + 1;
+      ++bi;
+    }
+    s_pi[t] = (unsigned char)bi;
+    s_pj[t] = (unsigned char)rem;
+  }
+  if (t == 0) s_bad = 0;
+  __syncthreads();
+  double* Ab = d.Ab;
+  double* g = d.g;
+  for (int k = 0; k < E; ++k) {
+    const int nb = min(BW, E - 1 - k);
+    double* Dk = Ab + (size_t)k * NVAR * ROWLEN + BW * NVAR;  // the diagonal block: (p, q) at Dk[p * ROWLEN + q]
+    if (t < 64) {
+      // lane r < 12 holds row r of the block; L L^T = D by columns, then L y = g_k
+      const int r = lane < NVAR ? lane : 0;
+      double row[NVAR];
+#pragma unroll
+      for (int q = 0; q < NVAR; ++q) row[q] = Dk[r * ROWLEN + q];
+      double self = 1.0;
+      bool bad = false;
+#pragma unroll
+      for (int c = 0; c < NVAR; ++c) {
+        const double dcc = shfl_d(row[c], c);
+        // a pivot at or below 2^-40 of its diagonal entry (NaN included) holds no bit worth dividing by: singular
+        if (!(dcc > 0x1p-40 * d.diag0[k * NVAR + c])) bad = true;
+        const double dd = sqrt(dcc);
+        const double lc = lane == c ? dd : row[c] / dd;
+        row[c] = lc;
+        if (lane == c) self = dd;
+#pragma unroll
+        for (int q = c + 1; q < NVAR; ++q) {
+          const double lqc = shfl_d(lc, q);
+          row[q] -= lc * lqc;  // used by lanes >= q only
+        }
+      }
+      const double gr = g[k * NVAR + r];
+      double acc = 0.0, yv = 0.0;
+#pragma unroll
+      for (int c = 0; c < NVAR; ++c) {
+        const double yc = shfl_d((gr - acc) / self, c);
+        if (lane == c) yv = yc;
+        acc += row[c] * yc;
+      }
+      if (lane < NVAR) {
+#pragma unroll
+        for (int q = 0; q < NVAR; ++q) {
+          const double v = q <= lane ? row[q] : 0.0;
+          s_L[lane][q] = v;
+          Dk[lane * ROWLEN + q] = v;
+        }
+        s_y[lane] = yv;
+        g[k * NVAR + lane] = yv;
+      }
+      if (bad && lane == 0) s_bad = 1;
+    }
+    __syncthreads();
+    if (s_bad) break;
+    if (t < nb * NVAR) {  // the panel: row (i, p) of L_ik = A_ik L_kk^-T, and g_i -= L_ik y_k
+      const int i = k + 1 + t / NVAR, p = t % NVAR;
+      double* a = Ab + ((size_t)i * NVAR + p) * ROWLEN + (BW - (i - k)) * NVAR;
+      double x[NVAR];
+      double dot = 0.0;
+#pragma unroll
+      for (int q = 0; q < NVAR; ++q) {
+        double v = a[q];
+#pragma unroll
+        for (int m = 0; m < q; ++m) v -= x[m] * s_L[q][m];
+        x[q] = v / s_L[q][q];
+      }
+#pragma unroll
+      for (int q = 0; q < NVAR; ++q) {
+        a[q] = x[q];
+        s_P[t][q] = x[q];
+        dot += x[q] * s_y[q];
+      }
+      g[i * NVAR + p] -= dot;
+    }
+    __syncthreads();
+    const int entries = nb * (nb + 1) / 2 * BLK;
+    // A_ij -= L_ik L_jk^T for k < j <= i <= k + nb.  In batches of TU entries per thread, every load of a batch before its first
+    // store: a load behind a store into the same array is not moved up by the compiler, and the step would pay one memory round
+    // trip per entry instead of one per batch.
+    constexpr int TU = 8;
+    for (int base = t; base < entries; base += 1024 * TU) {
+      double* at[TU];
+      double old[TU];
+#pragma unroll
+      for (int u = 0; u < TU; ++u) {
+        const int idx = base + u * 1024;
+        at[u] = nullptr;
+        if (idx < entries) {
+          const int pr = idx / BLK, wi = idx % BLK, p = wi / NVAR, q = wi % NVAR;
+          const int i = k + 1 + s_pi[pr], j = k + 1 + s_pj[pr];
+          at[u] = Ab + ((size_t)i * NVAR + p) * ROWLEN + (BW - (i - j)) * NVAR + q;
+          old[u] = *at[u];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < TU; ++u) {
+        const int idx = base + u * 1024;
+        if (idx < entries) {
+          const int pr = idx / BLK, wi = idx % BLK, p = wi / NVAR, q = wi % NVAR;
+          const int bi = s_pi[pr], bj = s_pj[pr];
+          double acc = 0.0;
+#pragma unroll
+          for (int m = 0; m < NVAR; ++m) acc += s_P[bi * NVAR + p][m] * s_P[bj * NVAR + q][m];
+          *at[u] = old[u] - acc;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (s_bad) {
+    if (t == 0) {
+      h->status = DMS_DEFORM_SINGULAR;
+      h->optimised = 0;
+      h->done = 1;
+      h->iterations += 1;
+    }
+    return;
+  }
+  for (int k = E - 1; k >= 0; --k) {  // L^T x = y
+    const int nb = min(BW, E - 1 - k);
+    const double* Dk = Ab + (size_t)k * NVAR * ROWLEN + BW * NVAR;
+    if (t < 64 * NVAR) {
+      const int q = t % NVAR, part = t / NVAR;
+      double acc = 0.0;
+      for (int ri = part; ri < nb * NVAR; ri += 64) {
+        const int i = k + 1 + ri / NVAR, p = ri % NVAR;
+        acc += Ab[((size_t)i * NVAR + p) * ROWLEN + (BW - (i - k)) * NVAR + q] * g[i * NVAR + p];
+      }
+      s_red[part][q] = acc;
+    }
+    __syncthreads();
+    if (t < 64) {  // lane c < 12 holds column c of L_kk
+      const int c0 = lane < NVAR ? lane : 0;
+      double col[NVAR];
+#pragma unroll
+      for (int m = 0; m < NVAR; ++m) col[m] = m >= c0 ? Dk[m * ROWLEN + c0] : 0.0;
+      const double self = Dk[c0 * ROWLEN + c0];
+      double rhs = g[k * NVAR + c0];
+      for (int part = 0; part < 64; ++part) rhs -= s_red[part][c0];
+      double acc = 0.0, xv = 0.0;
+#pragma unroll
+      for (int c = NVAR - 1; c >= 0; --c) {
+        const double xc = shfl_d((rhs - acc) / self, c);
+        if (lane == c) xv = xc;
+        acc += col[c] * xc;
+      }
+      if (lane < NVAR) g[k * NVAR + lane] = xv;
+    }
+    __syncthreads();
+  }
+  for (int idx = t; idx < E * NVAR; idx += 1024) d.delta[idx] = g[idx];
+}
+
+// applyDeltaSparse (:960-990): float += double
+__global__ __launch_bounds__(256) void k_apply(Dev d, int it) {
+  const Hdr* h = d.h;
+  if (!h->initialised || h->done) return;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= h->E * NVAR) return;
+  const int node = h->e0 + idx / NVAR, var = idx % NVAR;
+  const double dl = d.delta[idx];
+  if (it == 1) d.delta0[idx] = dl;
+  float* x = var < 9 ? d.rot + 9 * node + var : d.trans + 3 * node + (var - 9);
+  *x = (float)((double)*x + dl);
+}
+
+// squaredNorm / norm in the restatement's order, meanConsErr, and the exit tests of :515
+__global__ __launch_bounds__(256) void k_norms(Dev d, int P, int it) {
+  Hdr* h = d.h;
+  if (!h->initialised || (it > 0 && h->done)) return;
+  if (it < 0 && h->status != DMS_DEFORM_SINGULAR) return;  // it = -1: meanConsErr of the reset graph after a singular exit
+  __shared__ double s_a[256], s_b[256];
+  __shared__ float s_c[2 * DMS_DEFORM_MAX_CONSTRAINTS];
+  const int t = threadIdx.x, rows = h->n_rows, unknowns = h->E * NVAR;
+  double a = 0.0, b = 0.0;
+  for (int i = t; i < rows; i += 256) {
+    const double x = d.resid[i];
+    if (it == 0) d.resid0[i] = x;
+    a += x * x;
+  }
+  if (it > 0)
+    for (int i = t; i < unknowns; i += 256) {
+      const double x = d.delta[i];
+      b += x * x;
+    }
+  s_a[t] = a;
+  s_b[t] = b;
+  for (int l = t; l < P; l += 256) s_c[l] = d.cnorm[l];
+  __syncthreads();
+  for (int s = 128; s >= 1; s >>= 1) {
+    if (t < s) {
+      s_a[t] += s_a[t + s];
+      s_b[t] += s_b[t + s];
+    }
+    __syncthreads();
+  }
+  if (t != 0) return;
+  float sum = 0.f;
+  for (int l = 0; l < P; ++l) sum = sum + s_c[l];
+  const float mce = sum / (float)P;
+  const float error = (float)s_a[0];
+  h->mce_after = mce;
+  if (it < 0) return;
+  h->error = error;
+  if (it == 0) {
+    h->mce_before = mce;
+    h->error0 = error;
+    h->last_error = (double)error;
+    return;
+  }
+  const double e = (double)error, dn = sqrt(s_b[0]), diff = e - h->last_error;
+  h->iter_err[it - 1] = e;
+  h->iter_dn[it - 1] = dn;
+  h->iterations = it;
+  int why = -1;
+  if (e > h->last_error)
+    why = DMS_DEFORM_EXIT_ERROR_GREW;
+  else if (dn < 1e-2)
+    why = DMS_DEFORM_EXIT_SMALL_DELTA;
+  else if (e < 1e-3)
+    why = DMS_DEFORM_EXIT_SMALL_ERROR;
+  else if (fabs(diff) < 1e-5 * e)
+    why = DMS_DEFORM_EXIT_SMALL_CHANGE;
+  else if (it == 3)
+    why = DMS_DEFORM_EXIT_ITERATIONS;
+  if (why >= 0) {
+    h->exit_reason = why;
+    h->done = 1;
+  } else {
+    h->last_error = e;
+  }
+}
+
+// Deformation.cpp:165-209: the node table, newRelativeCons, lastDeformTime; a singular system resets the graph first
+__global__ __launch_bounds__(256) void k_finalize(Dev d, int P, int time, int relax) {
+  Hdr* h = d.h;
+  if (!h->initialised) return;
+  const bool singular = h->status == DMS_DEFORM_SINGULAR;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx < h->n_nodes) {
+    if (singular) identity_node(d, idx);
+    float* row = d.table + 16 * idx;
+    for (int q = 0; q < 3; ++q) row[q] = d.nodes4[4 * idx + q];
+    for (int q = 0; q < 9; ++q) row[3 + q] = d.rot[9 * idx + q];
+    for (int q = 0; q < 3; ++q) row[12 + q] = d.trans[3 * idx + q];
+    row[15] = d.nodes4[4 * idx + 3];
+  }
+  if (idx < P && !singular && d.rel_idx[idx] >= 0) {
+    float* row = d.rel + 8 * d.rel_idx[idx];
+    for (int q = 0; q < 3; ++q) {
+      row[q] = d.pos[3 * idx + q];  // the pool after applyGraphToVertices: the last residual pass computed it from the final graph
+      row[3 + q] = d.tgt[3 * idx + q];
+    }
+    row[6] = (float)d.vtime[idx];
+    row[7] = d.ttime[idx];
+  }
+  if (idx == 0) {
+    h->applied = singular ? 0 : 1;
+    if (!singular && !relax) h->last_deform = (long long)time;
+  }
+}
+
+}  // namespace
+}  // namespace dms
+
+using namespace dms;
+
+struct dms_deform {
+  Dev dev{};
+  char* arena = nullptr;
+  int capN = 0, capC = 0;
+  int n_upper = 0;         // host-side upper bound of the node count (the count itself lives on the device)
+  int n_pool = 0, n_rel = 0, n_cons = 0;
+  int last_pool = 0, last_rel = 0;
+  size_t max_rows = 0, max_nnz = 0;
+  hipStream_t last_stream = nullptr;
+  Hdr* h_hdr = nullptr;  // pinned
+  float* h_rel = nullptr;  // pinned, capC rows of 8
+};
+
+static void carve(dms_deform* o, Carver& c) {
+  Dev& d = o->dev;
+  const size_t N = (size_t)o->capN, P = (size_t)2 * o->capC;
+  d.h = c.take<Hdr>(1);
+  d.nodes4 = c.take<float>(4 * N);
+  d.rot = c.take<float>(9 * N);
+  d.trans = c.take<float>(3 * N);
+  d.table = c.take<float>(16 * N);
+  d.raw4 = c.take<float>(4 * N);
+  d.src = c.take<float>(3 * P);
+  d.tgt = c.take<float>(3 * P);
+  d.ttime = c.take<float>(P);
+  d.vtime = c.take<int>(P);
+  d.rel_idx = c.take<int>(P);
+  d.ids = c.take<int>(4 * P);
+  d.w = c.take<double>(4 * P);
+  d.coef = c.take<double>(16 * P);
+  d.pos = c.take<float>(3 * P);
+  d.cnorm = c.take<float>(P);
+  d.edge_row = c.take<int>(4 * N);
+  d.edge_nz = c.take<int>(4 * N);
+  d.con_row = c.take<int>(P);
+  d.con_nz = c.take<int>(P);
+  d.resid = c.take<double>(o->max_rows);
+  d.resid0 = c.take<double>(o->max_rows);
+  d.indptr = c.take<int>(o->max_rows + 1);
+  d.jcols = c.take<int>(o->max_nnz);
+  d.jvals = c.take<double>(o->max_nnz);
+  d.Ac = c.take<double>(N * NVAR * ROWLEN);
+  d.Ab = c.take<double>(N * NVAR * ROWLEN);
+  d.g = c.take<double>(N * NVAR);
+  d.diag0 = c.take<double>(N * NVAR);
+  d.delta = c.take<double>(N * NVAR);
+  d.delta0 = c.take<double>(N * NVAR);
+  d.rel = c.take<float>(8 * (size_t)o->capC);
+  d.capN = o->capN;
+  d.capP = (int)P;
+}
+
+static inline int blocks_of(size_t n, int per) {
+  const size_t b = (n + per - 1) / per;
+  return (int)(b ? b : 1);
+}
+
+static int sync_last(dms_deform* d) {
+  DMS_HIP(hipStreamSynchronize(d->last_stream));
+  return DMS_OK;
+}
+
+extern "C" {
+static void fill_result(const dms_deform* d, dms_deform_result* out);
+}
+
+namespace dms {
+// The frame step's one read after a solve: the status block and the new relative-constraint rows behind one synchronisation.
+// *rel8: pinned rows of 8 floats, valid until the next call; res->relative_rows of them count.
+int deform_fetch(dms_deform* d, dms_deform_result* res, const float** rel8) {
+  DMS_REQUIRE(d && res && rel8, "null argument");
+  DMS_HIP(hipMemcpyAsync(d->h_hdr, d->dev.h, sizeof(Hdr), hipMemcpyDeviceToHost, d->last_stream));
+  if (d->last_rel > 0)
+    DMS_HIP(hipMemcpyAsync(d->h_rel, d->dev.rel, (size_t)d->last_rel * 8 * sizeof(float), hipMemcpyDeviceToHost, d->last_stream));
+  DMS_HIP(hipStreamSynchronize(d->last_stream));
+  fill_result(d, res);
+  *rel8 = d->h_rel;
+  return DMS_OK;
+}
+
+// rows of `stride` floats {source xyz, target xyz, target time, ...}: the frame step's constraint buffer has 8 per row
+int deform_add_rows(dms_deform* d, const float* rows_dev, int stride, int n, int srcTime, int pin, hipStream_t s) {
+  DMS_REQUIRE(d && rows_dev && n >= 0 && stride >= 7, "bad argument");
+  if (d->n_cons + n > d->capC) {
+    set_error("%s: %d constraints, made for %d", __func__, d->n_cons + n, d->capC);
+    return DMS_ERR_CAPACITY;
+  }
+  if (n == 0) return DMS_OK;
+  hipLaunchKernelGGL(k_add, dim3(blocks_of(n, 256)), dim3(256), 0, s, d->dev, rows_dev, stride, n, d->n_pool, d->n_rel, srcTime, pin ? 1 : 0);
+  DMS_CHECK_LAUNCH();
+  d->n_pool += pin ? 2 * n : n;
+  d->n_rel += n;
+  d->n_cons += n;
+  return DMS_OK;
+}
+}  // namespace dms
+
+extern "C" {
+
+int dms_deform_create(dms_deform** out, int max_nodes, int max_constraints) {
+  DMS_REQUIRE(out, "null argument");
+  DMS_REQUIRE(max_nodes > K && max_nodes <= DMS_DEFORM_MAX_NODES, "max_nodes outside [5, DMS_DEFORM_MAX_NODES]");
+  DMS_REQUIRE(max_constraints >= 1 && max_constraints <= DMS_DEFORM_MAX_CONSTRAINTS, "max_constraints outside [1, DMS_DEFORM_MAX_CONSTRAINTS]");
+  dms_deform* o = new dms_deform();
+  o->capN = max_nodes;
+  o->capC = max_constraints;
+  const size_t N = (size_t)max_nodes, P = (size_t)2 * max_constraints;
+  o->max_rows = (ROT_ROWS + REG_ROWS * K) * N + CON_ROWS * P;  // maxRows of :471
+  o->max_nnz = 27 * N + (size_t)REG_ROWS * 5 * K * N + (size_t)CON_ROWS * 4 * K * P;
+  Carver sz;
+  carve(o, sz);
+  const size_t bytes = up256(sz.off);
+  hipError_t e = hipMalloc((void**)&o->arena, bytes);
+  if (e == hipSuccess) e = hipMemset(o->arena, 0, bytes);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&o->h_hdr, sizeof(Hdr));
+  if (e == hipSuccess) e = hipHostMalloc((void**)&o->h_rel, (size_t)max_constraints * 8 * sizeof(float));
+  if (e != hipSuccess) {
+    if (o->arena) (void)hipFree(o->arena);
+    if (o->h_hdr) (void)hipHostFree(o->h_hdr);
+    delete o;
+    return hip_fail(e, "allocating the deformation solver", __FILE__, __LINE__);
+  }
+  Carver cv;
+  cv.base = o->arena;
+  carve(o, cv);
+  *out = o;
+  return DMS_OK;
+}
+
+int dms_deform_destroy(dms_deform* d) {
+  if (!d) return DMS_OK;
+  if (d->arena) (void)hipFree(d->arena);
+  if (d->h_hdr) (void)hipHostFree(d->h_hdr);
+  if (d->h_rel) (void)hipHostFree(d->h_rel);
+  delete d;
+  return DMS_OK;
+}
+
+int dms_deform_set_nodes(dms_deform* d, const float* rows4_dev, int n, dms_stream s) {
+  DMS_REQUIRE(d && rows4_dev, "null argument");
+  DMS_REQUIRE(n > K, "a graph needs more than 4 nodes");
+  if (n > d->capN) {
+    set_error("%s: %d nodes, made for %d", __func__, n, d->capN);
+    return DMS_ERR_CAPACITY;
+  }
+  hipLaunchKernelGGL(k_set_nodes, dim3(blocks_of(n, 256)), dim3(256), 0, (hipStream_t)s, d->dev, rows4_dev, n);
+  DMS_CHECK_LAUNCH();
+  d->n_upper = n;
+  return DMS_OK;
+}
+
+int dms_deform_sample_model(dms_deform* d, dms_model* m, int sampleRate, dms_stream s) {
+  DMS_REQUIRE(d && m && sampleRate >= 2, "bad argument");
+  if (int rc = model_flush_pending(m, (hipStream_t)s)) return rc;
+  size_t n = (m->count_upper + (size_t)sampleRate - 1) / (size_t)sampleRate;
+  if (n > (size_t)d->capN) n = d->capN;
+  if (n == 0) return DMS_OK;
+  hipLaunchKernelGGL(k_sample, dim3(blocks_of(n, 256)), dim3(256), 0, (hipStream_t)s, m->buf[m->cur], m->d_count, sampleRate, d->dev);
+  DMS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_rank, dim3(blocks_of(n, 256)), dim3(256), 0, (hipStream_t)s, m->d_count, sampleRate, d->dev);
+  DMS_CHECK_LAUNCH();
+  if ((int)n > d->n_upper) d->n_upper = (int)n;
+  return DMS_OK;
+}
+
+int dms_deform_add_constraints(dms_deform* d, const float* rows7_dev, int n, int srcTime, int pin, int relative, dms_stream s) {
+  DMS_REQUIRE(d && rows7_dev && n >= 0, "bad argument");
+  DMS_REQUIRE(!relative, "relative constraints are not solved here (they break the band): keep the caller's solver for them");
+  return deform_add_rows(d, rows7_dev, 7, n, srcTime, pin, (hipStream_t)s);
+}
+
+int dms_deform_clear_constraints(dms_deform* d) {
+  DMS_REQUIRE(d, "null argument");
+  d->n_pool = d->n_rel = d->n_cons = 0;
+  return DMS_OK;
+}
+
+int dms_deform_constrain(dms_deform* d, int time, int relaxGraph, dms_stream stream) {
+  DMS_REQUIRE(d, "null argument");
+  if (d->n_pool == 0) {
+    set_error("%s: no constraints", __func__);
+    return DMS_ERR_STATE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const Dev& dev = d->dev;
+  const int P = d->n_pool, relax = relaxGraph ? 1 : 0;
+  const size_t slot_lds = ((size_t)P * 8 + 15) / 16 * 16;  // compact_touching's two arrays
+  const int items = blocks_of((size_t)5 * d->capN + P, 256), node_blocks = d->n_upper > 0 ? d->n_upper : 1;
+  hipLaunchKernelGGL(k_weights, dim3(blocks_of(P, 64)), dim3(64), 0, s, dev, P);
+  DMS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_setup, dim3(1), dim3(1024), 0, s, dev, P, relax);
+  DMS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_residual, dim3(items), dim3(256), 0, s, dev, P, 0);
+  DMS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_norms, dim3(1), dim3(256), 0, s, dev, P, 0);
+  DMS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_jacobian, dim3(items), dim3(256), 0, s, dev, P);
+  DMS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_assemble_const, dim3(node_blocks), dim3(256), slot_lds, s, dev, P);
+  DMS_CHECK_LAUNCH();
+  for (int it = 1; it <= 3; ++it) {
+    hipLaunchKernelGGL(k_iter_assemble, dim3(node_blocks), dim3(256), slot_lds, s, dev, P);
+    DMS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_solve, dim3(1), dim3(1024), 0, s, dev);
+    DMS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_apply, dim3(blocks_of((size_t)d->n_upper * NVAR, 256)), dim3(256), 0, s, dev, it);
+    DMS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_residual, dim3(items), dim3(256), 0, s, dev, P, 1);
+    DMS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_norms, dim3(1), dim3(256), 0, s, dev, P, it);
+    DMS_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(k_finalize, dim3(blocks_of((size_t)(d->capN > P ? d->capN : P), 256)), dim3(256), 0, s, dev, P, time, relax);
+  DMS_CHECK_LAUNCH();
+  // a singular exit has reset the graph: the pool and meanConsErr (:530) are those of the reset graph (both return at once otherwise)
+  hipLaunchKernelGGL(k_residual, dim3(items), dim3(256), 0, s, dev, P, 2);
+  DMS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_norms, dim3(1), dim3(256), 0, s, dev, P, -1);
+  DMS_CHECK_LAUNCH();
+  d->last_stream = s;
+  d->last_pool = P;
+  d->last_rel = d->n_rel;
+  d->n_pool = d->n_rel = d->n_cons = 0;  // constraints.clear(), Deformation.cpp:214
+  return DMS_OK;
+}
+
+static int fetch_hdr(dms_deform* d) {
+  DMS_HIP(hipMemcpyAsync(d->h_hdr, d->dev.h, sizeof(Hdr), hipMemcpyDeviceToHost, d->last_stream));
+  DMS_HIP(hipStreamSynchronize(d->last_stream));
+  return DMS_OK;
+}
+
+static void fill_result(const dms_deform* d, dms_deform_result* out) {
+  const Hdr& h = *d->h_hdr;
+  memset(out, 0, sizeof(*out));
+  out->applied = h.applied;
+  out->optimised = h.optimised;
+  out->status = h.status;
+  out->iterations = h.iterations;
+  out->exit_reason = h.exit_reason;
+  out->nodes = h.n_nodes;
+  out->enabled_nodes = h.E;
+  out->constraints = h.n_pool;
+  out->rows = h.n_rows;
+  out->relative_rows = h.applied ? d->last_rel : 0;
+  out->error = h.error;
+  out->error_initial = h.error0;
+  out->mean_cons_err_before = h.mce_before;
+  out->mean_cons_err_after = h.mce_after;
+  for (int i = 0; i < 3; ++i) {
+    out->iter_error[i] = h.iter_err[i];
+    out->iter_delta_norm[i] = h.iter_dn[i];
+  }
+  out->last_deform_time = h.last_deform;
+}
+
+int dms_deform_get_result(dms_deform* d, dms_deform_result* out) {
+  DMS_REQUIRE(d && out, "null argument");
+  if (int rc = fetch_hdr(d)) return rc;
+  fill_result(d, out);
+  return DMS_OK;
+}
+
+int dms_deform_graph_device(dms_deform* d, const float** table16_dev, const int** node_count_dev) {
+  DMS_REQUIRE(d && table16_dev && node_count_dev, "null argument");
+  *table16_dev = d->dev.table;
+  *node_count_dev = &d->dev.h->n_nodes;
+  return DMS_OK;
+}
+
+static int copy_out(dms_deform* d, void* dst, const void* src_dev, size_t elem, int have, int max_n, int* n) {
+  if (n) *n = have;
+  const int take = have < max_n ? have : max_n;
+  if (take > 0 && dst) DMS_HIP(hipMemcpy(dst, src_dev, (size_t)take * elem, hipMemcpyDeviceToHost));
+  return DMS_OK;
+}
+
+int dms_deform_get_relative_constraints(dms_deform* d, float* rows8_host, int max_rows, int* n) {
+  DMS_REQUIRE(d && n && (rows8_host || max_rows == 0), "bad argument");
+  if (int rc = fetch_hdr(d)) return rc;
+  return copy_out(d, rows8_host, d->dev.rel, 8 * sizeof(float), d->h_hdr->applied ? d->last_rel : 0, max_rows, n);
+}
+
+int dms_deform_last_deform_time(dms_deform* d, long long* t) {
+  DMS_REQUIRE(d && t, "null argument");
+  if (int rc = fetch_hdr(d)) return rc;
+  *t = d->h_hdr->last_deform;
+  return DMS_OK;
+}
+
+int dms_deform_set_last_deform_time(dms_deform* d, long long t) {
+  DMS_REQUIRE(d, "null argument");
+  DMS_HIP(hipDeviceSynchronize());  // whatever stream the nodes or a solve were enqueued on
+  DMS_HIP(hipMemcpy(&d->dev.h->last_deform, &t, sizeof(t), hipMemcpyHostToDevice));
+  return DMS_OK;
+}
+
+int dms_deform_get_vertex_weights(dms_deform* d, int* ids4_host, double* weights4_host, int max_vertices, int* n) {
+  DMS_REQUIRE(d && n, "null argument");
+  if (int rc = sync_last(d)) return rc;
+  if (int rc = copy_out(d, ids4_host, d->dev.ids, K * sizeof(int), d->last_pool, max_vertices, n)) return rc;
+  return copy_out(d, weights4_host, d->dev.w, K * sizeof(double), d->last_pool, max_vertices, n);
+}
+
+int dms_deform_get_first_residual(dms_deform* d, double* r_host, int max_rows, int* n) {
+  DMS_REQUIRE(d && n, "null argument");
+  if (int rc = fetch_hdr(d)) return rc;
+  return copy_out(d, r_host, d->dev.resid0, sizeof(double), d->h_hdr->n_rows, max_rows, n);
+}
+
+int dms_deform_get_first_jacobian(dms_deform* d, int* indptr_host, int* cols_host, double* vals_host, int max_rows, int max_nnz, int* n,
+                                  int* nnz) {
+  DMS_REQUIRE(d && n && nnz, "null argument");
+  if (int rc = fetch_hdr(d)) return rc;
+  const int rows = d->h_hdr->E ? d->h_hdr->n_rows : 0, nz = d->h_hdr->E ? d->h_hdr->nnz : 0;
+  if (int rc = copy_out(d, indptr_host, d->dev.indptr, sizeof(int), rows ? rows + 1 : 0, max_rows + 1, nullptr)) return rc;
+  if (int rc = copy_out(d, cols_host, d->dev.jcols, sizeof(int), nz, max_nnz, nullptr)) return rc;
+  if (int rc = copy_out(d, vals_host, d->dev.jvals, sizeof(double), nz, max_nnz, nullptr)) return rc;
+  *n = rows;
+  *nnz = nz;
+  return DMS_OK;
+}
+
+int dms_deform_get_first_delta(dms_deform* d, double* delta_host, int max_unknowns, int* n) {
+  DMS_REQUIRE(d && n, "null argument");
+  if (int rc = fetch_hdr(d)) return rc;
+  const Hdr& h = *d->h_hdr;
+  const bool have = h.iterations >= 1 && !(h.status == DMS_DEFORM_SINGULAR && h.iterations == 1);
+  return copy_out(d, delta_host, d->dev.delta0, sizeof(double), have ? h.E * NVAR : 0, max_unknowns, n);
+}
+
+int dms_deform_get_pool(dms_deform* d, float* xyz_host, int max_vertices, int* n) {
+  DMS_REQUIRE(d && n, "null argument");
+  if (int rc = sync_last(d)) return rc;
+  return copy_out(d, xyz_host, d->dev.pos, 3 * sizeof(float), d->last_pool, max_vertices, n);
+}
+
+}  // extern "C"

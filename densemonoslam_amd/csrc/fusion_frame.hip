@@ -254,6 +254,12 @@ struct dms_fusion {
   float* nid_host = nullptr;  // pinned [2]
   int frames_since_fusion = 0;
   float last_nid = 0.f;
+  // dms_fusion_set_loop_solver: the frame step closes its local loops itself (ElasticFusion.cpp:441-493)
+  bool loop_solver = false;
+  int graph_sample_rate = 5000;      // Options::defGraphSampleRate
+  dms_deform* deform = nullptr;      // created when the solver is first switched on
+  int deforms = 0;                   // ElasticFusion::deforms (:485)
+  std::vector<float> relative_cons;  // context.relativeCons() (:489-492): rows of 8 floats
   // between dms_fusion_process_frame_begin and _end
   bool in_frame = false, cur_bootstrap = false, cur_fuse_now = true;
   int live_set = 0, lastnext_set = 0;  // ring sets of the previous frame's live pyramids and of its lastNextImage
@@ -885,6 +891,7 @@ int dms_fusion_destroy(dms_fusion* f) {
   if (f->h_loop) (void)hipHostFree(f->h_loop);
   if (f->h_gloop) (void)hipHostFree(f->h_gloop);
   if (f->odom_m2m) dms_odometry_destroy(f->odom_m2m);
+  if (f->deform) dms_deform_destroy(f->deform);
   dms_odometry_destroy(f->odom);
   dms_model* const own = f->own_model ? f->own_model : f->model;
   if (f->model && f->model != own) f->model->sharers -= 1;  // (a joined camera: the map's owner outlives it, dmslam_fusion.h)
@@ -1450,16 +1457,18 @@ static int synthesise_depth(dms_fusion* f, int timeDeltaEff, hipStream_t s) {
                        f->tick - timeDeltaEff, 65535, 0, f->zbuf, nullptr, &f->depth_synth, 1, s);
 }
 
-static int clean_map(dms_fusion* f, const float* graph_host, int graph_nodes, int timeDeltaEff, hipStream_t s) {
+static int clean_map(dms_fusion* f, const float* graph_host, const float* graph_dev, int graph_nodes, int timeDeltaEff, hipStream_t s) {
   StageTimer t(f->clock, s, "clean", f->profiling);
   return model_clean(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->imap, graph_nodes > 0 ? &f->depth_synth : nullptr, &f->cam,
-                     f->p.confidence, graph_host, graph_nodes, timeDeltaEff, f->p.maxDepthProcessed, 0, 1, &f->state->surfels, s);
+                     f->p.confidence, graph_host, graph_nodes, timeDeltaEff, f->p.maxDepthProcessed, 0, 1, &f->state->surfels, s, graph_dev);
 }
 
-static int process_frame_end(dms_fusion* f, const float* graph_host, int graph_nodes, const float* newPose16, dms_stream st, bool one_call) {
+// graph_dev: the node table in device memory (the loop solver's) instead of graph_host
+static int process_frame_end(dms_fusion* f, const float* graph_host, int graph_nodes, const float* newPose16, dms_stream st, bool one_call,
+                             const float* graph_dev = nullptr) {
   DMS_REQUIRE(f, "null argument");
   DMS_REQUIRE(f->in_frame, "dms_fusion_process_frame_begin has not been called");
-  DMS_REQUIRE(graph_nodes == 0 || graph_host, "null graph");
+  DMS_REQUIRE(graph_nodes == 0 || graph_host || graph_dev, "null graph");
   hipStream_t s = (hipStream_t)st;
   int rc;
   int fused = 0;
@@ -1486,7 +1495,7 @@ static int process_frame_end(dms_fusion* f, const float* graph_host, int graph_n
       if ((rc = fuse_measurements(f, s))) return rc;
       if ((rc = index_map_for_clean(f, timeDeltaEff, s))) return rc;
       if (graph_nodes > 0 && (rc = synthesise_depth(f, timeDeltaEff, s))) return rc;
-      if ((rc = clean_map(f, graph_host, graph_nodes, timeDeltaEff, s))) return rc;
+      if ((rc = clean_map(f, graph_host, graph_dev, graph_nodes, timeDeltaEff, s))) return rc;
       surfels_written = true;  // the clean's scan also stores the new count into the result block
       fused = 1;
     }
@@ -1506,11 +1515,89 @@ static int process_frame_end(dms_fusion* f, const float* graph_host, int graph_n
   return DMS_OK;
 }
 
+// ElasticFusion.cpp:441-493 inside the one-call frame: the host reads the candidate's verdict (one mid-frame synchronisation, as the
+// NID gate and --rl have); on an accepted loop the graph is sampled from the map as it stands, the frame's own constraint buffer goes
+// into the solver (pinned while deforms == 0) and the solve is enqueued; the host then reads its status and node count.
+static int close_local_loop(dms_fusion* f, hipStream_t s, const float** table_dev, int* nodes, const float** est_pose) {
+  *nodes = 0;
+  DMS_HIP(hipStreamSynchronize(s));
+  const char* slot = f->h_loop + (size_t)f->last_slot * f->loop_bytes;
+  const LoopState* L = (const LoopState*)slot;
+  if (!L->ok || L->n_constraints <= 0) return DMS_OK;
+  int rc;
+  if ((rc = dms_deform_sample_model(f->deform, f->model, f->graph_sample_rate, (dms_stream)s))) return rc;
+  if ((rc = dms_deform_clear_constraints(f->deform))) return rc;
+  const float* rows = (const float*)((const char*)f->loop + up256(sizeof(LoopState)));
+  if ((rc = deform_add_rows(f->deform, rows, 8, L->n_constraints, f->tick, f->deforms == 0, s))) return rc;
+  if ((rc = dms_deform_constrain(f->deform, f->tick, 0, (dms_stream)s))) return rc;
+  dms_deform_result res;
+  const float* rel = nullptr;
+  if ((rc = deform_fetch(f->deform, &res, &rel))) return rc;  // the second read: status, node count and the new relative rows
+  if (!res.applied || res.nodes <= 0) return DMS_OK;          // the frame ends as an unaccepted loop does
+  const int* count_dev;
+  if ((rc = dms_deform_graph_device(f->deform, table_dev, &count_dev))) return rc;
+  *nodes = res.nodes;
+  *est_pose = L->est_pose;
+  f->deforms += 1;  // deforms += rawGraph.size() > 0 (:485)
+  // every (size / 3)-th new relative constraint (:489-492); the reference's step of 0 for fewer than 3 rows never ends: at least 1
+  const int n = res.relative_rows, step = n / 3 > 0 ? n / 3 : 1;
+  for (int i = 0; i < n; i += step) f->relative_cons.insert(f->relative_cons.end(), rel + (size_t)i * 8, rel + (size_t)(i + 1) * 8);
+  return DMS_OK;
+}
+
 int dms_fusion_process_frame(dms_fusion* f, const void* rgb_dev, int rgb_channels, const unsigned short* depth_dev, const float* inPose16,
                              float weightMultiplier, dms_stream st) {
+  // what the loop solver cannot run on is refused before anything of the frame is enqueued
+  DMS_REQUIRE(!f || !f->loop_solver || (f->model->sharers == 1 && f->clusters.size() == 1 && f->req_cluster == 0),
+              "the loop solver needs a map this camera owns alone, without clusters");
   int rc = dms_fusion_process_frame_begin(f, rgb_dev, rgb_channels, depth_dev, inPose16, weightMultiplier, st);
   if (rc) return rc;
+  if (f->loop_solver && f->p.local_loop_closure && !f->cur_bootstrap && !f->lost) {
+    const float* table_dev = nullptr;
+    const float* est_pose = nullptr;
+    int nodes = 0;
+    if ((rc = close_local_loop(f, (hipStream_t)st, &table_dev, &nodes, &est_pose))) {
+      // the solve failed to run: the frame is finished as an unaccepted loop is, so that tick and ring state stay whole, and the
+      // error is reported (the error text is the solve's)
+      const int rc_end = process_frame_end(f, nullptr, 0, nullptr, st, true);
+      (void)rc_end;
+      return rc;
+    }
+    if (nodes > 0) return process_frame_end(f, nullptr, nodes, est_pose, st, true, table_dev);
+  }
   return process_frame_end(f, nullptr, 0, nullptr, st, true);
+}
+
+int dms_fusion_set_loop_solver(dms_fusion* f, int on, int sampleRate) {
+  DMS_REQUIRE(f, "null argument");
+  DMS_REQUIRE(!f->in_frame, "between process_frame_begin and _end");
+  if (!on) {
+    f->loop_solver = false;
+    return DMS_OK;
+  }
+  if (sampleRate <= 0) sampleRate = 5000;  // Options::defGraphSampleRate
+  DMS_REQUIRE(sampleRate >= 2, "sampleRate below 2");
+  DMS_REQUIRE(f->p.local_loop_closure, "the context was created without local_loop_closure");
+  DMS_REQUIRE(f->model == f->clusters[0] && f->model->sharers == 1 && f->clusters.size() == 1 && f->req_cluster == 0,
+              "the loop solver needs a map this camera owns alone, without clusters");
+  const int cons = (f->p.width / 20) * (f->p.height / 20);
+  DMS_REQUIRE(cons >= 1 && cons <= DMS_DEFORM_MAX_CONSTRAINTS, "the frame size gives more constraint samples than the solver takes");
+  if (!f->deform) {
+    // (one node fewer than the reference's buffer: the clean takes fewer than MAX_NODES = 2048 nodes, GlobalModel.cpp:703)
+    if (int rc = dms_deform_create(&f->deform, DMS_DEFORM_MAX_NODES - 1, cons)) return rc;
+  }
+  f->loop_solver = true;
+  f->graph_sample_rate = sampleRate;
+  return DMS_OK;
+}
+
+dms_deform* dms_fusion_deformation(dms_fusion* f) { return f ? f->deform : nullptr; }
+int dms_fusion_get_deforms(dms_fusion* f) { return f ? f->deforms : 0; }
+int dms_fusion_get_relative_constraints(dms_fusion* f, float* rows8_host, int max_rows, int* n) {
+  DMS_REQUIRE(f && n && (rows8_host || max_rows == 0), "null argument");
+  *n = (int)(f->relative_cons.size() / 8);
+  for (int i = 0; i < *n && i < max_rows; ++i) memcpy(rows8_host + (size_t)i * 8, f->relative_cons.data() + (size_t)i * 8, 8 * sizeof(float));
+  return DMS_OK;
 }
 
 int dms_fusion_process_frame_end(dms_fusion* f, const float* graph_host, int graph_nodes, const float* newPose16, dms_stream st) {

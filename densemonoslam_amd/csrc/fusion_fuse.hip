@@ -910,7 +910,7 @@ int model_flush_pending(dms_model* m, hipStream_t s) {
 
 int model_clean(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_indexmap_out* im, const dms_image2d* depth_synth,
                 const dms_camera* cam, float confThreshold, const float* graph_host, int graph_nodes, int timeDelta, float maxDepth,
-                int isFern, int transposed, unsigned* count_out2, hipStream_t s) {
+                int isFern, int transposed, unsigned* count_out2, hipStream_t s, const float* graph_dev) {
   DMS_REQUIRE(m && !m->pending_update, "a deferred update pass is still pending (index_map applies it)");
   DMS_REQUIRE(m && pose && im && cam, "null argument");
   DMS_REQUIRE(timeIdx >= 0 && timeIdx < DMS_MAX_SENSORS, "timeIdx out of range");
@@ -921,9 +921,10 @@ int model_clean(dms_model* m, const dms_pose_block* pose, int time, int timeIdx,
     set_error("dms_model_clean: %d deformation nodes exceed the limit %d", graph_nodes, m->max_nodes);
     return DMS_ERR_CAPACITY;
   }
-  if (graph_nodes > 0) {
-    DMS_REQUIRE(graph_host, "null graph");
-    DMS_HIP(hipMemcpyAsync(m->nodes, graph_host, (size_t)graph_nodes * 16 * sizeof(float), hipMemcpyHostToDevice, s));
+  if (graph_nodes > 0) {  // graph_dev: the table is in device memory already (the deformation solver's)
+    DMS_REQUIRE(graph_host || graph_dev, "null graph");
+    DMS_HIP(hipMemcpyAsync(m->nodes, graph_dev ? graph_dev : graph_host, (size_t)graph_nodes * 16 * sizeof(float),
+                           graph_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
   }
   CleanArgs a;
   a.pose = pose;

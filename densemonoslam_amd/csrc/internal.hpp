@@ -1,6 +1,7 @@
 // Internal C++ entry points shared between translation units of libdmslam_hip.so.
 #pragma once
 #include "common.hpp"
+#include "../../include/dmslam_deform.h"
 #include "../../include/dmslam_render_panels.h"
 
 namespace dms {
@@ -108,7 +109,12 @@ int model_fuse_scratch(dms_model* m, float* slot_pos4, float* slot_col4, float* 
                        unsigned* winner, size_t winner_count, hipStream_t s);
 int model_clean(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_indexmap_out* im, const dms_image2d* depth_synth,
                 const dms_camera* cam, float confThreshold, const float* graph_host, int graph_nodes, int timeDelta, float maxDepth,
-                int isFern, int transposed, unsigned* count_out2, hipStream_t s);
+                int isFern, int transposed, unsigned* count_out2, hipStream_t s, const float* graph_dev = nullptr);
+
+// deform.hip: dms_deform_add_constraints over rows of `stride` >= 7 floats
+int deform_add_rows(dms_deform* d, const float* rows_dev, int stride, int n, int srcTime, int pin, hipStream_t s);
+// status block and new relative-constraint rows (pinned, rows of 8 floats) behind one synchronisation
+int deform_fetch(dms_deform* d, dms_deform_result* res, const float** rel8);
 
 // track.hip
 struct TrackFold {  // the track call a model pyramid launch prepares (odometry_initModel_fused)

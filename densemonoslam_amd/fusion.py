@@ -732,6 +732,35 @@ class ElasticFusion:
               "dms_fusion_get_loop_constraints")
         return out[:n.value].copy()
 
+    def setLoopSolver(self, on=True, sampleRate=5000):
+        """processFrame closes its local loops itself (dms_fusion_set_loop_solver): Deformation::constrain runs on the GPU"""
+        lib.dms_fusion_set_loop_solver.argtypes = [_P, _I, _I]
+        check(lib.dms_fusion_set_loop_solver(self.h, int(bool(on)), int(sampleRate)), "dms_fusion_set_loop_solver")
+
+    def deformation(self):
+        """The context's solver as a deform.Deformation view (None until the loop solver was first switched on)"""
+        from . import deform
+
+        lib.dms_fusion_deformation.restype = C.c_void_p
+        lib.dms_fusion_deformation.argtypes = [_P]
+        h = lib.dms_fusion_deformation(self.h)
+        return deform.Deformation.view(h, (self.width // 20) * (self.height // 20)) if h else None
+
+    def deforms(self):
+        """ElasticFusion::getDeforms: frames whose local loop was closed by the loop solver"""
+        lib.dms_fusion_get_deforms.argtypes = [_P]
+        return int(lib.dms_fusion_get_deforms(self.h))
+
+    def relativeConstraints(self):
+        """context.relativeCons(): n x 8 float32 {deformed source, target, source time, target time}"""
+        lib.dms_fusion_get_relative_constraints.argtypes = [_P, C.POINTER(C.c_float), _I, C.POINTER(C.c_int)]
+        n = C.c_int(0)
+        check(lib.dms_fusion_get_relative_constraints(self.h, None, 0, C.byref(n)), "dms_fusion_get_relative_constraints")
+        out = np.zeros((max(1, n.value), 8), np.float32)
+        check(lib.dms_fusion_get_relative_constraints(self.h, out.ctypes.data_as(C.POINTER(C.c_float)), n.value, C.byref(n)),
+              "dms_fusion_get_relative_constraints")
+        return out[:n.value].copy()
+
     OPTIONS = {"rgbOnly": 0, "icpWeight": 1, "pyramid": 2, "fastOdom": 3, "so3": 4, "frameToFrameRGB": 5, "confidence": 6, "depthCut": 7}
 
     def setOption(self, name, value):
