@@ -35,6 +35,12 @@ class Case:
         self.src_time = int(self.nodes[-1, 3]) + 1  # the closing frame's tick
         self.time = self.src_time
         self.last_deform_time = last_deform_time
+        self.relax = False
+
+    @property
+    def batches(self):
+        """the addConstraints calls of the case, in order: (rows, source time, pin)"""
+        return [(self.rows, self.src_time, self.pins)]
 
     def __repr__(self):
         return self.name
@@ -73,6 +79,117 @@ def singular_case():
 def no_enabled_case():
     c = Case("n24_c40_none_enabled", 24, 40, 9)
     c.last_deform_time = int(c.nodes[-1, 3])
+    return c
+
+
+# ---- the edges of the solver: capacity, short enabled suffixes, batches, pool sizes at chunk boundaries, one hot node, NaN ------------------
+def capacity_case():
+    return Case("n2048_c2048", 2048, 2048, 7)  # the solver's capacity: pool 4096
+
+
+def frame_capacity_case():
+    return Case("n2047_c768", 2047, 768, 7)  # the frame step's solver
+
+
+def wrap_cases():
+    """the sizes around which the solver's 1024-thread setup passes wrap, and one whose disabled prefix is longer than 1024 nodes"""
+    ldt, kept = _suffix_time(1300, 12, 200)
+    assert 190 <= kept <= 200, kept
+    return [Case("n%d_c64" % n, n, 64, 12) for n in (1023, 1024, 1025)] + [
+        Case("n1300_c64_nopins_suffix%d" % kept, 1300, 64, 12, pins=False, last_deform_time=ldt)]
+
+
+# shift per suffix length: the one of (0.05, 1, 3, 20, 40) that stays 1 % clear of every exit threshold and runs the most iterations
+SUFFIX_SHIFT = {1: 0.05, 2: 0.05, 4: 40.0, 5: 40.0, 18: 20.0, 19: 20.0, 20: 20.0, 21: 20.0, 22: 20.0, 41: 20.0, 63: 20.0}
+
+
+def suffix_cases():
+    """64 nodes, 96 constraints, exactly E enabled nodes at the end of the graph, with and without pins"""
+    out = []
+    for e, shift in SUFFIX_SHIFT.items():
+        ldt, kept = _suffix_time(64, 21, e)
+        assert kept == e, (e, kept)
+        for pins in (True, False):
+            out.append(Case("n64_c96_suffix%d_%s" % (e, "pins" if pins else "nopins"), 64, 96, 21, pins=pins, last_deform_time=ldt, shift=shift))
+    return out + [dense_suffix_case(e, seed) for e, seed in ((19, 25), (20, 23), (21, 24), (22, 23))]
+
+
+def dense_suffix_case(e, seed):
+    """The last 64 nodes of a 2048-node path: they lie closer together than their noise, so a vertex's four nearest of the 20 in its
+    window are up to 19 nodes apart and the normal matrix fills the whole band (on make_nodes(64, .) they are neighbours and the band
+    is 5 blocks wide).  Unpinned, exactly e enabled nodes, shift 20: three iterations, 2 % clear or better."""
+    c = Case("n64_c96_dense_suffix%d_nopins" % e, 64, 4, seed, pins=False, shift=20.0)
+    c.nodes = make_nodes(2048, seed)[-64:]
+    t = c.nodes[:, 3]
+    assert t[64 - e - 1] < t[64 - e], (e, seed)
+    c.rows = make_rows(c.nodes[44:], 96, seed, 20.0)
+    c.last_deform_time = int(t[64 - e - 1])
+    c.src_time = c.time = int(t[-1]) + 1
+    return c
+
+
+def suffix_case(e, pins=True):
+    return [c for c in suffix_cases() if c.name == "n64_c96_suffix%d_%s" % (e, "pins" if pins else "nopins")][0]
+
+
+class BatchCase(Case):
+    """Constraints added in several calls: sizes[i] rows with pin flag pin_flags[i] and source time src_times[i]"""
+
+    def __init__(self, name, n, sizes, pin_flags, src_offsets, seed, shift=1.0):
+        Case.__init__(self, name, n, sum(sizes), seed, pins=None, shift=shift)
+        cuts = np.cumsum([0] + list(sizes))
+        self._batches = [(self.rows[a:b], self.src_time + off, bool(pin)) for a, b, pin, off in zip(cuts[:-1], cuts[1:], pin_flags, src_offsets)]
+
+    @property
+    def batches(self):
+        return self._batches
+
+
+def batch_case():
+    """four calls with mixed pin flags and two source times"""
+    return BatchCase("n45_batches_30p_17_1p_50", 45, (30, 17, 1, 50), (True, False, True, False), (0, -7, -7, 0), 13, shift=20.0)
+
+
+def boundary_cases():
+    """pools at the wave (64) and chunk (256) boundaries of the assembly's compaction"""
+    out = [Case("n45_pool%d_nopins" % m, 45, m, 14, pins=False, shift=3.0) for m in (63, 64, 65, 255, 256, 257)]
+    return out + [Case("n45_pool%d_pins" % (2 * m), 45, m, 14, shift=3.0) for m in (128, 129)]
+
+
+def hot_node_case(m):
+    """m pinned constraints whose sources lie within 2 mm of node 60 of 64: the sources (of the closing frame's time, so
+    weighted among the last 20 nodes) all touch the same four nodes"""
+    c = Case("n64_c%d_hot_node" % m, 64, 4, 15)
+    rng = np.random.default_rng(15 + m)
+    d = rng.normal(size=(m, 3))
+    d *= (0.002 * rng.random(size=(m, 1)) ** (1 / 3)) / np.linalg.norm(d, axis=1, keepdims=True)
+    src = c.nodes[60, :3].astype(np.float64) + d
+    tgt = src + np.array([0.02, -0.01, 0.015])
+    c.rows = np.concatenate([src, tgt, np.full((m, 1), c.nodes[2, 3])], 1).astype(np.float32)  # the pins are weighted among the first nodes
+    return c
+
+
+def single_unpinned_case():
+    return Case("n24_c1_nopins", 24, 1, 16, pins=False)
+
+
+def poisoned_case(value):
+    """64 nodes, 40 pinned constraints at the full staged shift (40); one more, added in a call of its own with a source time in the
+    middle of the graph, has `value` (NaN or Inf) as its source x: the normal matrix is poisoned around block 30"""
+    c = BatchCase("n64_c40_%s_mid_graph" % ("nan" if np.isnan(value) else "inf"), 64, (39, 1), (True, True), (0, 0), 17, shift=40.0)
+    rows, _, _ = c._batches[1]
+    rows = rows.copy()
+    rows[0, 0] = value
+    rows[0, 6] = c.nodes[30, 3]
+    c._batches[1] = (rows, int(c.nodes[30, 3]), True)
+    c.rows = np.concatenate([c._batches[0][0], rows])
+    return c
+
+
+def relax_case():
+    c = staged_cases()[4]
+    c.name += "_relax"
+    c.relax = True
     return c
 
 

@@ -313,8 +313,9 @@ def normal_equations(indptr, cols, vals, r, ncols, dtype=np.float64):
     return U, gvec, widest
 
 
-def band_cholesky_solve(U, gvec):
-    """In-place right-looking Cholesky on the upper band, then both triangular solves.  None for a non-positive pivot."""
+def band_cholesky_solve(U, gvec, failed_at=None):
+    """In-place right-looking Cholesky on the upper band, then both triangular solves.  None for a non-positive pivot (its scalar
+    column is appended to failed_at, where given)."""
     bw = U.shape[1] - 1
     n = len(gvec)
     dtype = U.dtype
@@ -324,6 +325,8 @@ def band_cholesky_solve(U, gvec):
     for k in range(n):
         piv = U[k, 0]
         if not piv > dtype.type(PIVOT_REL) * diag0[k]:
+            if failed_at is not None:
+                failed_at.append(k)
             return None
         d = np.sqrt(piv)
         U[k, 0] = d
@@ -343,12 +346,12 @@ def band_cholesky_solve(U, gvec):
     return y[:n]
 
 
-def solve(indptr, cols, vals, r, ncols, solver="A"):
+def solve(indptr, cols, vals, r, ncols, solver="A", failed_at=None):
     dtype = np.float64 if solver == "A" else np.longdouble
     U, gvec, widest = normal_equations(indptr, cols, vals, r, ncols, dtype)
     gmax = np.abs(gvec).max() if ncols else 0
     Ukeep = U.copy()
-    x = band_cholesky_solve(U, gvec)
+    x = band_cholesky_solve(U, gvec, failed_at)
     return x, Ukeep, gvec, widest
 
 
@@ -399,12 +402,13 @@ def optimise(p, last_deform_time, solver="A", delta_override=None):
     it = 0
     while it < 3:
         it += 1
-        x, U, gvec, wd = solve(*J, r, ncols, solver)
+        failed_at = []
+        x, U, gvec, wd = solve(*J, r, ncols, solver, failed_at)
         widest = max(widest, wd)
         if it == 1:
             out["U0"], out["g0"] = U, gvec
         if x is None:
-            out.update(status=STATUS_SINGULAR, optimised=False, iterations=it, error=error, widest=widest)
+            out.update(status=STATUS_SINGULAR, optimised=False, iterations=it, error=error, widest=widest, pivot_failed_at=failed_at[0])
             g.reset()
             out["meanConsErr_after"] = mean_cons_error(p)
             return out
@@ -455,13 +459,33 @@ def node_table(g):
     return tab
 
 
+def pool_of_batches(batches):
+    """pool_of over several addConstraint batches (rows7, src_time, pin) in call order: the pool of every batch behind the one before.
+    Also, per pool vertex, the relative row it becomes (numbered across the batches, -1 for a pin) and that row's times."""
+    src, tgt, vt, pin = [np.zeros((0, 3), np.float32)], [np.zeros((0, 3), np.float32)], [np.zeros(0, np.int64)], [np.zeros(0, bool)]
+    rel_times = []
+    for rows7, src_time, pins in batches:
+        rows7 = np.asarray(rows7, np.float32).reshape(-1, 7)
+        s, t, v, q = pool_of(rows7, src_time, pins)
+        src.append(s); tgt.append(t); vt.append(v); pin.append(q)
+        rel_times += [(np.float32(src_time), r[6]) for r in rows7]
+    pin = np.concatenate(pin)
+    rel_idx = np.where(pin, -1, np.cumsum(~pin) - 1)
+    return np.concatenate(src), np.concatenate(tgt), np.concatenate(vt), pin, rel_idx, rel_times
+
+
 def constrain(nodes4, rows7, src_time, pin_constraints, time, relax_graph, last_deform_time, solver="A", delta_override=None, graph=None):
-    """Deformation::constrain (Deformation.cpp:91-220) without ferns and poses.  Returns the dict of optimise plus applied, table,
-    pool (the deformed pool vertices), relative (rows {deformed src, target, src time, target time} of the non-pin constraints),
-    lastDeformTime, ids, weights."""
+    """Deformation::constrain for one batch of constraints (see constrain_batches)"""
+    return constrain_batches(nodes4, [(rows7, src_time, pin_constraints)], time, relax_graph, last_deform_time, solver, delta_override, graph)
+
+
+def constrain_batches(nodes4, batches, time, relax_graph, last_deform_time, solver="A", delta_override=None, graph=None):
+    """Deformation::constrain (Deformation.cpp:91-220) without ferns and poses, over the constraints of several addConstraint batches
+    (rows7, src_time, pin) in call order.  Returns the dict of optimise plus applied, table, pool (the deformed pool vertices), relative
+    (rows {deformed src, target, src time, target time} of the non-pin constraints, in constraint order), rel_idx (per pool vertex, its
+    row of relative or -1), lastDeformTime, ids, weights."""
     g = graph if graph is not None else Graph(nodes4)
-    rows7 = np.asarray(rows7, np.float32).reshape(-1, 7)
-    src, tgt, vt, pin = pool_of(rows7, src_time, pin_constraints)
+    src, tgt, vt, pin, rel_idx, rel_times = pool_of_batches(batches)
     p = Problem(g, src, tgt, vt, pin)
     out = optimise(p, 0 if relax_graph else last_deform_time, solver, delta_override)
     out["ids"], out["weights"] = p.ids, p.w
@@ -469,15 +493,14 @@ def constrain(nodes4, rows7, src_time, pin_constraints, time, relax_graph, last_
     out["graph"] = g
     out["lastDeformTime"] = last_deform_time
     out["table"] = node_table(g)
+    out["rel_idx"] = rel_idx
     if out["applied"]:
         pool = np.array([vertex_position(g, p.src[v], p.ids[v], p.w[v]) for v in range(len(p.src))], np.float32).reshape(-1, 3)
         out["pool"] = pool
         rel = []
-        k = 0
         for v in range(len(p.src)):
             if not pin[v]:
-                rel.append(np.concatenate([pool[v], tgt[v], [np.float32(src_time), rows7[k][6]]]))
-                k += 1
+                rel.append(np.concatenate([pool[v], tgt[v], rel_times[rel_idx[v]]]))
         out["relative"] = np.array(rel, np.float32).reshape(-1, 8)
         if not relax_graph:
             out["lastDeformTime"] = int(time)  # :203-206

@@ -10,11 +10,14 @@ import pytest
 from tests import deform_cases, deform_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ALL_CASES = deform_cases.staged_cases() + [deform_cases.singular_case(), deform_cases.no_enabled_case()]
+# the inputs of tests/test_deform_edges_gpu.py whose path is asserted there: small ones, and the two at capacity
+EDGE_CASES = (deform_cases.suffix_cases() + [deform_cases.batch_case()] + deform_cases.boundary_cases() + [deform_cases.hot_node_case(300), deform_cases.relax_case()])
+CAPACITY_CASES = [deform_cases.hot_node_case(2048), deform_cases.frame_capacity_case(), deform_cases.capacity_case()]
+ALL_CASES = deform_cases.staged_cases() + [deform_cases.singular_case(), deform_cases.no_enabled_case()] + EDGE_CASES + CAPACITY_CASES
 
 
 def _run(c, solver="A"):
-    return R.constrain(c.nodes, c.rows, c.src_time, c.pins, c.time, False, c.last_deform_time, solver)
+    return R.constrain_batches(c.nodes, c.batches, c.time, c.relax, c.last_deform_time, solver)
 
 
 @pytest.fixture(scope="module")
@@ -81,6 +84,48 @@ def test_inputs_stay_clear_of_every_exit_threshold(runs):
                 assert abs(a - b) >= 0.01 * max(abs(a), abs(b)), (name, it + 1, what, a, b)
         seen.add(o["exit"])
     assert {0, 1, 2, 3, 5} <= seen, seen  # the cases reach these exits
+    assert len(runs) == len(ALL_CASES) and all(o["status"] == R.STATUS_OK for n, o in runs.items() if n != "n5_c1_singular")
+
+
+def test_edge_inputs_are_what_their_names_say(runs):
+    """Enabled counts, pool sizes and paths of the inputs of tests/test_deform_edges_gpu.py, as the restatement finds them"""
+    for c in deform_cases.suffix_cases():
+        e = int(c.name.split("suffix")[1].split("_")[0])
+        assert runs[c.name]["enabled"] == e and runs[c.name]["iterations"] == (1 if e <= 2 else 3), c
+    assert [len(runs[c.name]["ids"]) for c in deform_cases.boundary_cases()] == [63, 64, 65, 255, 256, 257, 256, 258]
+    b = deform_cases.batch_case()
+    assert [(len(r), p) for r, _, p in b.batches] == [(30, True), (17, False), (1, True), (50, False)]
+    assert len({t for _, t, _ in b.batches}) == 2 and len(runs[b.name]["ids"]) == 129 and len(runs[b.name]["relative"]) == 98
+    assert list(runs[b.name]["rel_idx"][:6]) == [0, -1, 1, -1, 2, -1] and list(runs[b.name]["rel_idx"][60:79]) == list(range(30, 47)) + [47, -1]
+    for m in (300, 2048):
+        o = runs["n64_c%d_hot_node" % m]
+        counts = np.bincount(o["ids"].ravel(), minlength=64)
+        assert len(np.unique(o["ids"], axis=0)) == 2 and counts.max() == m
+        assert (o["status"], o["iterations"], R.EXIT_NAMES[o["exit"]]) == (R.STATUS_OK, 1, "small error")
+    o = runs["n45_c120_nopins_suffix32_relax"]
+    assert (o["enabled"], o["iterations"], R.EXIT_NAMES[o["exit"]], o["lastDeformTime"]) == (45, 3, "small error", 15)
+    for name in ("n2047_c768", "n2048_c2048"):
+        assert (runs[name]["iterations"], R.EXIT_NAMES[runs[name]["exit"]]) == (1, "small error") and runs[name]["widest"] <= R.HALF_BAND
+    o = _run(deform_cases.single_unpinned_case())
+    assert o["status"] == R.STATUS_SINGULAR and len(o["ids"]) == 1
+
+
+@pytest.mark.parametrize("value", [np.nan, np.inf], ids=["nan", "inf"])
+def test_poisoned_constraint_fails_a_pivot_before_the_last_block(value):
+    """One constraint with a NaN / Inf source in the middle of the graph: the first non-positive pivot lies in a block column with
+    columns left to factorise, and the verdict is SINGULAR with the graph reset"""
+    c = deform_cases.poisoned_case(value)
+    with np.errstate(all="ignore"):
+        o = _run(c)
+    k = o["pivot_failed_at"] // R.NVAR
+    assert o["status"] == R.STATUS_SINGULAR and not o["applied"] and o["enabled"] == 64 and 0 < k < o["enabled"] - 1, k
+    assert 20 <= k <= 40  # around block 30
+    touched = o["ids"][np.isnan(o["weights"]).any(axis=1)]
+    assert len(touched) == 1 and k == touched.min()
+    assert np.array_equal(o["table"][:, 3:15], np.tile(np.array([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0], np.float32), (64, 1)))
+    # the staged singular input, by contrast, fails in its last block
+    s = _run(deform_cases.singular_case())
+    assert s["pivot_failed_at"] // R.NVAR == s["enabled"] - 1
 
 
 def test_singular_and_empty_systems(runs):
@@ -146,11 +191,11 @@ def test_constants_and_neighbours(host):
         assert got.tolist() == R.neighbours(n), n
 
 
-@pytest.mark.parametrize("case", deform_cases.staged_cases() + [deform_cases.no_enabled_case()], ids=repr)
+@pytest.mark.parametrize("case", deform_cases.staged_cases() + [deform_cases.no_enabled_case()] + EDGE_CASES, ids=repr)
 def test_host_build_of_the_row_header_equals_the_restatement_bit_for_bit(host, runs, case):
     o = runs[case.name]
     g = o["graph"]  # the graph AFTER the iterations: rotations and translations away from the identity
-    p = R.Problem(g, *R.pool_of(case.rows, case.src_time, case.pins))
+    p = R.Problem(g, *R.pool_of_batches(case.batches)[:4])
     nodes = np.ascontiguousarray(case.nodes, np.float32)
     ids, w = np.zeros((len(p.src), 4), np.int32), np.zeros((len(p.src), 4))
     src = np.ascontiguousarray(p.src, np.float32)
@@ -160,8 +205,8 @@ def test_host_build_of_the_row_header_equals_the_restatement_bit_for_bit(host, r
     for state in ("after", "identity"):
         if state == "identity":
             g = R.Graph(case.nodes)
-            g.enabled = g.times > case.last_deform_time
-            p = R.Problem(g, *R.pool_of(case.rows, case.src_time, case.pins))
+            g.enabled = g.times > (0 if case.relax else case.last_deform_time)
+            p = R.Problem(g, *R.pool_of_batches(case.batches)[:4])
         resid, indptr, cols, vals = _host_rows(host, g, p)
         want_r = R.residual(p)
         wi, wc, wv = R.jacobian(p)

@@ -40,7 +40,8 @@ def gpu_run(d, c, relax=False):
     d.setNodes(c.nodes)
     d.setLastDeformTime(c.last_deform_time)
     d.clearConstraints()
-    d.addConstraints(c.rows, c.src_time, c.pins)
+    for rows, src_time, pin in c.batches:
+        d.addConstraints(rows, src_time, pin)
     d.constrain(c.time, relax)
     r = d.result()
     ids, w = d.vertexWeights()
@@ -49,8 +50,8 @@ def gpu_run(d, c, relax=False):
     return out
 
 
-def ref_run(c, solver):
-    return R.constrain(c.nodes, c.rows, c.src_time, c.pins, c.time, False, c.last_deform_time, solver)
+def ref_run(c, solver, relax=False):
+    return R.constrain_batches(c.nodes, c.batches, c.time, relax, c.last_deform_time, solver)
 
 
 @pytest.fixture(scope="module")
