@@ -52,9 +52,9 @@ __device__ __forceinline__ f3 fill_vertex_at(const FillArgs& a, int sx, int sy, 
   return mk3((((float)x - a.cx) * z) * a.ifx, (((float)y - a.cy) * z) * a.ify, z);
 }
 
-// pixel (px, py) whose existing (predicted) values are sv / sn / si; ov / on / oi = what was stored
-__device__ __forceinline__ void fill_pixel_out(const FillArgs& a, int px, int py, const float4& sv, const float4& sn, const uchar4& si, float4& ov,
-                                               float4& on, uchar4& oi) {
+// pixel (px, py) whose existing (predicted) values are sv / sn / si; ov / on / oi = the filled values (nothing is stored)
+__device__ __forceinline__ void fill_pixel_values(const FillArgs& a, int px, int py, const float4& sv, const float4& sn, const uchar4& si, float4& ov,
+                                                  float4& on, uchar4& oi) {
   const size_t i = (size_t)py * a.cols + px;
   const float colsf = (float)a.cols, rowsf = (float)a.rows;
   const float tcx = ((float)px + 0.5f) / colsf, tcy = ((float)py + 0.5f) / rowsf;
@@ -66,7 +66,6 @@ __device__ __forceinline__ void fill_pixel_out(const FillArgs& a, int px, int py
     } else {
       ov = sv;
     }
-    a.out_vertex[i] = ov;
   }
   {  // fill_normal.frag:33-48 with geometry.glsl:48-58 forward differences
     if (sn.z == 0.f || a.pass_geom == 1) {
@@ -80,15 +79,22 @@ __device__ __forceinline__ void fill_pixel_out(const FillArgs& a, int px, int py
     } else {
       on = sn;
     }
-    a.out_normal[i] = on;
   }
   {  // fill_rgb.frag:29-37: samp.x + samp.y + samp.z == 0 on normalised bytes <=> all three zero
     if ((si.x == 0 && si.y == 0 && si.z == 0) || a.pass_rgb == 1)
       oi = a.rgba[i];
     else
       oi = si;
-    a.out_image[i] = oi;
   }
+}
+// the same, stored to the fill-in images
+__device__ __forceinline__ void fill_pixel_out(const FillArgs& a, int px, int py, const float4& sv, const float4& sn, const uchar4& si, float4& ov,
+                                               float4& on, uchar4& oi) {
+  const size_t i = (size_t)py * a.cols + px;
+  fill_pixel_values(a, px, py, sv, sn, si, ov, on, oi);
+  a.out_vertex[i] = ov;
+  a.out_normal[i] = on;
+  a.out_image[i] = oi;
 }
 __device__ __forceinline__ void fill_pixel(const FillArgs& a, int px, int py, const float4& sv, const float4& sn, const uchar4& si) {
   float4 ov, on;
@@ -173,12 +179,32 @@ __device__ __forceinline__ void fill_dense_test(const FillArgs& a, int t, int* s
   }
 }
 
-// the same decision from the 16 counters of the resolve pass: 1 = fill in (not dense enough)
+// the same decision from a count of non-black samples: 1 = fill in (not dense enough)
+__device__ __forceinline__ int dense_from_count(unsigned tot, int samples) { return ((float)(int)tot / (float)samples > 0.95f) ? 0 : 1; }
+// ... from the 16 counters of the resolve pass
 __device__ __forceinline__ int dense_from_counters(const unsigned* cnt, int samples) {
   unsigned tot = 0;
 #pragma unroll
   for (int k = 0; k < 16; ++k) tot += cnt[k * 16];
-  return ((float)(int)tot / (float)samples > 0.95f) ? 0 : 1;
+  return dense_from_count(tot, samples);
+}
+
+// the z-buffer cell (column-major: x * rows + y) of sample k of the W/20 x H/20 subsample: the pixel fill_sample_masks marks and
+// fill_dense_test reads, for the pass that takes the decision from the z-buffer itself (fusion_map.hip: k_predict_model)
+__host__ __device__ __forceinline__ int fill_sample_cell(int k, int cols, int rows) {
+  const int dw = cols / 20, dh = rows / 20;
+  const int i = k % dw, j = k / dw;
+  const int sx = texel(((float)i + 0.5f) / (float)dw, (float)cols, cols), sy = texel(((float)j + 0.5f) / (float)dh, (float)rows, rows);
+  return sx * rows + sy;
+}
+// host: all of them, for the rider that empties those cells after that pass; returns their number, 0 if two samples share a pixel
+// (the masks would count it once: never at 20 pixels per sample)
+inline int fill_sample_cells(int cols, int rows, int* cells /* (cols / 20) * (rows / 20) */) {
+  const int n = (cols / 20) * (rows / 20);
+  for (int k = 0; k < n; ++k) cells[k] = fill_sample_cell(k, cols, rows);
+  for (int k = 1; k < n; ++k)
+    if (cells[k] == cells[k - 1] || (k >= cols / 20 && cells[k] == cells[k - cols / 20])) return 0;
+  return n;
 }
 
 }  // namespace dms

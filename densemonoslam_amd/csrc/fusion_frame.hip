@@ -287,6 +287,15 @@ struct dms_fusion {
   unsigned* tickets = nullptr;  // 16 counters, 64 bytes apart (fused fill-in: non-black subsampled pixels of the tracking prediction); subsample masks at word 512
   bool fold_track_init = true;     // the tracker call's set-up as a block group of the model pyramid kernel (DMS_FOLD_TRACK_INIT=0: its own launch)
   bool dense_by_counters = false;  // this frame's denseEnough decision is taken from them by the model pyramid kernel
+  // fused_model_prediction: the tracking prediction of an eligible frame is resolved straight into the tracker's model maps
+  // (fusion_map.hip: k_predict_model) - its images have no other reader.  sample_cells: the z-buffer cells of the denseEnough
+  // samples (fill.hpp: fill_sample_cells), which that kernel's blocks all read and the tracker's SO3 launch empties.
+  int* sample_cells = nullptr;
+  int n_sample_cells = 0;
+  int predict_model_threads = 256;   // block shape (DMS_PREDICT_MODEL_THREADS = 256 / 512 / 1024 to compare: DESIGN.md 6)
+  bool one_call_now = false;         // the frame in flight came through dms_fusion_process_frame
+  bool model_written = false;        // this frame's tracking prediction took the fused path: track_frame launches no model pyramid kernel
+  long predict_fused = 0, predict_plain = 0;  // tracking predictions of either kind (dms_fusion_get_predict_stats)
   double host_wait_ms = 0.0;     // host time spent blocked on the bounded run-ahead ("host_wait" of dms_fusion_get_kernel_time)
   bool pre_valid = false;        // zbuf2 holds a projection
   int pre_tick = 0;              // ... rendered for this tick
@@ -399,6 +408,7 @@ void layout(dms_fusion* f, Carver& c) {
   f->zbuf2 = (unsigned long long*)c.take(N * 8);
   f->zbuf_assoc = (unsigned long long*)c.take(N * 8);
   f->tickets = (unsigned*)c.take(2048 + 512 + 1024);  // + the subsample masks (128 words at word 512) + the thumbnail masks (256 words at word 640)
+  f->sample_cells = (int*)c.take((size_t)((W < 2048 ? W : 2048) / 20) * ((H < 2048 ? H : 2048) / 20) * sizeof(int));
   f->state = (FrameState*)c.take(sizeof(FrameState));
   f->lazy_pose = (dms_pose_block*)c.take(sizeof(dms_pose_block));
 }
@@ -431,7 +441,14 @@ struct PredictOpts {
   bool have_prior = false;                    // tracking: the caller brought a pose
   const TrackInitArgs* track_init = nullptr;  // tracking: the tracker call's set-up, to ride on the resolve pass ...
   bool* track_init_taken = nullptr;           // ... and whether it did
+  const PredictModelArgs* model = nullptr;    // tracking, fused_model_prediction: resolve into the tracker's model maps (track_frame)
 };
+
+// a tracking prediction resolves the projection the previous frame's final prediction rendered ahead (zbuf2) when that is still
+// what it would render itself; otherwise it projects into zbuf
+static bool tracking_resolves_shared(const dms_fusion* f, bool have_prior) {
+  return f->pre_valid && !have_prior && f->pre_tick == f->tick && f->pre_version == f->model->version;
+}
 
 int predict_body(dms_fusion* f, hipStream_t s, Predict kind, const PredictOpts& o) {
   const bool dense_test = kind == Predict::tracking;  // ElasticFusion.cpp:165-167
@@ -470,10 +487,13 @@ int predict_body(dms_fusion* f, hipStream_t s, Predict kind, const PredictOpts& 
     StageTimer t(f->clock, s, "predict", f->profiling);
     const int W = f->p.width, H = f->p.height;
     bool done = false;
+    DMS_REQUIRE(!o.model || (fused && dense_test), "the fused prediction + model pass needs the fused fill-in of a tracking prediction");
+    if (o.model) f->dense_by_counters = false;  // (every block of that pass takes the decision itself)
     if (kind == Predict::tracking && f->pre_valid) {
-      if (!o.have_prior && f->pre_tick == f->tick && f->pre_version == f->model->version) {
+      if (tracking_resolves_shared(f, o.have_prior)) {
         if ((rc = splat_predict(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, o.confidence, f->tick, f->p.timeIdx, f->tick,
-                                f->p.timeDelta, 1, f->zbuf2, &f->pred, nullptr, 1, s, nullptr, nullptr, 1, fused, fused ? o.track_init : nullptr)))
+                                f->p.timeDelta, 1, f->zbuf2, &f->pred, nullptr, 1, s, nullptr, nullptr, 1, fused, fused ? o.track_init : nullptr,
+                                o.model)))
           return rc;
         done = true;
       } else if ((rc = clear_zbuf(f->zbuf2, W * H, s))) {  // stale: the resolve that would have cleaned it never runs
@@ -528,7 +548,7 @@ int predict_body(dms_fusion* f, hipStream_t s, Predict kind, const PredictOpts& 
         f->lazy_deferred += 1;
       } else if ((rc = splat_predict(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, o.confidence, f->tick, f->p.timeIdx, f->tick,
                               f->p.timeDelta, 1, f->zbuf, &f->pred, nullptr, 1, s, dual ? second : nullptr, dual ? f->zbuf2 : nullptr, 0,
-                              fused, fused ? o.track_init : nullptr)))
+                              fused, fused ? o.track_init : nullptr, o.model)))
         return rc;
       if (dual) {
         f->pre_valid = true;
@@ -551,8 +571,9 @@ int predict_body(dms_fusion* f, hipStream_t s, Predict kind, const PredictOpts& 
 int predict_view(dms_fusion* f, float confidence, hipStream_t s) { return predict_body(f, s, Predict::view, PredictOpts{confidence}); }
 
 // a frame's tracking prediction (ElasticFusion.cpp:165: confidence 0.7) with the denseEnough test
-int predict_tracking(dms_fusion* f, hipStream_t s, bool have_prior, const TrackInitArgs* track_init, bool* track_init_taken) {
-  return predict_body(f, s, Predict::tracking, PredictOpts{0.7f, nullptr, false, have_prior, track_init, track_init_taken});
+int predict_tracking(dms_fusion* f, hipStream_t s, bool have_prior, const TrackInitArgs* track_init, bool* track_init_taken,
+                     const PredictModelArgs* model = nullptr) {
+  return predict_body(f, s, Predict::tracking, PredictOpts{0.7f, nullptr, false, have_prior, track_init, track_init_taken, model});
 }
 
 // finalPredict (ElasticFusion.cpp:586); its last kernel mirrors the result block into the pinned host slot
@@ -723,6 +744,7 @@ void dms_fusion_default_params(dms_fusion_params* p, int width, int height, floa
   p->hybrid_loops = 0;
   p->lazy_final_prediction = 1;
   p->fused_associate = 1;
+  p->fused_model_prediction = 1;
 }
 
 // far depth cut-offs raise the static exponents of the trackers' first reductions (canon.hpp): set at creation and whenever the
@@ -826,6 +848,11 @@ int dms_fusion_create(dms_fusion** out, const dms_fusion_params* p) {
   if (const char* lm = getenv("DMS_LATE_MAIN")) f->late.forced = atoi(lm) != 0 ? 1 : 0;
   if (const char* lz = getenv("DMS_LAZY_FINAL_PREDICTION")) f->p.lazy_final_prediction = atoi(lz) != 0 ? 1 : 0;  // A/B runs
   if (const char* fa = getenv("DMS_FUSED_ASSOCIATE")) f->p.fused_associate = atoi(fa) != 0 ? 1 : 0;                // A/B runs
+  if (const char* fm = getenv("DMS_FUSED_MODEL_PREDICTION")) f->p.fused_model_prediction = atoi(fm) != 0 ? 1 : 0;  // A/B runs
+  if (const char* pt = getenv("DMS_PREDICT_MODEL_THREADS")) {
+    const int t = atoi(pt);
+    if (t == 256 || t == 512 || t == 1024) f->predict_model_threads = t;
+  }
   if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_inputs, hipEventDisableTiming);
   if (e == hipSuccess) e = hipMemset(f->arena, 0, f->arena_bytes);
   if (e == hipSuccess) e = hipHostMalloc((void**)&f->h_state, 4 * sizeof(FrameState), hipHostMallocMapped);
@@ -858,6 +885,11 @@ int dms_fusion_create(dms_fusion** out, const dms_fusion_params* p) {
     unsigned tm[256];
     f->thumb_masks_ok = thumb_sample_masks(p->width, p->height, tm);
     (void)hipMemcpy(f->tickets + 640, tm, sizeof(tm), hipMemcpyHostToDevice);
+    if (p->width <= 2048 && p->height <= 2048) {
+      std::vector<int> cells((size_t)(p->width / 20) * (p->height / 20));
+      f->n_sample_cells = fill_sample_cells(p->width, p->height, cells.data());
+      (void)hipMemcpy(f->sample_cells, cells.data(), (size_t)f->n_sample_cells * sizeof(int), hipMemcpyHostToDevice);
+    }
   }
   Pose16 I;
   for (int i = 0; i < 16; ++i) I.v[i] = (i % 5 == 0) ? 1.f : 0.f;
@@ -1224,7 +1256,32 @@ static int track_frame(dms_fusion* f, const float* inPose16, float weightMultipl
   memset(&early, 0, sizeof(early));
   bool early_taken = false;
   const bool want_early = f->p.hybrid_tracking && f->fold_track_init && !f->lost && odometry_early_init_args(f->odom, &fold, &early) != 0;
-  if ((rc = predict_tracking(f, s, inPose16 != nullptr, want_early ? &early : nullptr, &early_taken))) return rc;
+  // fused_model_prediction: nothing but the model pyramid kernel below can read this prediction's images when the frame is one
+  // dms_fusion_process_frame call (every reader after the frame gets the FINAL prediction, eager or materialised) without a block
+  // that looks at the view in between (NID key-framing, the loop blocks; a lost camera and frameToFrameRGB take the pass-through
+  // fill-in): then the prediction is resolved straight into the tracker's model maps, with the tracker call's set-up riding on it
+  // as it rides on the pyramid kernel, and the tracker's SO3 launch hosts the depth / intensity pyramid and empties the sampled
+  // z-buffer cells (odometry_model_views_begin says whether that launch exists: resident tracker, so3, not DMS_TRACK_FUSE /
+  // DMS_SO3_BESIDE_MODEL)
+  PredictModelArgs pm;
+  memset(&pm, 0, sizeof(pm));
+  f->model_written = false;
+  if (f->p.fused_model_prediction && f->one_call_now && f->p.hybrid_tracking && f->p.fused_fill_in && f->fold_track_init && !want_early && !f->lost &&
+      !f->p.nid_keyframing && !f->p.local_loop_closure && !f->p.hybrid_loops && !f->p.frameToFrameRGB && f->n_sample_cells > 0 &&
+      odometry_model_views_begin(f->odom, &fold, &pm.maps, &early, tracking_resolves_shared(f, inPose16 != nullptr) ? f->zbuf2 : f->zbuf,
+                                 f->sample_cells, f->n_sample_cells) != 0) {
+    pm.pose16 = f->state->cur.pose;
+    pm.flag_out = &f->state->fill_in;
+    pm.sample_cells = f->sample_cells;
+    pm.n_cells = f->n_sample_cells;
+    pm.samples = (f->p.width / 20) * (f->p.height / 20);
+    pm.threads = f->predict_model_threads;
+    f->model_written = true;
+  }
+  (f->model_written ? f->predict_fused : f->predict_plain) += 1;
+  if ((rc = predict_tracking(f, s, inPose16 != nullptr, (want_early || f->model_written) ? &early : nullptr, &early_taken,
+                             f->model_written ? &pm : nullptr)))
+    return rc;
   if (want_early && !early_taken) odometry_early_init_args(f->odom, nullptr, &early);  // (no fused resolve pass this frame: the set-up folds into the pyramid kernel as before)
   if (!f->p.hybrid_tracking) {  // with tracking on, the tracker's last kernel does this
     hipLaunchKernelGGL(k_frame_after_track, dim3(1), dim3(64), 0, s, f->state, weightMultiplier);
@@ -1235,7 +1292,9 @@ static int track_frame(dms_fusion* f, const float* inPose16, float weightMultipl
     StageTimer t(f->clock, s, "odom_init", f->profiling);
     // WARNING (reference): initICP* must be called before initRGB* (ElasticFusion.cpp:172)
     // (the set-up of the tracker call below rides on the pyramid kernel: no launch of its own, DMS_FOLD_TRACK_INIT=0 to compare)
-    if ((rc = odometry_initModel_fused(f->odom, f->pred.vertex.data, f->pred.normal.data, f->pred.image.data, f->fill.vertex.data,
+    // (fused_model_prediction: the prediction's kernel has written the model maps - the stage is kept, it encloses no launch)
+    if (!f->model_written &&
+        (rc = odometry_initModel_fused(f->odom, f->pred.vertex.data, f->pred.normal.data, f->pred.image.data, f->fill.vertex.data,
                                        f->fill.normal.data, f->fill.image.data, &f->state->fill_in, f->p.frameToFrameRGB ? 1 : 0,
                                        f->state->cur.pose, s, 1,  // (last pyramid step: inside the tracker's first kernel, below)
                                        f->dense_by_counters ? f->tickets : nullptr, (f->p.width / 20) * (f->p.height / 20),
@@ -1550,7 +1609,9 @@ int dms_fusion_process_frame(dms_fusion* f, const void* rgb_dev, int rgb_channel
   // what the loop solver cannot run on is refused before anything of the frame is enqueued
   DMS_REQUIRE(!f || !f->loop_solver || (f->model->sharers == 1 && f->clusters.size() == 1 && f->req_cluster == 0),
               "the loop solver needs a map this camera owns alone, without clusters");
+  if (f) f->one_call_now = true;  // (nobody can ask for an image between the halves: see track_frame)
   int rc = dms_fusion_process_frame_begin(f, rgb_dev, rgb_channels, depth_dev, inPose16, weightMultiplier, st);
+  if (f) f->one_call_now = false;
   if (rc) return rc;
   if (f->loop_solver && f->p.local_loop_closure && !f->cur_bootstrap && !f->lost) {
     const float* table_dev = nullptr;
@@ -1610,6 +1671,13 @@ int dms_fusion_get_lazy_stats(dms_fusion* f, int* eager, long* deferred, long* m
   if (deferred) *deferred = f->lazy_deferred;
   if (materialised) *materialised = f->lazy_materialised;
   if (stale) *stale = f->lazy_stale;
+  return DMS_OK;
+}
+
+int dms_fusion_get_predict_stats(dms_fusion* f, long* fused, long* plain) {
+  DMS_REQUIRE(f, "null argument");
+  if (fused) *fused = f->predict_fused;
+  if (plain) *plain = f->predict_plain;
   return DMS_OK;
 }
 

@@ -18,6 +18,7 @@
 #include "internal.hpp"
 #include "host_util.hpp"
 #include "track_init.hpp"
+#include "model_bodies.hpp"
 
 namespace dms {
 
@@ -1110,6 +1111,18 @@ __global__ __launch_bounds__(256) void k_splat_project(ProjArgs a, SurfelPlanes 
   }
 }
 
+// what a resolved pixel stores, from its winner: the image from the packed colour (RGBA8 render target: round(c * 255)) ...
+__device__ __forceinline__ uchar4 resolved_image(float packed) {
+  const f3 rgb = decode_color(packed);
+  return make_uchar4((unsigned char)f2i_rn(rgb.x * 255.0f), (unsigned char)f2i_rn(rgb.y * 255.0f), (unsigned char)f2i_rn(rgb.z * 255.0f), 255);
+}
+// ... and the vertex (x, y, z, confidence) and normal (x, y, z, radius) from the fragment's depth z
+__device__ __forceinline__ void resolved_geometry(const ProjArgs& a, const SplatSurfel& s, float z, int px, int py, float4& o_v, float4& o_n) {
+  const float fcx = (float)px + 0.5f, fcy = (float)py + 0.5f;
+  o_v = make_float4(((fcx - a.cx) * z) * (1.f / a.fx), ((fcy - a.cy) * z) * (1.f / a.fy), z, s.conf);
+  o_n = make_float4(s.nrm.x, s.nrm.y, s.nrm.z, s.rad);
+}
+
 // FILL: the hole fill-in of the prediction (fill.hpp) for the pixel just resolved — the launch and the re-read of the
 // three images that a separate fill-in pass costs are saved; the result-block mirror is done by block 0; for the
 // denseEnough decision the threads that own a subsampled pixel count the non-black ones into 16 counters, which the
@@ -1181,16 +1194,11 @@ __global__ __launch_bounds__(256) void k_splat_resolve(ProjArgs a, SurfelPlanes 
       continue;
     }
     const float4 cc = sp.col[i];
-    const f3 rgb = decode_color(cc.x);
-    // RGBA8 render target: round(c * 255)
-    const uchar4 o_img = make_uchar4((unsigned char)f2i_rn(rgb.x * 255.0f), (unsigned char)f2i_rn(rgb.y * 255.0f),
-                                     (unsigned char)f2i_rn(rgb.z * 255.0f), 255);
+    const uchar4 o_img = resolved_image(cc.x);
     image[p] = o_img;
     if (FILL && sampled && o_img.x > 0 && o_img.y > 0 && o_img.z > 0) atomicAdd(fa.dense_cnt + ((px + py) & 15) * 16, 1u);
-    const float z = c.z;
-    const float fcx = (float)px + 0.5f, fcy = (float)py + 0.5f;
-    const float4 o_v = make_float4(((fcx - a.cx) * z) * (1.f / a.fx), ((fcy - a.cy) * z) * (1.f / a.fy), z, s.conf);
-    const float4 o_n = make_float4(s.nrm.x, s.nrm.y, s.nrm.z, s.rad);
+    float4 o_v, o_n;
+    resolved_geometry(a, s, c.z, px, py, o_v, o_n);
     vertex[p] = o_v;
     normal[p] = o_n;
     // time = uint(colTime.z) into a 16-bit unsigned target
@@ -1207,11 +1215,127 @@ __global__ __launch_bounds__(256) void k_splat_resolve(ProjArgs a, SurfelPlanes 
   }
 }
 
+// fused_model_prediction: the tracking prediction of a frame whose seven images (pred.image / vertex / normal / time, fill.image /
+// vertex / normal) have ONE reader, the tracker's model pyramid kernel (prep.hip: k_model_levels012), resolved straight into that
+// kernel's outputs.  Each pixel is resolved and filled as k_splat_resolve<false, true> does it (the same helpers), the source is
+// selected as model_level0_body selects it, and level 0 of the model maps (vmap, nmap, float depth, intensity) is stored from the
+// registers; neither prediction nor fill-in image is written.  Levels 1 and 2 of vmap / nmap come from the same wave: its 8 x 8
+// tile (lane = 8 * column + row) holds 4 x 4 level-1 and 2 x 2 level-2 pixels, gathered by lane shuffles in resize4's operand order -
+// no halo, no barrier.  The depth / intensity pyramid (5 x 5 windows) is left to rider blocks of the tracker's SO3 launch, a kernel
+// boundary later (track.hip: So3Extra).
+//   denseEnough: the source choice depends on the whole resolved image (more than 95 % of the W/20 x H/20 samples non-black), and
+// there is no next launch to sum counters in.  Every block takes the decision itself before its tiles: per sample (pm.sample_cells:
+// the z-buffer cell of each) the cell, the winner's packed colour, the resolve's own decode and byte test - an integer count, so
+// every block gets the bits dense_from_counters gives.  No block waits for another.  For that the SAMPLED cells must outlive the
+// launch: no block empties them (clear_after skips them); a rider of the SO3 launch does, from the list of the same cells.
+//   NT: threads per block (NT / 64 tiles at a time); the grid is sized so that each wave takes about one tile, as the resolve's.
+template <int NT>
+__global__ __launch_bounds__(NT) void k_predict_model(ProjArgs a, SurfelPlanes sp, size_t cap, unsigned long long* __restrict__ zbuf, int clear_after,
+                                                      FillArgs fa, TrackInitArgs ti, PredictModelArgs pm) {
+  // the set-up of the tracker call that follows comes first in the grid, as in the model pyramid kernel (block 0's one-lane state
+  // set-up is the longest dependency chain of the launch)
+  if ((int)blockIdx.x < ti.blocks) {
+    track_init_body((int)blockIdx.x, ti.blocks, (int)threadIdx.x, NT, ti.st, ti.prior, ti.prior_pose16, ti.fx, ti.fy, ti.cx, ti.cy, ti.so3, ti.first_level,
+                    ti.sync_words, ti.n_sync, ti.inject_timeout, nullptr);
+    return;
+  }
+  const unsigned b = blockIdx.x - (unsigned)ti.blocks, nres = gridDim.x - (unsigned)ti.blocks;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  constexpr int kWaves = NT / 64;
+  __shared__ int s_cnt[kWaves];
+  {
+    // (the cells from the list the SO3 rider empties them by.  Computing them here - fill_sample_cell's two float divisions per
+    // sample - with four samples per thread in flight at a time was measured slower: DESIGN.md 6)
+    int cnt = 0;
+    for (int k = (int)threadIdx.x; k < pm.n_cells; k += NT) {
+      const unsigned long long key = zbuf[pm.sample_cells[k]];
+      if ((unsigned)(key >> 32) < 0xFFFFFFu) {
+        const uchar4 c = resolved_image(sp.col[(unsigned)(key & 0xFFFFFFFFull)].x);
+        cnt += (c.x > 0 && c.y > 0 && c.z > 0) ? 1 : 0;
+      }
+    }
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+    if (lane == 0) s_cnt[wave] = cnt;
+  }
+  __syncthreads();
+  unsigned tot = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) tot += (unsigned)s_cnt[w];
+  const bool useB = dense_from_count(tot, pm.samples) != 0;
+  if (b == 0 && threadIdx.x == 0) *pm.flag_out = useB ? 1 : 0;
+  const Pose34 P = load_pose34(pm.pose16);
+  const bool xf = pm.pose16 != nullptr;
+  const int rows0 = a.rows, rows1 = pm.maps.v[1].rows / 3, cols1 = pm.maps.v[1].cols, rows2 = pm.maps.v[2].rows / 3, cols2 = pm.maps.v[2].cols;
+  const int tiles_y = (a.rows + 7) >> 3, tiles_x = (a.cols + 7) >> 3, ntiles = tiles_x * tiles_y;
+  for (int t = xcd_block(b, nres, a.xcd) * kWaves + wave; t < ntiles; t += nres * kWaves) {  // (wave-uniform: all 64 lanes reach the shuffles)
+    const int tx = t / tiles_y, ty = t - tx * tiles_y;
+    const int px = tx * 8 + (lane >> 3), py = ty * 8 + (lane & 7);
+    const bool inside = px < a.cols && py < a.rows;
+    f3 rv = mk3(0.f, 0.f, 0.f), rn = mk3(0.f, 0.f, 0.f);
+    if (inside) {
+      const size_t cell = (size_t)px * a.rows + py;
+      const unsigned long long key = zbuf[cell];
+      if (clear_after) {
+        const bool sampled = ((fa.sample_mask[px >> 5] >> (px & 31)) & (fa.sample_mask[64 + (py >> 5)] >> (py & 31)) & 1u) != 0u;
+        if (!sampled) zbuf[cell] = kZClear;
+      }
+      float4 o_v = make_float4(0.f, 0.f, 0.f, 0.f), o_n = make_float4(0.f, 0.f, 0.f, 0.f);
+      uchar4 o_img = make_uchar4(0, 0, 0, 0);
+      if ((unsigned)(key >> 32) < 0xFFFFFFu) {
+        const unsigned i = (unsigned)(key & 0xFFFFFFFFull);
+        SplatSurfel s;
+        splat_vertex(a, sp.pos[i], sp.nrm + i, sp.times[(size_t)a.timeIdx * cap + i], s);
+        f3 c;
+        float zw;
+        splat_fragment(a, s, px, py, c, zw);
+        o_img = resolved_image(sp.col[i].x);
+        resolved_geometry(a, s, c.z, px, py, o_v, o_n);
+      }
+      if (useB) {  // (the fill-in images had no other reader: a dense view needs neither the depth nor the colour frame)
+        float4 ov, on;
+        uchar4 oi;
+        fill_pixel_values(fa, px, py, o_v, o_n, o_img, ov, on, oi);
+        o_v = ov;
+        o_n = on;
+        o_img = oi;
+      }
+      model_level0_store(px, py, rows0, o_v, o_n, o_img, P, xf, pm.maps.v[0], pm.maps.n[0], pm.maps.depth0, pm.maps.inten0, pm.maps.cutOff, rv, rn);
+    }
+    // level 1: the lane at an even column and an even row of the tile gathers (y, x), (y, x + 1), (y + 1, x), (y + 1, x + 1) = lanes
+    // + 0, + 8, + 1, + 9; level 2 from the UNTRANSFORMED level-1 values two columns / rows apart, as model_levels12_body forms it
+    f3 qv[4], qn[4], lv, ln;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int src = (lane & ~9) + (j & 1) * 8 + (j >> 1);
+      qv[j] = mk3(__shfl(rv.x, src, 64), __shfl(rv.y, src, 64), __shfl(rv.z, src, 64));
+      qn[j] = mk3(__shfl(rn.x, src, 64), __shfl(rn.y, src, 64), __shfl(rn.z, src, 64));
+    }
+    model_level_down(qv, qn, lv, ln);
+    const int x1 = px >> 1, y1 = py >> 1;
+    if ((lane & 9) == 0 && x1 < cols1 && y1 < rows1) store_transformed(pm.maps.v[1], pm.maps.n[1], rows1, y1, x1, lv, ln, P, xf);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int src = (lane & ~27) + (j & 1) * 16 + (j >> 1) * 2;
+      qv[j] = mk3(__shfl(lv.x, src, 64), __shfl(lv.y, src, 64), __shfl(lv.z, src, 64));
+      qn[j] = mk3(__shfl(ln.x, src, 64), __shfl(ln.y, src, 64), __shfl(ln.z, src, 64));
+    }
+    const int x2 = px >> 2, y2 = py >> 2;
+    if ((lane & 27) == 0 && x2 < cols2 && y2 < rows2) {  // then all four level-1 pixels exist
+      f3 v2, n2;
+      model_level_down(qv, qn, v2, n2);
+      store_transformed(pm.maps.v[2], pm.maps.n[2], rows2, y2, x2, v2, n2, P, xf);
+    }
+  }
+}
+
 int splat_predict(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, float maxDepth, float confThreshold, int time,
                   int timeIdx, int maxTime, int timeDelta, int active, unsigned long long* zbuf, dms_predict_out* out,
                   dms_image2d* depth_out, int zclean, hipStream_t s, const float* second_conf_time_maxtime, unsigned long long* zbuf2,
-                  int resolve_only, const FillArgs* fill, const TrackInitArgs* init) {
+                  int resolve_only, const FillArgs* fill, const TrackInitArgs* init, const PredictModelArgs* pm) {
   DMS_REQUIRE(m && pose && cam && zbuf, "null argument");
+  DMS_REQUIRE(!pm || (fill && !depth_out && fill->sample_mask && fill->mirror_words == 0 && !fill->thumb_block && zclean && pm->sample_cells && pm->n_cells == pm->samples &&
+                      pm->samples == (m->width / 20) * (m->height / 20) && pm->samples > 0 && pm->flag_out && (pm->threads == 256 || pm->threads == 512 || pm->threads == 1024)),
+              "the fused prediction + model pass takes the place of the fused resolve + fill-in pass of a tracking prediction only");
   DMS_REQUIRE(!init || init->blocks == 0 || (fill && !depth_out), "the tracker set-up rides on the fused resolve + fill-in pass only");
   DMS_REQUIRE(!m->pending_update, "a deferred update pass is still pending (index_map applies it)");
   DMS_REQUIRE(timeIdx >= 0 && timeIdx < DMS_MAX_SENSORS, "timeIdx out of range");
@@ -1257,6 +1381,19 @@ int splat_predict(dms_model* m, const dms_pose_block* pose, const dms_camera* ca
   if (depth_out) {
     hipLaunchKernelGGL((k_splat_resolve<true, false>), rg, dim3(256), 0, s, a, m->buf[m->cur], m->cap, zbuf, (uchar4*)nullptr,
                        (float4*)nullptr, (float4*)nullptr, (unsigned short*)nullptr, (float*)depth_out->data, zclean, no_fill, no_init);
+  } else if (pm) {
+    DMS_REQUIRE(fill->cols == W && fill->rows == H && W <= 2048 && H <= 2048 && pm->maps.v[0].cols == W && pm->maps.v[0].rows == 3 * H &&
+                    pm->maps.v[1].cols == W / 2 && pm->maps.v[1].rows == 3 * (H / 2) && pm->maps.v[2].cols == W / 4 && pm->maps.v[2].rows == 3 * (H / 4),
+                "model maps do not describe this prediction's pyramid");
+    const TrackInitArgs& ti = (init && init->blocks > 0) ? *init : no_init;
+    const int waves = pm->threads / 64, ntiles = ((W + 7) / 8) * ((H + 7) / 8);
+    const dim3 g(ti.blocks + min((ntiles + waves - 1) / waves, 2048));
+    if (pm->threads == 1024)
+      hipLaunchKernelGGL(k_predict_model<1024>, g, dim3(1024), 0, s, a, m->buf[m->cur], m->cap, zbuf, zclean, *fill, ti, *pm);
+    else if (pm->threads == 512)
+      hipLaunchKernelGGL(k_predict_model<512>, g, dim3(512), 0, s, a, m->buf[m->cur], m->cap, zbuf, zclean, *fill, ti, *pm);
+    else
+      hipLaunchKernelGGL(k_predict_model<256>, g, dim3(256), 0, s, a, m->buf[m->cur], m->cap, zbuf, zclean, *fill, ti, *pm);
   } else if (fill) {
     DMS_REQUIRE(fill->ex_image == (const uchar4*)out->image.data && fill->ex_vertex == (const float4*)out->vertex.data &&
                     fill->ex_normal == (const float4*)out->normal.data && fill->cols == W && fill->rows == H &&

@@ -25,6 +25,24 @@ struct ProjectRider {
   int copy_words;
 };
 
+// track.hip -> fusion_map.hip: the tracker's model maps (stacked vmap / nmap planes of the three levels, level 0 of the float depth
+// and intensity pyramids) as views, for the prediction pass that writes them itself (fused_model_prediction)
+struct ModelMapViews {
+  View<float> v[3], n[3], depth0;
+  View<unsigned char> inten0;
+  float cutOff;  // verticesToDepth
+};
+// fusion_map.hip: k_predict_model
+struct PredictModelArgs {
+  ModelMapViews maps;
+  const float* pose16;      // model pose for transformMaps
+  int* flag_out;            // the denseEnough decision (1 = fill-in values used), stored by block 0
+  const int* sample_cells;  // z-buffer cells of the decision's sample pixels (fill.hpp: fill_sample_cells), n_cells of them
+  int n_cells;
+  int samples;              // the decision's denominator, (W / 20) * (H / 20)
+  int threads;              // block shape: 256, 512 or 1024
+};
+
 // prep.hip
 int pyrDown(const dms_image2d* src, dms_image2d* dst, hipStream_t s);
 int createVMap(const dms_camera* intr, const dms_image2d* depth, dms_image2d* vmap, float cutoff, hipStream_t s);
@@ -92,7 +110,8 @@ int untranspose(const void* src, void* dst, int cols, int rows, int elem, hipStr
 int splat_predict(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, float maxDepth, float confThreshold, int time,
                   int timeIdx, int maxTime, int timeDelta, int active, unsigned long long* zbuf, dms_predict_out* out,
                   dms_image2d* depth_out, int zclean, hipStream_t s, const float* second_conf_time_maxtime = nullptr,
-                  unsigned long long* zbuf2 = nullptr, int resolve_only = 0, const FillArgs* fill = nullptr, const TrackInitArgs* init = nullptr);
+                  unsigned long long* zbuf2 = nullptr, int resolve_only = 0, const FillArgs* fill = nullptr, const TrackInitArgs* init = nullptr,
+                  const PredictModelArgs* pm = nullptr);
 int splat_project_only(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, float maxDepth, float confThreshold, int time,
                        int timeIdx, int maxTime, int timeDelta, int active, unsigned long long* zbuf, hipStream_t s, const ProjectRider* rider);
 int model_sample_graph(dms_model* m, int sampleRate, float* rows4_host, int max_rows, int* n_host, hipStream_t s);
@@ -129,6 +148,13 @@ int odometry_early_init_args(dms_odometry* o, const TrackFold* fold, TrackInitAr
 int odometry_initModel_fused(dms_odometry* o, const void* vA, const void* nA, const void* iA, const void* vB, const void* nB,
                              const void* iB, const int* flag_dev, int force_b_img, const float* pose16_dev, hipStream_t s,
                              int defer_last_step = 0, unsigned* dense_cnt = nullptr, int dense_samples = 0, const TrackFold* fold = nullptr);
+// fused_model_prediction: in place of odometry_initModel_fused when the caller's own kernel writes the model maps.  Returns 1 and
+// fills `mv` and `ti` (the folded set-up of the track call `fold` describes, to ride on that kernel) when the next
+// odometry_track_enqueue on this handle has a resident SO3 launch to host the riders - both steps of the depth / intensity pyramid
+// from the level-0 planes, and the emptying of the n_cells z-buffer cells `cells` of `zbuf` the caller's kernel leaves behind; 0
+// (nothing changed) otherwise.  The caller's kernel and the track call follow on one stream.
+int odometry_model_views_begin(dms_odometry* o, const TrackFold* fold, ModelMapViews* mv, TrackInitArgs* ti, unsigned long long* zbuf,
+                               const int* cells, int n_cells);
 int odometry_initLive_fused(dms_odometry* o, const void* verts, const void* norms, const void* rgba, const int* any_flag_dev,
                             hipStream_t s);
 int odometry_enable_ring(dms_odometry* o);

@@ -73,7 +73,18 @@ __device__ __forceinline__ void store_transformed(View<float> vmap, View<float> 
   }
 }
 
-// level 0: transformed maps, float depth (verticesToDepth) and intensity, one thread per pixel
+// level 0 of one pixel from its selected values: transformed maps, float depth (verticesToDepth) and intensity
+__device__ __forceinline__ void model_level0_store(int x, int y, int rows, const float4 v, const float4 q, const uchar4 c, const Pose34& P, bool xf,
+                                                   View<float> vmap, View<float> nmap, View<float> depth, View<unsigned char> inten, float cutOff, f3& rv,
+                                                   f3& rn) {
+  raw_maps(v, q, rv, rn);
+  store_transformed(vmap, nmap, rows, y, x, rv, rn, P, xf);
+  depth.at(y, x) = (v.z > cutOff || v.z <= 0.f) ? qnan() : v.z;
+  const float f = ((float)c.x * 0.114f + (float)c.y * 0.299f) + (float)c.z * 0.587f;
+  inten.at(y, x) = (unsigned char)f2i_rz(f);
+}
+
+// level 0: one thread per pixel
 // (tx, ty, BYv: the thread's place in a 64 x BYv block - the built-in indices of a 2-D launch, derived from the linear id in a 1-D one)
 __device__ __forceinline__ void model_level0_body(int tx, int ty, int BYv, int bx, int by, const ModelSrc& m, int rows, int cols, View<float> vmap,
                                                   View<float> nmap, View<float> depth, View<unsigned char> inten, float cutOff) {
@@ -87,11 +98,7 @@ __device__ __forceinline__ void model_level0_body(int tx, int ty, int BYv, int b
   const uchar4 c = (useB || m.force_b_img) ? m.iB[i] : m.iA[i];
   const Pose34 P = load_pose34(m.pose16);
   f3 rv, rn;
-  raw_maps(v, q, rv, rn);
-  store_transformed(vmap, nmap, rows, y, x, rv, rn, P, m.pose16 != nullptr);
-  depth.at(y, x) = (v.z > cutOff || v.z <= 0.f) ? qnan() : v.z;
-  const float f = ((float)c.x * 0.114f + (float)c.y * 0.299f) + (float)c.z * 0.587f;
-  inten.at(y, x) = (unsigned char)f2i_rz(f);
+  model_level0_store(x, y, rows, v, q, c, P, m.pose16 != nullptr, vmap, nmap, depth, inten, cutOff, rv, rn);
 }
 
 // resizeMap rule on four raw values
@@ -104,6 +111,12 @@ __device__ __forceinline__ f3 resize4(const f3& a, const f3& b, const f3& c, con
   n.z = (a.z + b.z + c.z + d.z) / 4;
   if (NORMALIZE) n = normalized3(n);
   return n;
+}
+
+// one level down from the four UNTRANSFORMED values under a pixel, in the order (y, x), (y, x + 1), (y + 1, x), (y + 1, x + 1)
+__device__ __forceinline__ void model_level_down(const f3 (&v)[4], const f3 (&n)[4], f3& lv, f3& ln) {
+  lv = resize4<false>(v[0], v[1], v[2], v[3]);
+  ln = resize4<true>(n[0], n[1], n[2], n[3]);
 }
 
 // levels 1 and 2: one thread per level-1 pixel (its 2x2 level-0 pixels); the four level-1 pixels under one level-2 pixel
@@ -128,8 +141,7 @@ __device__ __forceinline__ void model_levels12_body(int tx, int ty, int BYv, int
       const size_t i = (size_t)(2 * y1 + (j >> 1)) * cols0 + (2 * x1 + (j & 1));
       raw_maps(vs[i], ns[i], rv[j], rn[j]);
     }
-    lv = resize4<false>(rv[0], rv[1], rv[2], rv[3]);
-    ln = resize4<true>(rn[0], rn[1], rn[2], rn[3]);
+    model_level_down(rv, rn, lv, ln);
     store_transformed(v1, n1, rows1, y1, x1, lv, ln, P, m.pose16 != nullptr);
   }
   f3 qv[4], qn[4];
@@ -140,17 +152,46 @@ __device__ __forceinline__ void model_levels12_body(int tx, int ty, int BYv, int
     qn[j] = mk3(__shfl(ln.x, src, 64), __shfl(ln.y, src, 64), __shfl(ln.z, src, 64));
   }
   if (k == 0 && x2 < cols2 && y2 < rows2) {  // then all four level-1 pixels exist
-    const f3 a = resize4<false>(qv[0], qv[1], qv[2], qv[3]);
-    const f3 b = resize4<true>(qn[0], qn[1], qn[2], qn[3]);
+    f3 a, b;
+    model_level_down(qv, qn, a, b);
     store_transformed(v2, n2, rows2, y2, x2, a, b, P, m.pose16 != nullptr);
   }
 }
 
+// Where the depth / intensity pyramid steps take their level-0 taps from.  SourceTaps: the selected float4 / uchar4 sources, every
+// tap re-deriving what model_level0_body stores; PlaneTaps: the level-0 planes themselves, once a kernel boundary lies between their
+// writer and the step (the fused prediction + model kernel, fusion_map.hip).  The same values either way.
+struct SourceTaps {
+  const float4* vs;
+  const uchar4* is;
+  int cols0;
+  float cutOff;
+  __device__ __forceinline__ SourceTaps(const ModelSrc& m, int cols0_, float cutOff_) : cols0(cols0_), cutOff(cutOff_) {
+    const bool useB = model_use_b(m);
+    vs = useB ? m.vB : m.vA;
+    is = (useB || m.force_b_img) ? m.iB : m.iA;
+  }
+  __device__ __forceinline__ float depth(int gy, int gx) const {
+    const float z = vs[(size_t)gy * cols0 + gx].z;
+    return (z > cutOff || z <= 0.f) ? qnan() : z;
+  }
+  __device__ __forceinline__ unsigned char inten(int gy, int gx) const {
+    const uchar4 cc = is[(size_t)gy * cols0 + gx];
+    return (unsigned char)f2i_rz(((float)cc.x * 0.114f + (float)cc.y * 0.299f) + (float)cc.z * 0.587f);
+  }
+};
+struct PlaneTaps {
+  View<const float> d0;
+  View<const unsigned char> i0;
+  __device__ __forceinline__ float depth(int gy, int gx) const { return d0.at(gy, gx); }
+  __device__ __forceinline__ unsigned char inten(int gy, int gx) const { return i0.at(gy, gx); }
+};
+
 // first pyramid step of the model depth / intensity images, taken straight from the sources: every tap re-derives the
 // level-0 depth (verticesToDepth rule) and intensity (imageBGRToIntensity rule) that model_level0_body stores,
 // so the step does not have to wait for level 0
-template <int BYV>
-__device__ __forceinline__ void model_pyr_step1_body(int tx, int ty, int bx, int by, const ModelSrc& m, int rows0, int cols0, float cutOff, View<float> ddst,
+template <int BYV, class Taps>
+__device__ __forceinline__ void model_pyr_step1_taps(int tx, int ty, int bx, int by, const Taps& src, int rows0, int cols0, View<float> ddst,
                                                      View<unsigned char> idst) {
   constexpr int BX = 64, BY = BYV;
   // The block's 64 x BY outputs read a (2 * 64 + 3) x (2 * BY + 3) window of level 0: every source pixel is converted once,
@@ -159,9 +200,6 @@ __device__ __forceinline__ void model_pyr_step1_body(int tx, int ty, int bx, int
   constexpr int TW = 2 * BX + 3, TH = 2 * BY + 3;
   __shared__ float s_d[TH][TW + 1];
   __shared__ unsigned char s_c[TH][TW + 1];
-  const bool useB = model_use_b(m);
-  const float4* vs = useB ? m.vB : m.vA;
-  const uchar4* is = (useB || m.force_b_img) ? m.iB : m.iA;
   const int sx0 = 2 * (bx * BX) - 2, sy0 = 2 * (by * BY) - 2;
   for (int e = ty * BX + tx; e < TH * TW; e += BX * BY) {
     const int r = e / TW, c = e - r * TW;
@@ -169,11 +207,8 @@ __device__ __forceinline__ void model_pyr_step1_body(int tx, int ty, int bx, int
     float sv = qnan();
     unsigned char cv = 0;
     if (gx >= 0 && gy >= 0 && gx < cols0 && gy < rows0) {
-      const size_t i = (size_t)gy * cols0 + gx;
-      const float z = vs[i].z;
-      sv = (z > cutOff || z <= 0.f) ? qnan() : z;
-      const uchar4 cc = is[i];
-      cv = (unsigned char)f2i_rz(((float)cc.x * 0.114f + (float)cc.y * 0.299f) + (float)cc.z * 0.587f);
+      sv = src.depth(gy, gx);
+      cv = src.inten(gy, gx);
     }
     s_d[r][c] = sv;
     s_c[r][c] = cv;
@@ -187,6 +222,11 @@ __device__ __forceinline__ void model_pyr_step1_body(int tx, int ty, int bx, int
   ddst.at(y, x) = live::float_half(dt, x, y, cols0, rows0);
   idst.at(y, x) = live::u8_half(ct, x, y, cols0, rows0);
 }
+template <int BYV>
+__device__ __forceinline__ void model_pyr_step1_body(int tx, int ty, int bx, int by, const ModelSrc& m, int rows0, int cols0, float cutOff, View<float> ddst,
+                                                     View<unsigned char> idst) {
+  model_pyr_step1_taps<BYV>(tx, ty, bx, by, SourceTaps(m, cols0, cutOff), rows0, cols0, ddst, idst);
+}
 
 // BOTH pyramid steps of the model depth / intensity images for a tile of LEVEL-2 pixels, straight from the sources (round 6): the
 // block converts the level-0 window its outputs depend on into LDS (as model_pyr_step1_body does), takes the first step into a
@@ -194,18 +234,15 @@ __device__ __forceinline__ void model_pyr_step1_body(int tx, int ty, int bx, int
 // stores to the level-1 images - and the second step from that tile.  The pyramid's last step then needs no launch boundary after
 // the first one (it rides on the tracker's first launch otherwise: k_so3_level's rider blocks).  16 x 8 level-2 pixels per block
 // of NT threads: level-1 window 35 x 19, level-0 window 73 x 41.
-template <int NT>
-__device__ __forceinline__ void model_pyr_step2_body(int t, int bx, int by, const ModelSrc& m, int rows0, int cols0, float cutOff, int rows1, int cols1,
-                                                     View<float> ddst2, View<unsigned char> idst2) {
+template <int NT, class Taps>
+__device__ __forceinline__ void model_pyr_step2_taps(int t, int bx, int by, const Taps& src, int rows0, int cols0, int rows1, int cols1, View<float> ddst2,
+                                                     View<unsigned char> idst2) {
   constexpr int OX = 16, OY = 8;
   constexpr int W1 = 2 * OX + 3, H1 = 2 * OY + 3, W0 = 2 * W1 + 3, H0 = 2 * H1 + 3;
   __shared__ float s_d0[H0][W0 + 1];
   __shared__ unsigned char s_c0[H0][W0 + 1];
   __shared__ float s_d1[H1][W1 + 1];
   __shared__ unsigned char s_c1[H1][W1 + 1];
-  const bool useB = model_use_b(m);
-  const float4* vs = useB ? m.vB : m.vA;
-  const uchar4* is = (useB || m.force_b_img) ? m.iB : m.iA;
   const int x1o = 2 * (bx * OX) - 2, y1o = 2 * (by * OY) - 2;  // level-1 window origin
   const int x0o = 2 * x1o - 2, y0o = 2 * y1o - 2;              // level-0 window origin
   for (int e = t; e < H0 * W0; e += NT) {
@@ -214,11 +251,8 @@ __device__ __forceinline__ void model_pyr_step2_body(int t, int bx, int by, cons
     float sv = qnan();
     unsigned char cv = 0;
     if (gx >= 0 && gy >= 0 && gx < cols0 && gy < rows0) {
-      const size_t i = (size_t)gy * cols0 + gx;
-      const float z = vs[i].z;
-      sv = (z > cutOff || z <= 0.f) ? qnan() : z;
-      const uchar4 cc = is[i];
-      cv = (unsigned char)f2i_rz(((float)cc.x * 0.114f + (float)cc.y * 0.299f) + (float)cc.z * 0.587f);
+      sv = src.depth(gy, gx);
+      cv = src.inten(gy, gx);
     }
     s_d0[r][c] = sv;
     s_c0[r][c] = cv;
@@ -245,6 +279,11 @@ __device__ __forceinline__ void model_pyr_step2_body(int t, int bx, int by, cons
     ddst2.at(y, x) = live::float_half(dt, x, y, cols1, rows1);
     idst2.at(y, x) = live::u8_half(ct, x, y, cols1, rows1);
   }
+}
+template <int NT>
+__device__ __forceinline__ void model_pyr_step2_body(int t, int bx, int by, const ModelSrc& m, int rows0, int cols0, float cutOff, int rows1, int cols1,
+                                                     View<float> ddst2, View<unsigned char> idst2) {
+  model_pyr_step2_taps<NT>(t, bx, by, SourceTaps(m, cols0, cutOff), rows0, cols0, rows1, cols1, ddst2, idst2);
 }
 
 }  // namespace dms

@@ -93,6 +93,13 @@ struct dms_odometry {
   // the set-up of the next track call ran inside the model pyramid kernel (odometry_initModel_fused, fold_init): that call then
   // launches no kernel of its own before the SO3 level, which also carries the deferred pyramid step; the promised parameters
   bool init_folded = false;
+  // fused_model_prediction (odometry_model_views_begin): the caller's kernel wrote the model maps and level 0 of the depth /
+  // intensity pyramid; the next track call's SO3 launch carries BOTH pyramid steps from those planes and empties the z-buffer cells
+  // that kernel had to leave alone
+  bool pyr_from_planes = false;
+  unsigned long long* rider_zbuf = nullptr;
+  const int* rider_cells = nullptr;
+  int rider_n_cells = 0;
   // round 6: the call's set-up enqueued AHEAD, as rider blocks of the frame's first kernel (odometry_early_init_args), so that the SO3
   // stage can run inside the model pyramid launch (k_so3_model) instead of after it
   bool early_init = false, so3_in_model = false;
@@ -1407,6 +1414,10 @@ __global__ __launch_bounds__(kPB) void k_gn_level(TrackState* st, GnArgs a, Leve
 // Independent work riding on the SO3 launch when the call's set-up was folded into the model pyramid kernel (frame step):
 // the pyramid's deferred last step in gx * gy blocks of 64 x 8 pixels behind the nb_so3 resident blocks (gx = 0: none),
 // and the re-arming of the frame step's dense counters.
+// fused_model_prediction (planes != 0, k_so3_level only): the frame's prediction kernel wrote level 0 of the depth / intensity pyramid
+// itself, and BOTH steps ride here from those planes (d0, i0), independent of each other: g2x * g2y blocks of 16 x 8 level-2 pixels
+// (model_pyr_step2_taps: both steps in LDS) first, then gx * gy blocks of 64 x 8 level-1 pixels (model_pyr_step1_taps) into ddst /
+// idst, then ONE block that empties the n_cells z-buffer cells that kernel had to leave for its other blocks to read.
 struct So3Extra {
   int nb_so3, gx, gy;
   unsigned* zero16;
@@ -1414,7 +1425,16 @@ struct So3Extra {
   View<float> ddst;
   View<const unsigned char> isrc;
   View<unsigned char> idst;
+  int planes, g2x, g2y;
+  View<const float> d0;
+  View<const unsigned char> i0;
+  View<float> ddst2;
+  View<unsigned char> idst2;
+  unsigned long long* zbuf;
+  const int* cells;
+  int n_cells;
 };
+static inline int so3_rider_blocks(const So3Extra& ex) { return ex.planes ? ex.g2x * ex.g2y + ex.gx * ex.gy + 1 : ex.gx * ex.gy; }
 
 // ---------------------------------------------------------------------------------------
 // Persistent SO3 pre-alignment: all (<= 10) iterations in one launch, same protocol as k_gn_level
@@ -1560,7 +1580,21 @@ __global__ __launch_bounds__(kPB) void k_so3_level(TrackState* st, const unsigne
   // Blocks past the resident grid carry independent work of the same call: the model pyramid's last step, whose output the
   // first Gauss-Newton level reads (not this kernel) — see So3Extra.  They take no part in the all-reduce.
   if ((int)blockIdx.x >= ex.nb_so3) {
-    const int c = (int)blockIdx.x - ex.nb_so3, by = c / ex.gx, bx = c - by * ex.gx;
+    int c = (int)blockIdx.x - ex.nb_so3;
+    if (ex.planes) {
+      const PlaneTaps taps = {ex.d0, ex.i0};
+      const int n2 = ex.g2x * ex.g2y, n1 = ex.gx * ex.gy;
+      if (c < n2) {
+        model_pyr_step2_taps<kPB>((int)threadIdx.x, c % ex.g2x, c / ex.g2x, taps, ex.d0.rows, ex.d0.cols, ex.ddst.rows, ex.ddst.cols, ex.ddst2, ex.idst2);
+      } else if (c < n2 + n1) {
+        c -= n2;
+        model_pyr_step1_taps<kPB / 64>((int)(threadIdx.x & 63), (int)(threadIdx.x >> 6), c % ex.gx, c / ex.gx, taps, ex.d0.rows, ex.d0.cols, ex.ddst, ex.idst);
+      } else {
+        for (int k = (int)threadIdx.x; k < ex.n_cells; k += kPB) ex.zbuf[ex.cells[k]] = kZClear;
+      }
+      return;
+    }
+    const int by = c / ex.gx, bx = c - by * ex.gx;
     model_pyr_step_pixel(bx * 64 + (int)(threadIdx.x & 63), by * (kPB / 64) + (int)(threadIdx.x >> 6), ex.dsrc, ex.ddst, ex.isrc, ex.idst);
     return;
   }
@@ -2391,7 +2425,26 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
                 "track call differs from the one its folded set-up was prepared for");
     ex.zero16 = o->dense_cnt_zero;
     o->dense_cnt_zero = nullptr;
-    if (o->deferred_pyr) {
+    if (o->pyr_from_planes) {
+      o->pyr_from_planes = false;
+      DMS_REQUIRE(!o->fuse_coarse && !o->deferred_pyr, "the pyramid steps from the level-0 planes ride on the SO3 launch only");
+      dms_image2d d0 = o->lastDepth[0].img(), d1 = o->lastDepth[1].img(), d2 = o->lastDepth[2].img();
+      dms_image2d i0 = o->lastImage[0].img(), i1 = o->lastImage[1].img(), i2 = o->lastImage[2].img();
+      ex.planes = 1;
+      ex.gx = (d1.cols + 63) / 64;
+      ex.gy = (d1.rows + kPB / 64 - 1) / (kPB / 64);
+      ex.g2x = (d2.cols + 15) / 16;
+      ex.g2y = (d2.rows + 7) / 8;
+      ex.d0 = view<const float>(&d0);
+      ex.i0 = view<const unsigned char>(&i0);
+      ex.ddst = view<float>(&d1);
+      ex.idst = view<unsigned char>(&i1);
+      ex.ddst2 = view<float>(&d2);
+      ex.idst2 = view<unsigned char>(&i2);
+      ex.zbuf = o->rider_zbuf;
+      ex.cells = o->rider_cells;
+      ex.n_cells = o->rider_n_cells;
+    } else if (o->deferred_pyr) {
       o->deferred_pyr = false;
       dms_image2d d1 = o->lastDepth[1].img(), d2 = o->lastDepth[2].img(), i1 = o->lastImage[1].img(), i2 = o->lastImage[2].img();
       ex.gx = (d2.cols + 63) / 64;
@@ -2558,7 +2611,7 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
       StageTimer t(o->clock, s, "so3_level", timed(o));
       SolveCam cam = {o->fx, o->fy, o->cx, o->cy};
       ex.nb_so3 = nbp;
-      hipLaunchKernelGGL(k_so3_level, dim3(nbp + ex.gx * ex.gy), dim3(kPB), 0, s, o->state, (const unsigned char*)li.p, li.pitch,
+      hipLaunchKernelGGL(k_so3_level, dim3(nbp + so3_rider_blocks(ex)), dim3(kPB), 0, s, o->state, (const unsigned char*)li.p, li.pitch,
                          (const unsigned char*)ni.p, ni.pitch, ni.cols, ni.rows, o->ar, cam, first_level, 10, o->exp_bias + o->depth_bias, o->first_delay_for(nbp, 3), ex);
       DMS_CHECK_LAUNCH();
     } else
@@ -2953,6 +3006,55 @@ int odometry_early_init_args(dms_odometry* o, const TrackFold* fold, TrackInitAr
   return 1;
 }
 
+// the set-up of the track call `fold` describes as a block group of the kernel that prepares the call's model side: fills `ti` and
+// records the promise the call is checked against (odometry_track_enqueue)
+static void fold_init_args(dms_odometry* o, const TrackFold* fold, TrackInitArgs* ti) {
+  const int it1 = fold->pyramid ? 5 : 0, it2 = fold->pyramid ? 4 : 0;
+  ti->st = o->state;
+  ti->prior_pose16 = fold->prior_pose16;
+  ti->fx = o->fx;
+  ti->fy = o->fy;
+  ti->cx = o->cx;
+  ti->cy = o->cy;
+  ti->so3 = 1;
+  ti->first_level = it2 > 0 ? 2 : (it1 > 0 ? 1 : 0);
+  ti->sync_words = o->ar;
+  ti->n_sync = (int)((size_t)kArSets * kArWords / 2);
+  ti->inject_timeout = (!o->early_init && o->inject_timeouts > 0) ? 1 : 0;
+  if (!o->early_init && o->inject_timeouts > 0) o->inject_timeouts -= 1;
+  ti->blocks = 16;
+  o->init_folded = true;
+  o->folded_so3 = 1;
+  o->folded_first_level = ti->first_level;
+  o->folded_prior = fold->prior_pose16;
+}
+
+int odometry_model_views_begin(dms_odometry* o, const TrackFold* fold, ModelMapViews* mv, TrackInitArgs* ti, unsigned long long* zbuf,
+                               const int* cells, int n_cells) {
+  if (!o || !fold || !mv || !ti || !zbuf || !cells) return 0;
+  if (!o->resident || o->fuse_coarse || o->so3_beside_model || !fold->prior_pose16 || !fold->so3 || fold->interMap || so3_resident_blocks(o) <= 0) return 0;
+  for (int i = 0; i < DMS_NUM_PYRS; ++i) {
+    dms_image2d v = o->vmaps_g_prev[i].img(), n = o->nmaps_g_prev[i].img();
+    mv->v[i] = view<float>(&v);
+    mv->n[i] = view<float>(&n);
+  }
+  dms_image2d d0 = o->lastDepth[0].img(), i0 = o->lastImage[0].img();
+  mv->depth0 = view<float>(&d0);
+  mv->inten0 = view<unsigned char>(&i0);
+  mv->cutOff = o->maxDepthRGB;
+  memset(ti, 0, sizeof(*ti));
+  o->early_init = false;
+  o->so3_in_model = false;
+  o->deferred_pyr = false;
+  o->dense_cnt_zero = nullptr;
+  fold_init_args(o, fold, ti);
+  o->pyr_from_planes = true;
+  o->rider_zbuf = zbuf;
+  o->rider_cells = cells;
+  o->rider_n_cells = n_cells;
+  return 1;
+}
+
 // initICPModel + initRGBModel of the frame step in four launches (prep.hip, modelPyramidFused).
 // The operator-layer staging copy vmaps_tmp is not written on this path; nextDepth is aliased to
 // lastDepth by the caller, so nothing reads it.
@@ -2980,26 +3082,8 @@ int odometry_initModel_fused(dms_odometry* o, const void* vA, const void* nA, co
   TrackInitArgs ti;
   memset(&ti, 0, sizeof(ti));
   o->init_folded = false;
-  if (fold && fold->prior_pose16 && fold->so3 && !fold->interMap && defer_last_step && so3_resident_blocks(o) > 0) {
-    const int it1 = fold->pyramid ? 5 : 0, it2 = fold->pyramid ? 4 : 0;
-    ti.st = o->state;
-    ti.prior_pose16 = fold->prior_pose16;
-    ti.fx = o->fx;
-    ti.fy = o->fy;
-    ti.cx = o->cx;
-    ti.cy = o->cy;
-    ti.so3 = 1;
-    ti.first_level = it2 > 0 ? 2 : (it1 > 0 ? 1 : 0);
-    ti.sync_words = o->ar;
-    ti.n_sync = (int)((size_t)kArSets * kArWords / 2);
-    ti.inject_timeout = (!o->early_init && o->inject_timeouts > 0) ? 1 : 0;
-    if (!o->early_init && o->inject_timeouts > 0) o->inject_timeouts -= 1;
-    ti.blocks = 16;
-    o->init_folded = true;
-    o->folded_so3 = 1;
-    o->folded_first_level = ti.first_level;
-    o->folded_prior = fold->prior_pose16;
-  }
+  o->pyr_from_planes = false;
+  if (fold && fold->prior_pose16 && fold->so3 && !fold->interMap && defer_last_step && so3_resident_blocks(o) > 0) fold_init_args(o, fold, &ti);
   if (o->early_init && o->init_folded) {
     // The set-up ran a kernel ahead: the resident SO3 stage goes beside the model pyramid's groups in ONE launch (k_so3_model), the
     // pyramid's last step comes straight from the sources in that launch, nothing is deferred.

@@ -41,7 +41,7 @@ class FusionParams(C.Structure):
         ("nid_bins_depth", C.c_int), ("nid_pyramid_level", C.c_int),
         ("local_loop_closure", C.c_int), ("reloc", C.c_int), ("num_sensors", C.c_int), ("share_projection", C.c_int),
         ("fused_fill_in", C.c_int), ("hybrid_loops", C.c_int), ("lazy_final_prediction", C.c_int),
-        ("fused_associate", C.c_int),
+        ("fused_associate", C.c_int), ("fused_model_prediction", C.c_int),
     ]
 
 
@@ -127,6 +127,7 @@ lib.dms_relative_transform.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float
 lib.dms_pose_compose.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
 lib.dms_fusion_set_profiling.argtypes = [_P, _I]
 lib.dms_fusion_get_lazy_stats.argtypes = [_P, C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]
+lib.dms_fusion_get_predict_stats.argtypes = [_P, C.POINTER(C.c_long), C.POINTER(C.c_long)]
 
 
 class InterMapResult(C.Structure):
@@ -721,6 +722,12 @@ class ElasticFusion:
         e, d, m, st = C.c_int(0), C.c_long(0), C.c_long(0), C.c_long(0)
         check(lib.dms_fusion_get_lazy_stats(self.h, C.byref(e), C.byref(d), C.byref(m), C.byref(st)), "dms_fusion_get_lazy_stats")
         return {"eager": bool(e.value), "deferred": int(d.value), "materialised": int(m.value), "stale": int(st.value)}
+
+    def predictStats(self):
+        """fused_model_prediction: {fused, plain} tracking predictions so far (dms_fusion_get_predict_stats)"""
+        a, b = C.c_long(0), C.c_long(0)
+        check(lib.dms_fusion_get_predict_stats(self.h, C.byref(a), C.byref(b)), "dms_fusion_get_predict_stats")
+        return {"fused": int(a.value), "plain": int(b.value)}
 
     def loopConstraints(self):
         """Surface constraints of the last fetched frame's loop candidate: n x 7 float32

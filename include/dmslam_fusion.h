@@ -273,6 +273,17 @@ typedef struct dms_fusion_params {
    * Poses, results, the map and every image a caller can ask for are the same bits either way.  0: index map, then fuse, as
    * dms_index_map + dms_model_fuse.  DMS_FUSED_ASSOCIATE=0 / 1 in the environment overrides the field (A/B runs). */
   int fused_associate;
+  /* 1 (default): a frame's tracking prediction (ElasticFusion.cpp:165) is resolved straight into the tracker's model pyramid (:172-189)
+   * when nothing else can read its images: one kernel resolves and fills each pixel, selects predicted or filled values by the
+   * denseEnough decision and writes level 0 of the model maps plus levels 1 and 2 of the vertex / normal maps; the prediction and
+   * fill-in images are not written, the model pyramid kernel is not launched, and both steps of the depth / intensity pyramid
+   * ride on the tracker's SO3 launch.  Taken when all of these hold: one dms_fusion_process_frame call (not the _begin / _end pair,
+   * whose caller may ask for images between the halves), hybrid tracking, fused_fill_in, so3 with the resident tracker, the camera
+   * not lost, not the map's first frame, no nid_keyframing, local_loop_closure, hybrid_loops or frameToFrameRGB.  An armed frame
+   * block does not disqualify (it reads the FINAL prediction).  After the frame every reader gets the final prediction, so
+   * poses, results, the map, the tracker's buffers and every image a caller can ask for are the same bits either way.
+   * 0: resolve, then model pyramid.  DMS_FUSED_MODEL_PREDICTION=0 / 1 in the environment overrides the field (A/B runs). */
+  int fused_model_prediction;
 } dms_fusion_params;
 
 void dms_fusion_default_params(dms_fusion_params* p, int width, int height, float fx, float fy, float cx, float cy);
@@ -347,6 +358,9 @@ int dms_fusion_process_frame_end(dms_fusion* f, const float* graph_host, int gra
  * been asked for); deferred = frames that skipped theirs so far; materialised = skipped predictions rendered on demand; stale = those
  * of them that found a map changed since the frame.  Any pointer may be NULL. */
 int dms_fusion_get_lazy_stats(dms_fusion* f, int* eager, long* deferred, long* materialised, long* stale);
+/* fused_model_prediction: tracking predictions so far that went straight into the tracker's model pyramid (fused) and that were
+ * rendered as images for the model pyramid kernel (plain).  Either pointer may be NULL. */
+int dms_fusion_get_predict_stats(dms_fusion* f, long* fused, long* plain);
 /* Test hook for fused_associate: on = the frame's second index map does not hand the association's z-buffer back empty, so the next
  * fusing frame finds it in use and clears it itself - the path an error return between a frame's two index maps leaves behind. */
 int dms_fusion_debug_keep_assoc_zbuf(dms_fusion* f, int on);
