@@ -19,24 +19,20 @@
 
 #include <vector>
 
+#include "jpeg_core.hpp"
+
+// The decoder is three stages over plain data (the per-block and per-pixel arithmetic is csrc/jpeg_core.hpp, shared with the
+// device decoder of csrc/jpeg_dev.hip):
+//   parse      markers -> tables, frame and scan headers, Geometry, the offset of the entropy-coded data, the restart interval
+//   entropy    the entropy-coded data -> quantised coefficients: int16, 64 per block in natural order, blocks in the scan's MCU
+//              order, DC values already summed
+//   back half  coefficients -> RGB: dequantisation + inverse DCT into the component planes, upsampling + colour conversion
 namespace dms {
 namespace jpeg {
 
-struct Huff {
-  // canonical Huffman table: codes of length l lie in [mincode[l], maxcode[l]]; valptr[l] indexes the first of them
-  int mincode[17], maxcode[18], valptr[17];
-  unsigned char vals[256];
-  bool present = false;
-  // 9-bit lookahead: (length << 8) | symbol, 0 = longer code
-  unsigned short look[512];
-};
-
 struct Component {
   int id = 0, h = 1, v = 1, tq = 0, td = 0, ta = 0;
-  int dw = 0, dh = 0;          // downsampled size in samples (the "real" rows / columns)
-  int bw = 0, bh = 0;          // size in blocks, padded to whole MCUs
   int pred = 0;
-  std::vector<unsigned char> plane;  // bw * 8 x bh * 8 samples after the inverse DCT
 };
 
 struct Decoder {
@@ -50,9 +46,12 @@ struct Decoder {
 
   unsigned short qt[4][64] = {};
   bool qt_present[4] = {};
-  Huff dc[4], ac[4];
+  Huff dc[4] = {}, ac[4] = {};
+  bool dc_present[4] = {}, ac_present[4] = {};
   Component comp[3];
-  int ncomp = 0, width = 0, height = 0, hmax = 1, vmax = 1, restart_interval = 0;
+  int ncomp = 0, width = 0, height = 0, restart_interval = 0;
+  Geometry geo = {};
+  long blocks_done = 0;  // blocks the entropy stage completed (all of them, or those before the one it refused)
 
   bool fail(const char* what) {
     if (!err) err = what;
@@ -99,9 +98,7 @@ struct Decoder {
     skip(n);
     return v;
   }
-  static int extend(int v, int s) { return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v; }
-
-  bool build(Huff& h, const unsigned char* counts, const unsigned char* vals, int nvals) {
+  bool build(Huff& h, bool& present, const unsigned char* counts, const unsigned char* vals, int nvals) {
     int code = 0, k = 0;
     memset(h.look, 0, sizeof(h.look));
     for (int l = 1; l <= 16; ++l) {
@@ -121,142 +118,26 @@ struct Decoder {
       code <<= 1;
     }
     h.maxcode[17] = 0x7fffffff;
+    memset(h.vals, 0, sizeof(h.vals));
     memcpy(h.vals, vals, (size_t)nvals);
-    h.present = true;
+    present = true;
     return true;
   }
   int decode_symbol(const Huff& h) {
-    const int look = peek(9);
-    const unsigned short e = h.look[look];
-    if (e) {
-      skip(e >> 8);
-      return e & 0xff;
+    int len;
+    const int s = huff_symbol(h, (unsigned)peek(16), &len);
+    skip(len);
+    if (s < 0) {
+      fail(block_error_text(kErrBadCode));
+      return 0;
     }
-    int code = peek(16);
-    for (int l = 10; l <= 16; ++l) {
-      const int c = code >> (16 - l);
-      if (h.maxcode[l] >= 0 && c <= h.maxcode[l] && c >= h.mincode[l]) {
-        skip(l);
-        return h.vals[h.valptr[l] + c - h.mincode[l]];
-      }
-    }
-    fail("bad Huffman code");
-    skip(16);
-    return 0;
+    return s;
   }
 
-  // ---- one 8x8 block: coefficients (natural order) -> samples.  jidctint.c's arithmetic.
-  static inline int64_t descale(int64_t x, int n) { return (x + ((int64_t)1 << (n - 1))) >> n; }
-  static inline unsigned char range_limit(int64_t x) {  // libjpeg's table lookup with its 10-bit index mask
-    const int i = (int)(x & 1023);
-    if (i < 128) return (unsigned char)(128 + i);
-    if (i < 512) return 255;
-    if (i < 896) return 0;
-    return (unsigned char)(i - 896);
-  }
-  static void idct(const short* coef, const unsigned short* q, unsigned char* out, int stride) {
-    constexpr int CB = 13, P1 = 2;
-    constexpr int64_t F0_298 = 2446, F0_390 = 3196, F0_541 = 4433, F0_765 = 6270, F0_899 = 7373, F1_175 = 9633, F1_501 = 12299,
-                      F1_847 = 15137, F1_961 = 16069, F2_053 = 16819, F2_562 = 20995, F3_072 = 25172;
-    int64_t ws[64];
-    for (int c = 0; c < 8; ++c) {
-      const short* in = coef + c;
-      const unsigned short* qq = q + c;
-      if (!in[8] && !in[16] && !in[24] && !in[32] && !in[40] && !in[48] && !in[56]) {
-        const int64_t d = (int64_t)(in[0] * (int)qq[0]) * (1 << P1);
-        for (int r = 0; r < 8; ++r) ws[r * 8 + c] = d;
-        continue;
-      }
-      int64_t z2 = in[16] * (int)qq[16], z3 = in[48] * (int)qq[48];
-      int64_t z1 = (z2 + z3) * F0_541;
-      int64_t tmp2 = z1 + z3 * (-F1_847), tmp3 = z1 + z2 * F0_765;
-      z2 = in[0] * (int)qq[0];
-      z3 = in[32] * (int)qq[32];
-      int64_t tmp0 = (z2 + z3) * (1 << CB), tmp1 = (z2 - z3) * (1 << CB);
-      const int64_t tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-      tmp0 = in[56] * (int)qq[56];
-      tmp1 = in[40] * (int)qq[40];
-      tmp2 = in[24] * (int)qq[24];
-      tmp3 = in[8] * (int)qq[8];
-      z1 = tmp0 + tmp3;
-      z2 = tmp1 + tmp2;
-      z3 = tmp0 + tmp2;
-      int64_t z4 = tmp1 + tmp3;
-      const int64_t z5 = (z3 + z4) * F1_175;
-      tmp0 *= F0_298;
-      tmp1 *= F2_053;
-      tmp2 *= F3_072;
-      tmp3 *= F1_501;
-      z1 *= -F0_899;
-      z2 *= -F2_562;
-      z3 *= -F1_961;
-      z4 *= -F0_390;
-      z3 += z5;
-      z4 += z5;
-      tmp0 += z1 + z3;
-      tmp1 += z2 + z4;
-      tmp2 += z2 + z3;
-      tmp3 += z1 + z4;
-      ws[0 * 8 + c] = descale(tmp10 + tmp3, CB - P1);
-      ws[7 * 8 + c] = descale(tmp10 - tmp3, CB - P1);
-      ws[1 * 8 + c] = descale(tmp11 + tmp2, CB - P1);
-      ws[6 * 8 + c] = descale(tmp11 - tmp2, CB - P1);
-      ws[2 * 8 + c] = descale(tmp12 + tmp1, CB - P1);
-      ws[5 * 8 + c] = descale(tmp12 - tmp1, CB - P1);
-      ws[3 * 8 + c] = descale(tmp13 + tmp0, CB - P1);
-      ws[4 * 8 + c] = descale(tmp13 - tmp0, CB - P1);
-    }
-    for (int r = 0; r < 8; ++r) {
-      const int64_t* w = ws + r * 8;
-      unsigned char* o = out + (size_t)r * stride;
-      int64_t z2 = w[2], z3 = w[6];
-      int64_t z1 = (z2 + z3) * F0_541;
-      int64_t tmp2 = z1 + z3 * (-F1_847), tmp3 = z1 + z2 * F0_765;
-      int64_t tmp0 = (w[0] + w[4]) * (1 << CB), tmp1 = (w[0] - w[4]) * (1 << CB);
-      const int64_t tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-      tmp0 = w[7];
-      tmp1 = w[5];
-      tmp2 = w[3];
-      tmp3 = w[1];
-      z1 = tmp0 + tmp3;
-      z2 = tmp1 + tmp2;
-      z3 = tmp0 + tmp2;
-      int64_t z4 = tmp1 + tmp3;
-      const int64_t z5 = (z3 + z4) * F1_175;
-      tmp0 *= F0_298;
-      tmp1 *= F2_053;
-      tmp2 *= F3_072;
-      tmp3 *= F1_501;
-      z1 *= -F0_899;
-      z2 *= -F2_562;
-      z3 *= -F1_961;
-      z4 *= -F0_390;
-      z3 += z5;
-      z4 += z5;
-      tmp0 += z1 + z3;
-      tmp1 += z2 + z4;
-      tmp2 += z2 + z3;
-      tmp3 += z1 + z4;
-      constexpr int S = CB + P1 + 3;
-      o[0] = range_limit(descale(tmp10 + tmp3, S));
-      o[7] = range_limit(descale(tmp10 - tmp3, S));
-      o[1] = range_limit(descale(tmp11 + tmp2, S));
-      o[6] = range_limit(descale(tmp11 - tmp2, S));
-      o[2] = range_limit(descale(tmp12 + tmp1, S));
-      o[5] = range_limit(descale(tmp12 - tmp1, S));
-      o[3] = range_limit(descale(tmp13 + tmp0, S));
-      o[4] = range_limit(descale(tmp13 - tmp0, S));
-    }
-  }
-
-  bool decode_block(Component& c, int bx, int by) {
-    static const unsigned char zz[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                         41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                         30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-    short coef[64];
-    memset(coef, 0, sizeof(coef));
+  // ---- entropy stage: one 8x8 block -> 64 coefficients in natural order (coef is zeroed by the caller)
+  bool decode_block(Component& c, short* coef) {
     const int s = decode_symbol(dc[c.td]);
-    if (s > 15) return fail("bad DC size");
+    if (s > 15) return fail(block_error_text(kErrBadDcSize));
     if (s) c.pred += extend(get(s), s);
     coef[0] = (short)c.pred;
     for (int k = 1; k < 64;) {
@@ -268,13 +149,11 @@ struct Decoder {
         continue;
       }
       k += r;
-      if (k > 63) return fail("AC run past the block");
-      coef[zz[k]] = (short)extend(get(sz), sz);
+      if (k > 63) return fail(block_error_text(kErrAcRun));
+      coef[zigzag(k)] = (short)extend(get(sz), sz);
       ++k;
     }
-    if (err) return false;
-    idct(coef, qt[c.tq], c.plane.data() + (size_t)by * 8 * (c.bw * 8) + (size_t)bx * 8, c.bw * 8);
-    return true;
+    return !err;
   }
 
   // ---- markers
@@ -317,7 +196,7 @@ struct Decoder {
           int n = 0;
           for (int i = 0; i < 16; ++i) n += s[1 + i];
           if (tc > 1 || th > 3 || n > 256 || se - s < 17 + n) return fail("bad Huffman segment");
-          if (!build(tc ? ac[th] : dc[th], s + 1, s + 17, n)) return false;
+          if (!build(tc ? ac[th] : dc[th], tc ? ac_present[th] : dc_present[th], s + 1, s + 17, n)) return false;
           s += 17 + n;
         }
       } else if (m == 0xC0 || m == 0xC1) {  // SOF0 / SOF1: sequential, Huffman
@@ -347,7 +226,7 @@ struct Decoder {
           if (s[1 + 2 * i] != comp[i].id) return nosupport("scan component order");
           comp[i].td = s[2 + 2 * i] >> 4;
           comp[i].ta = s[2 + 2 * i] & 15;
-          if (comp[i].td > 3 || comp[i].ta > 3 || !dc[comp[i].td].present || !ac[comp[i].ta].present || !qt_present[comp[i].tq])
+          if (comp[i].td > 3 || comp[i].ta > 3 || !dc_present[comp[i].td] || !ac_present[comp[i].ta] || !qt_present[comp[i].tq])
             return fail("scan refers to a missing table");
         }
         got_scan = 1;
@@ -357,32 +236,56 @@ struct Decoder {
     }
   }
 
-  bool decode_scan() {
-    hmax = vmax = 1;
+  // ---- parse stage, second half: the scan's shape
+  bool setup_geometry() {
+    Geometry& g = geo;
+    g = Geometry();
+    g.hmax = g.vmax = 1;
     for (int i = 0; i < ncomp; ++i) {
       if (comp[i].h < 1 || comp[i].v < 1 || comp[i].h > 2 || comp[i].v > 2) return nosupport("sampling factors above 2");
-      hmax = comp[i].h > hmax ? comp[i].h : hmax;
-      vmax = comp[i].v > vmax ? comp[i].v : vmax;
+      g.hmax = comp[i].h > g.hmax ? comp[i].h : g.hmax;
+      g.vmax = comp[i].v > g.vmax ? comp[i].v : g.vmax;
     }
-    if (comp[0].h != hmax || comp[0].v != vmax || comp[1].h != 1 || comp[1].v != 1 || comp[2].h != 1 || comp[2].v != 1 || (hmax == 1 && vmax == 2))
+    if (comp[0].h != g.hmax || comp[0].v != g.vmax || comp[1].h != 1 || comp[1].v != 1 || comp[2].h != 1 || comp[2].v != 1 ||
+        (g.hmax == 1 && g.vmax == 2))
       return nosupport("chroma sampling other than 4:4:4, 4:2:2 or 4:2:0");
     if (width <= 0 || height <= 0) return fail("empty image");
-    const int mcux = (width + 8 * hmax - 1) / (8 * hmax), mcuy = (height + 8 * vmax - 1) / (8 * vmax);
+    g.width = width;
+    g.height = height;
+    g.restart_interval = restart_interval;
+    g.mcux = (width + 8 * g.hmax - 1) / (8 * g.hmax);
+    g.mcuy = (height + 8 * g.vmax - 1) / (8 * g.vmax);
+    int nb = 0, bytes = 0;
     for (int i = 0; i < ncomp; ++i) {
-      Component& c = comp[i];
-      c.dw = (width * c.h + hmax - 1) / hmax;
-      c.dh = (height * c.v + vmax - 1) / vmax;
-      c.bw = mcux * c.h;
-      c.bh = mcuy * c.v;
-      c.plane.assign((size_t)c.bw * 8 * c.bh * 8, 0);
-      c.pred = 0;
+      g.h[i] = comp[i].h;
+      g.v[i] = comp[i].v;
+      g.dw[i] = (width * comp[i].h + g.hmax - 1) / g.hmax;
+      g.dh[i] = (height * comp[i].v + g.vmax - 1) / g.vmax;
+      g.bw[i] = g.mcux * comp[i].h;
+      g.bh[i] = g.mcuy * comp[i].v;
+      g.off[i] = nb;
+      for (int k = 0; k < comp[i].h * comp[i].v; ++k) g.mcu_comp[nb++] = (unsigned char)i;
+      g.plane_off[i] = bytes;
+      bytes += g.bw[i] * 8 * g.bh[i] * 8;
     }
+    g.blocks_per_mcu = nb;
+    g.total_blocks = nb * g.mcux * g.mcuy;
+    g.plane_bytes = bytes;
+    return true;
+  }
+
+  // ---- entropy stage: the whole scan, sequentially.  coefs = geo.total_blocks * 64 zeroed values.
+  bool entropy(short* coefs) {
+    const Geometry& g = geo;
+    for (int i = 0; i < ncomp; ++i) comp[i].pred = 0;
     bitbuf = 0;
     bits = 0;
     hit_marker = false;
     int until_restart = restart_interval, next_rst = 0;
-    for (int my = 0; my < mcuy; ++my)
-      for (int mx = 0; mx < mcux; ++mx) {
+    short* coef = coefs;
+    blocks_done = 0;
+    for (int my = 0; my < g.mcuy; ++my)
+      for (int mx = 0; mx < g.mcux; ++mx) {
         if (restart_interval && until_restart == 0) {
           // byte-align, expect RSTn
           bitbuf = 0;
@@ -396,129 +299,178 @@ struct Decoder {
           until_restart = restart_interval;
           for (int i = 0; i < ncomp; ++i) comp[i].pred = 0;
         }
-        for (int i = 0; i < ncomp; ++i)
-          for (int v = 0; v < comp[i].v; ++v)
-            for (int h = 0; h < comp[i].h; ++h)
-              if (!decode_block(comp[i], mx * comp[i].h + h, my * comp[i].v + v)) return false;
+        for (int b = 0; b < g.blocks_per_mcu; ++b, coef += 64, ++blocks_done)
+          if (!decode_block(comp[g.mcu_comp[b]], coef)) return false;
         if (restart_interval) --until_restart;
       }
     return true;
   }
-
-  // ---- chroma to full resolution (jdsample.c: fullsize copy, h2v1_fancy_upsample, h2v2_fancy_upsample)
-  static void upsample(const Component& c, int hmax, int vmax, int width, int height, std::vector<unsigned char>& out) {
-    out.assign((size_t)width * height, 0);
-    const int stride = c.bw * 8, dw = c.dw, dh = c.dh;
-    const unsigned char* src = c.plane.data();
-    const int hx = hmax / c.h, vx = vmax / c.v;
-    if (hx == 1 && vx == 1) {
-      for (int y = 0; y < height; ++y) memcpy(&out[(size_t)y * width], src + (size_t)y * stride, (size_t)width);
-      return;
-    }
-    std::vector<unsigned char> row((size_t)dw * 2 + 2);
-    if (dw <= 2) {  // libjpeg only smooths planes more than two samples wide (jdsample.c jinit_upsampler): plain replication
-      for (int y = 0; y < height; ++y)
-        for (int x = 0; x < width; ++x) out[(size_t)y * width + x] = src[(size_t)(vx == 2 ? y >> 1 : y) * stride + (x >> 1)];
-      return;
-    }
-    for (int y = 0; y < height; ++y) {
-      const int r = vx == 2 ? y >> 1 : y;
-      const unsigned char* in0 = src + (size_t)r * stride;
-      if (vx == 1) {  // h2v1
-        unsigned char* o = row.data();
-        {
-          int v = in0[0];
-          *o++ = (unsigned char)v;
-          *o++ = (unsigned char)((v * 3 + in0[1] + 2) >> 2);
-          for (int x = 1; x < dw - 1; ++x) {
-            v = in0[x] * 3;
-            *o++ = (unsigned char)((v + in0[x - 1] + 1) >> 2);
-            *o++ = (unsigned char)((v + in0[x + 1] + 2) >> 2);
-          }
-          if (dw >= 2) {
-            v = in0[dw - 1];
-            *o++ = (unsigned char)((v * 3 + in0[dw - 2] + 1) >> 2);
-            *o++ = (unsigned char)v;
-          }
-        }
-      } else {  // h2v2: the nearer row 3/4, the further one 1/4; rows beyond the real ones are copies of the edge row
-        int r1 = (y & 1) ? r + 1 : r - 1;
-        if (r1 < 0) r1 = 0;
-        if (r1 > dh - 1) r1 = dh - 1;
-        const unsigned char* in1 = src + (size_t)r1 * stride;
-        unsigned char* o = row.data();
-        {
-          int thiscol = in0[0] * 3 + in1[0], nextcol = in0[1] * 3 + in1[1], lastcol;
-          *o++ = (unsigned char)((thiscol * 4 + 8) >> 4);
-          *o++ = (unsigned char)((thiscol * 3 + nextcol + 7) >> 4);
-          lastcol = thiscol;
-          thiscol = nextcol;
-          for (int x = 2; x < dw; ++x) {
-            nextcol = in0[x] * 3 + in1[x];
-            *o++ = (unsigned char)((thiscol * 3 + lastcol + 8) >> 4);
-            *o++ = (unsigned char)((thiscol * 3 + nextcol + 7) >> 4);
-            lastcol = thiscol;
-            thiscol = nextcol;
-          }
-          if (dw >= 2) {
-            *o++ = (unsigned char)((thiscol * 3 + lastcol + 8) >> 4);
-            *o++ = (unsigned char)((thiscol * 4 + 7) >> 4);
-          }
-        }
-      }
-      memcpy(&out[(size_t)y * width], row.data(), (size_t)width);
-    }
-  }
 };
 
-// Decodes `data` into width x height RGB8 (R, G, B byte order, rows top to bottom — libjpeg's JCS_RGB scanlines).
-// Returns 0, -1 (malformed / size mismatch) or -2 (a JPEG flavour this decoder does not handle); *err names the reason.
-inline int decode_rgb(const unsigned char* data, size_t len, int width, int height, unsigned char* rgb, const char** err) {
-  Decoder d;
+// parse stage: everything up to the first byte of the entropy-coded data (d.p afterwards).  0, -1 (malformed / size mismatch)
+// or -2 (a JPEG flavour this decoder does not handle); d.err names the reason.
+inline int parse(Decoder& d, const unsigned char* data, size_t len, int width, int height) {
   d.p = data;
   d.end = data + len;
+  if (len < 4 || data[0] != 0xFF || data[1] != 0xD8) {
+    d.fail("not a JPEG stream (no SOI)");
+    return -1;
+  }
+  int got = 0;
+  if (!d.parse_tables_and_scan(got) || !got) return d.unsupported ? -2 : -1;
+  if (d.width != width || d.height != height) {
+    d.fail("image size differs from the log's resolution");
+    return -1;
+  }
+  if (!d.setup_geometry()) return d.unsupported ? -2 : -1;
+  return 0;
+}
+
+// What the parallel entropy decoder needs besides the tables: the entropy-coded data cut at its restart markers, found with a byte
+// scan.  Segment i is bytes [start, end): `end` is the first 0xFF not followed by 0x00 (where the sequential bit reader starts to
+// supply zeros), the next segment starts behind the next RSTn.  The sequential decoder's two refusals at a restart ("missing
+// restart marker", "restart markers out of sequence") end the list early; *restart_err then names the one met while looking for
+// segment segs.size().
+struct Segment {
+  uint32_t start, end;
+};
+inline void find_segments(const unsigned char* data, size_t len, size_t scan_off, const Geometry& g, std::vector<Segment>& segs,
+                          const char** restart_err) {
+  const long mcus = (long)g.mcux * g.mcuy;
+  const long want = g.restart_interval ? (mcus + g.restart_interval - 1) / g.restart_interval : 1;
+  *restart_err = nullptr;
+  segs.clear();
+  size_t at = scan_off;
+  int next_rst = 0;
+  for (long s = 0; s < want; ++s) {
+    size_t e = at;
+    for (;;) {
+      const void* f = e < len ? memchr(data + e, 0xFF, len - e) : nullptr;
+      if (!f) {
+        e = len;
+        break;
+      }
+      e = (size_t)((const unsigned char*)f - data);
+      if (e + 1 >= len || data[e + 1] != 0x00) break;
+      e += 2;
+    }
+    Segment sg;
+    sg.start = (uint32_t)at;
+    sg.end = (uint32_t)e;
+    segs.push_back(sg);
+    if (s + 1 == want) break;
+    size_t q = e;
+    while (q < len && !(data[q] == 0xFF && q + 1 < len && data[q + 1] >= 0xD0 && data[q + 1] <= 0xD7)) ++q;
+    if (len - q < 2) {
+      *restart_err = "missing restart marker";
+      return;
+    }
+    if (data[q + 1] != 0xD0 + next_rst) {
+      *restart_err = "restart markers out of sequence";
+      return;
+    }
+    next_rst = (next_rst + 1) & 7;
+    at = q + 2;
+  }
+}
+
+// number of blocks of segment s (restart_interval MCUs, the last segment the remainder)
+inline long segment_blocks(const Geometry& g, long s) {
+  const long mcus = (long)g.mcux * g.mcuy;
+  if (!g.restart_interval) return mcus * g.blocks_per_mcu;
+  const long first = s * g.restart_interval;
+  const long n = mcus - first < g.restart_interval ? mcus - first : g.restart_interval;
+  return (n > 0 ? n : 0) * g.blocks_per_mcu;
+}
+
+// the lanes of the parallel entropy decoder: every segment cut into subsequences of S bytes
+inline void build_lanes(const Geometry& g, const std::vector<Segment>& segs, int S, std::vector<SegInfo>& si, std::vector<LaneInfo>& lanes) {
+  si.clear();
+  lanes.clear();
+  uint32_t block = 0;
+  for (size_t s = 0; s < segs.size(); ++s) {
+    SegInfo o;
+    o.start = segs[s].start;
+    o.end = segs[s].end;
+    o.first_lane = (uint32_t)lanes.size();
+    o.first_block = block;
+    o.nblocks = (uint32_t)segment_blocks(g, (long)s);
+    block += o.nblocks;
+    si.push_back(o);
+    const int n = segment_lanes(o.end - o.start, S);
+    for (int j = 0; j < n; ++j) {
+      LaneInfo l;
+      l.seg = (uint32_t)s;
+      l.first_byte = o.start + (uint32_t)j * (uint32_t)S;
+      l.stop_byte = j + 1 == n ? o.end : l.first_byte + (uint32_t)S;
+      l.flags = (j == 0 ? kLaneFirst : 0) | (j + 1 == n ? kLaneLast : 0);
+      lanes.push_back(l);
+    }
+  }
+}
+
+// back half, first step: coefficient block `b` (MCU order) -> its 8x8 samples in the component's plane
+inline void idct_block(const Geometry& g, const unsigned short* q, const short* coef, int b, unsigned char* planes) {
+  const int bpm = g.blocks_per_mcu, mcu = b / bpm, j = b - mcu * bpm, c = g.mcu_comp[j];
+  const int vy = (j - g.off[c]) / g.h[c], hx = (j - g.off[c]) - vy * g.h[c];
+  const int bx = (mcu % g.mcux) * g.h[c] + hx, by = (mcu / g.mcux) * g.v[c] + vy;
+  const int stride = g.bw[c] * 8;
+  unsigned char* out = planes + g.plane_off[c] + (size_t)by * 8 * stride + (size_t)bx * 8;
+  int64_t ws[64];
+  for (int col = 0; col < 8; ++col) {
+    int d[8];
+    int64_t w[8];
+    for (int r = 0; r < 8; ++r) d[r] = dequant(coef[r * 8 + col], q[r * 8 + col]);
+    idct_column(d, w);
+    for (int r = 0; r < 8; ++r) ws[r * 8 + col] = w[r];
+  }
+  for (int r = 0; r < 8; ++r) idct_row(ws + r * 8, out + (size_t)r * stride);
+}
+
+// back half: coefficients (entropy stage) -> RGB8, R and B exchanged where `flip`.  qt[c] = component c's quantisation table.
+inline void back_half(const Geometry& g, const unsigned short (*qt)[64], const short* coefs, unsigned char* rgb, int flip) {
+  std::vector<unsigned char> planes((size_t)g.plane_bytes);
+  for (int b = 0; b < g.total_blocks; ++b) idct_block(g, qt[g.mcu_comp[b % g.blocks_per_mcu]], coefs + (size_t)b * 64, b, planes.data());
+  const unsigned char* py = planes.data() + g.plane_off[0];
+  const unsigned char* pb = planes.data() + g.plane_off[1];
+  const unsigned char* pr = planes.data() + g.plane_off[2];
+  const int hx = g.hmax / g.h[1], vx = g.vmax / g.v[1];
+  // the colour terms as libjpeg's tables (one evaluation per value instead of one per pixel)
+  int cr_r[256], cb_b[256];
+  int64_t cr_g[256], cb_g[256];
+  for (int i = 0; i < 256; ++i) {
+    cr_r[i] = ycc_cr_r(i);
+    cb_b[i] = ycc_cb_b(i);
+    cr_g[i] = ycc_cr_g(i);
+    cb_g[i] = ycc_cb_g(i);
+  }
+  const int ro = flip ? 2 : 0, bo = flip ? 0 : 2;
+  for (int y = 0; y < g.height; ++y) {
+    unsigned char* o = rgb + (size_t)y * g.width * 3;
+    for (int x = 0; x < g.width; ++x, o += 3) {
+      const int Y = py[(size_t)y * (g.bw[0] * 8) + x];
+      const int B = upsampled_sample(pb, g.bw[1] * 8, g.dw[1], g.dh[1], hx, vx, x, y);
+      const int R = upsampled_sample(pr, g.bw[2] * 8, g.dw[2], g.dh[2], hx, vx, x, y);
+      o[ro] = clamp255(Y + cr_r[R]);
+      o[1] = clamp255(Y + (int)((cb_g[B] + cr_g[R]) >> 16));
+      o[bo] = clamp255(Y + cb_b[B]);
+    }
+  }
+}
+
+inline int decode_rgb(const unsigned char* data, size_t len, int width, int height, unsigned char* rgb, const char** err) {
+  Decoder d;
   auto out = [&](int rc) {
     if (err) *err = d.err ? d.err : "";
     return rc;
   };
-  if (len < 4 || data[0] != 0xFF || data[1] != 0xD8) {
-    d.fail("not a JPEG stream (no SOI)");
-    return out(-1);
-  }
-  int got = 0;
-  if (!d.parse_tables_and_scan(got) || !got) return out(d.unsupported ? -2 : -1);
-  if (d.width != width || d.height != height) {
-    d.fail("image size differs from the log's resolution");
-    return out(-1);
-  }
-  if (!d.decode_scan()) return out(d.unsupported ? -2 : -1);
-  std::vector<unsigned char> cb, cr;
-  Decoder::upsample(d.comp[1], d.hmax, d.vmax, width, height, cb);
-  Decoder::upsample(d.comp[2], d.hmax, d.vmax, width, height, cr);
-  // jdcolor.c build_ycc_rgb_table / ycc_rgb_convert
-  int cr_r[256], cb_b[256];
-  int64_t cr_g[256], cb_g[256];
-  for (int i = 0; i < 256; ++i) {
-    const int64_t x = i - 128;
-    cr_r[i] = (int)((91881 * x + 32768) >> 16);
-    cb_b[i] = (int)((116130 * x + 32768) >> 16);
-    cr_g[i] = -46802 * x;
-    cb_g[i] = -22554 * x + 32768;
-  }
-  auto clamp = [](int v) { return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v)); };
-  const int ystride = d.comp[0].bw * 8;
-  for (int y = 0; y < height; ++y) {
-    const unsigned char* yr = d.comp[0].plane.data() + (size_t)y * ystride;
-    const unsigned char* br = &cb[(size_t)y * width];
-    const unsigned char* rr = &cr[(size_t)y * width];
-    unsigned char* o = rgb + (size_t)y * width * 3;
-    for (int x = 0; x < width; ++x) {
-      const int Y = yr[x], B = br[x], R = rr[x];
-      o[3 * x + 0] = clamp(Y + cr_r[R]);
-      o[3 * x + 1] = clamp(Y + (int)((cb_g[B] + cr_g[R]) >> 16));
-      o[3 * x + 2] = clamp(Y + cb_b[B]);
-    }
-  }
+  const int rc = parse(d, data, len, width, height);
+  if (rc) return out(rc);
+  std::vector<short> coefs((size_t)d.geo.total_blocks * 64, 0);
+  if (!d.entropy(coefs.data())) return out(d.unsupported ? -2 : -1);
+  unsigned short qt[3][64];
+  for (int i = 0; i < 3; ++i) memcpy(qt[i], d.qt[d.comp[i].tq], sizeof(qt[i]));
+  back_half(d.geo, qt, coefs.data(), rgb, 0);
   return out(0);
 }
 

@@ -1,5 +1,6 @@
 """ctypes mirror of include/dmslam_io.h: eflcm.Frame messages, LCM event logs and .klg logs
-(the reference's LcmHandler / RawLcmLogReader / RawLogReader).  Host-side only."""
+(the reference's LcmHandler / RawLcmLogReader / RawLogReader); and of include/dmslam_io_device.h: the same readers
+with both destinations in device memory, JPEG colour decoded on the GPU."""
 import ctypes as C
 
 import numpy as np
@@ -79,6 +80,13 @@ class Frame:
         check(lib.dms_frame_unpack(C.byref(m), width, height, int(flipColors), d.ctypes.data_as(_P), rgb.ctypes.data_as(_P)), "dms_frame_unpack")
         return d, rgb
 
+    def unpack_device(self, jd, depth_dev, rgb_dev, flipColors=False, stream=None):
+        """unpack() with both destinations in device memory (dms_frame_unpack_device): jd is a JpegDevice, depth_dev / rgb_dev are
+        device pointers; everything is enqueued on `stream`."""
+        m = self._msg()
+        check(lib.dms_frame_unpack_device(jd.h, C.byref(m), jd.width, jd.height, int(bool(flipColors)), _P(depth_dev), _P(rgb_dev), _P(stream)),
+              "dms_frame_unpack_device")
+
 
 def jpeg_decode(data, width, height):
     """Baseline JPEG -> (H, W, 3) u8 in libjpeg's R, G, B order (dms_jpeg_decode)."""
@@ -134,6 +142,15 @@ class KlgReader:
             check(rc, "dms_klg_next")
             yield ts.value, d, rgb
 
+    def next_device(self, jd, depth_dev, rgb_dev, stream=None):
+        """The next frame into device memory (dms_klg_next_device), enqueued on `stream`: its timestamp, or None at the end."""
+        ts = C.c_int64(0)
+        rc = lib.dms_klg_next_device(self.h, jd.h, _P(depth_dev), _P(rgb_dev), C.byref(ts), _P(stream))
+        if rc == DMS_EOF:
+            return None
+        check(rc, "dms_klg_next_device")
+        return ts.value
+
     def rewind(self):
         check(lib.dms_klg_rewind(self.h))
 
@@ -141,3 +158,78 @@ class KlgReader:
         if self.h:
             lib.dms_klg_close(self.h)
             self.h = None
+
+
+# ---- include/dmslam_io_device.h: JPEG colour decoded on the GPU, readers with both destinations in device memory ----
+
+class JpegDevInfo(C.Structure):
+    _fields_ = [("entropy_on_host", C.c_int), ("subsequence_bytes", C.c_int), ("segments", C.c_int), ("subsequences", C.c_int),
+                ("rounds", C.c_int), ("settled_lanes", C.c_int), ("blocks", C.c_int)]
+
+
+JPEG_DEV_DEFAULT_SUBSEQUENCE, JPEG_DEV_ROUNDS = 64, 12
+lib.dms_jpeg_dev_create.argtypes = [C.POINTER(_P), C.c_int, C.c_int, C.c_size_t, C.c_int]
+lib.dms_jpeg_dev_destroy.argtypes = [_P]
+lib.dms_jpeg_dev_set_subsequence_bytes.argtypes = [_P, C.c_int]
+lib.dms_jpeg_dev_set_entropy_on_host.argtypes = [_P, C.c_int]
+lib.dms_jpeg_dev_set_image_size.argtypes = [_P, C.c_int, C.c_int]
+lib.dms_jpeg_dev_decode.argtypes = [_P, _P, C.c_size_t, C.c_int, C.c_int, _P, _P]
+lib.dms_jpeg_dev_status.argtypes = [_P, C.POINTER(JpegDevInfo)]
+lib.dms_jpeg_dev_get_coefficients.argtypes = [_P, _P, C.c_size_t, C.POINTER(C.c_int)]
+lib.dms_frame_unpack_device.argtypes = [_P, C.POINTER(FrameMsg), C.c_int, C.c_int, C.c_int, _P, _P, _P]
+lib.dms_klg_next_device.argtypes = [_P, _P, _P, _P, C.POINTER(C.c_int64), _P]
+
+
+class JpegDevice:
+    """dms_jpeg_dev: baseline JPEG -> RGB8 in device memory; `rgb_dev` arguments are device pointers (int) of
+    width * height * 3 bytes, `stream` a stream handle (int) or None."""
+
+    def __init__(self, width, height, max_stream_bytes=1 << 20, slots=3):
+        self.h = _P()
+        self.width, self.height, self.slots = width, height, slots
+        check(lib.dms_jpeg_dev_create(C.byref(self.h), width, height, max_stream_bytes, slots), "dms_jpeg_dev_create")
+
+    def set_subsequence_bytes(self, n):
+        check(lib.dms_jpeg_dev_set_subsequence_bytes(self.h, int(n)), "dms_jpeg_dev_set_subsequence_bytes")
+
+    def set_image_size(self, width, height):
+        """streams of another size, no larger than the one the object was created for"""
+        check(lib.dms_jpeg_dev_set_image_size(self.h, width, height), "dms_jpeg_dev_set_image_size")
+        self.width, self.height = width, height
+
+    def set_entropy_on_host(self, on):
+        """the mode Frame.unpack_device / KlgReader.next_device decode in (default: on the host, the measured winner)"""
+        check(lib.dms_jpeg_dev_set_entropy_on_host(self.h, int(bool(on))), "dms_jpeg_dev_set_entropy_on_host")
+
+    def decode(self, data, rgb_dev, flipColors=False, entropy_on_host=True, stream=None):
+        """enqueues the decode on `stream` and returns; parse-stage refusals raise at once"""
+        data = bytes(data)
+        check(lib.dms_jpeg_dev_decode(self.h, data, len(data), int(bool(flipColors)), int(bool(entropy_on_host)), _P(rgb_dev), _P(stream)),
+              "dms_jpeg_dev_decode")
+
+    def status(self):
+        """waits for the last decode; raises DmsError (DMS_ERR_FORMAT) where the device met a malformed block"""
+        info = JpegDevInfo()
+        rc = lib.dms_jpeg_dev_status(self.h, C.byref(info))
+        self.info = info
+        check(rc, "dms_jpeg_dev_status")
+        return info
+
+    def coefficients(self):
+        """(blocks, 64) int16 of the last decode: natural order, the scan's MCU order, DC values summed"""
+        cap = 6 * ((self.width + 7) // 8) * ((self.height + 7) // 8) + 6
+        out = np.zeros((cap, 64), np.int16)
+        n = C.c_int(0)
+        check(lib.dms_jpeg_dev_get_coefficients(self.h, out.ctypes.data_as(_P), cap, C.byref(n)), "dms_jpeg_dev_get_coefficients")
+        return out[:n.value].copy()
+
+    def close(self):
+        if self.h:
+            lib.dms_jpeg_dev_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
