@@ -439,8 +439,7 @@ struct PredictOpts {
   void* state_mirror = nullptr;               // final: the frame's pinned result slot, written by the last kernel
   bool one_call = false;                      // final: the frame came through dms_fusion_process_frame
   bool have_prior = false;                    // tracking: the caller brought a pose
-  const TrackInitArgs* track_init = nullptr;  // tracking: the tracker call's set-up, to ride on the resolve pass ...
-  bool* track_init_taken = nullptr;           // ... and whether it did
+  const TrackInitArgs* track_init = nullptr;  // tracking, fused_model_prediction: the tracker call's set-up, to ride on that pass
   const PredictModelArgs* model = nullptr;    // tracking, fused_model_prediction: resolve into the tracker's model maps (track_frame)
 };
 
@@ -557,7 +556,6 @@ int predict_body(dms_fusion* f, hipStream_t s, Predict kind, const PredictOpts& 
       }
     }
   }
-  if (o.track_init_taken) *o.track_init_taken = fused != nullptr && o.track_init && o.track_init->blocks > 0;
   if (!fused) {
     StageTimer t(f->clock, s, "fill_in", f->profiling);
     if ((rc = fill_in(&f->pred, &f->depth_filtered, &f->rgba, &f->cam, f->lost ? 1 : 0, (f->lost || f->p.frameToFrameRGB) ? 1 : 0, &f->fill,
@@ -571,9 +569,8 @@ int predict_body(dms_fusion* f, hipStream_t s, Predict kind, const PredictOpts& 
 int predict_view(dms_fusion* f, float confidence, hipStream_t s) { return predict_body(f, s, Predict::view, PredictOpts{confidence}); }
 
 // a frame's tracking prediction (ElasticFusion.cpp:165: confidence 0.7) with the denseEnough test
-int predict_tracking(dms_fusion* f, hipStream_t s, bool have_prior, const TrackInitArgs* track_init, bool* track_init_taken,
-                     const PredictModelArgs* model = nullptr) {
-  return predict_body(f, s, Predict::tracking, PredictOpts{0.7f, nullptr, false, have_prior, track_init, track_init_taken, model});
+int predict_tracking(dms_fusion* f, hipStream_t s, bool have_prior, const TrackInitArgs* track_init, const PredictModelArgs* model) {
+  return predict_body(f, s, Predict::tracking, PredictOpts{0.7f, nullptr, false, have_prior, track_init, model});
 }
 
 // finalPredict (ElasticFusion.cpp:586); its last kernel mirrors the result block into the pinned host slot
@@ -1249,26 +1246,21 @@ static int track_frame(dms_fusion* f, const float* inPose16, float weightMultipl
     DMS_CHECK_LAUNCH();
   }
   // ElasticFusion.cpp:165-167: an extra block of this predict's fill-in launch takes the denseEnough decision
-  // (round 6) the set-up of this frame's tracker call rides on the prediction's resolve pass - a kernel boundary before the model
-  // pyramid launch, which can then run the tracker's SO3 stage beside the pyramid (track.hip: k_so3_model)
   const TrackFold fold = {f->state->cur.pose, f->p.pyramid, f->p.fastOdom, f->p.so3, 0};
-  TrackInitArgs early;
-  memset(&early, 0, sizeof(early));
-  bool early_taken = false;
-  const bool want_early = f->p.hybrid_tracking && f->fold_track_init && !f->lost && odometry_early_init_args(f->odom, &fold, &early) != 0;
+  TrackInitArgs init;
+  memset(&init, 0, sizeof(init));
   // fused_model_prediction: nothing but the model pyramid kernel below can read this prediction's images when the frame is one
   // dms_fusion_process_frame call (every reader after the frame gets the FINAL prediction, eager or materialised) without a block
   // that looks at the view in between (NID key-framing, the loop blocks; a lost camera and frameToFrameRGB take the pass-through
   // fill-in): then the prediction is resolved straight into the tracker's model maps, with the tracker call's set-up riding on it
   // as it rides on the pyramid kernel, and the tracker's SO3 launch hosts the depth / intensity pyramid and empties the sampled
-  // z-buffer cells (odometry_model_views_begin says whether that launch exists: resident tracker, so3, not DMS_TRACK_FUSE /
-  // DMS_SO3_BESIDE_MODEL)
+  // z-buffer cells (odometry_model_views_begin says whether that launch exists: resident tracker, so3)
   PredictModelArgs pm;
   memset(&pm, 0, sizeof(pm));
   f->model_written = false;
-  if (f->p.fused_model_prediction && f->one_call_now && f->p.hybrid_tracking && f->p.fused_fill_in && f->fold_track_init && !want_early && !f->lost &&
+  if (f->p.fused_model_prediction && f->one_call_now && f->p.hybrid_tracking && f->p.fused_fill_in && f->fold_track_init && !f->lost &&
       !f->p.nid_keyframing && !f->p.local_loop_closure && !f->p.hybrid_loops && !f->p.frameToFrameRGB && f->n_sample_cells > 0 &&
-      odometry_model_views_begin(f->odom, &fold, &pm.maps, &early, tracking_resolves_shared(f, inPose16 != nullptr) ? f->zbuf2 : f->zbuf,
+      odometry_model_views_begin(f->odom, &fold, &pm.maps, &init, tracking_resolves_shared(f, inPose16 != nullptr) ? f->zbuf2 : f->zbuf,
                                  f->sample_cells, f->n_sample_cells) != 0) {
     pm.pose16 = f->state->cur.pose;
     pm.flag_out = &f->state->fill_in;
@@ -1279,10 +1271,7 @@ static int track_frame(dms_fusion* f, const float* inPose16, float weightMultipl
     f->model_written = true;
   }
   (f->model_written ? f->predict_fused : f->predict_plain) += 1;
-  if ((rc = predict_tracking(f, s, inPose16 != nullptr, (want_early || f->model_written) ? &early : nullptr, &early_taken,
-                             f->model_written ? &pm : nullptr)))
-    return rc;
-  if (want_early && !early_taken) odometry_early_init_args(f->odom, nullptr, &early);  // (no fused resolve pass this frame: the set-up folds into the pyramid kernel as before)
+  if ((rc = predict_tracking(f, s, inPose16 != nullptr, f->model_written ? &init : nullptr, f->model_written ? &pm : nullptr))) return rc;
   if (!f->p.hybrid_tracking) {  // with tracking on, the tracker's last kernel does this
     hipLaunchKernelGGL(k_frame_after_track, dim3(1), dim3(64), 0, s, f->state, weightMultiplier);
     DMS_CHECK_LAUNCH();

@@ -1132,16 +1132,7 @@ template <bool DEPTH_ONLY, bool FILL>
 __global__ __launch_bounds__(256) void k_splat_resolve(ProjArgs a, SurfelPlanes sp, size_t cap, unsigned long long* __restrict__ zbuf,
                                                        uchar4* __restrict__ image, float4* __restrict__ vertex, float4* __restrict__ normal,
                                                        unsigned short* __restrict__ timeImg, float* __restrict__ depthOut, int clear_after,
-                                                       FillArgs fa, TrackInitArgs ti) {
-  // (round 6) the last ti.blocks blocks of the grid carry the set-up of the tracker call that follows two launches later (track_init.hpp):
-  // it depends on the prior pose only, and doing it HERE - a kernel boundary before the model pyramid launch - lets that launch run
-  // the tracker's SO3 stage beside the pyramid (track.hip: k_so3_model)
-  const unsigned nres = gridDim.x - (FILL ? (unsigned)ti.blocks : 0u);
-  if (FILL && blockIdx.x >= nres) {
-    track_init_body((int)(blockIdx.x - nres), ti.blocks, (int)threadIdx.x, (int)blockDim.x, ti.st, ti.prior, ti.prior_pose16, ti.fx, ti.fy, ti.cx, ti.cy,
-                    ti.so3, ti.first_level, ti.sync_words, ti.n_sync, ti.inject_timeout, nullptr);
-    return;
-  }
+                                                       FillArgs fa) {
   if (FILL) {
     if (fa.mirror_words > 0 && blockIdx.x == 0 && (int)threadIdx.x < fa.mirror_words) fa.mirror_dst[threadIdx.x] = fa.mirror_src[threadIdx.x];
     if (fa.thumb_block && blockIdx.x == 0) {  // the frame block's pose and tick ride along (k_thumbnails does the same)
@@ -1155,7 +1146,7 @@ __global__ __launch_bounds__(256) void k_splat_resolve(ProjArgs a, SurfelPlanes 
   // is one 128-byte (float4) run
   const int tiles_y = (a.rows + 7) >> 3, tiles_x = (a.cols + 7) >> 3, ntiles = tiles_x * tiles_y;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves_per_block = blockDim.x >> 6;
-  for (int t = xcd_block(blockIdx.x, nres, a.xcd) * waves_per_block + wave; t < ntiles; t += nres * waves_per_block) {
+  for (int t = xcd_block(blockIdx.x, gridDim.x, a.xcd) * waves_per_block + wave; t < ntiles; t += gridDim.x * waves_per_block) {
     const int tx = t / tiles_y, ty = t - tx * tiles_y;
     const int px = tx * 8 + (lane >> 3), py = ty * 8 + (lane & 7);
     if (px >= a.cols || py >= a.rows) continue;
@@ -1336,7 +1327,7 @@ int splat_predict(dms_model* m, const dms_pose_block* pose, const dms_camera* ca
   DMS_REQUIRE(!pm || (fill && !depth_out && fill->sample_mask && fill->mirror_words == 0 && !fill->thumb_block && zclean && pm->sample_cells && pm->n_cells == pm->samples &&
                       pm->samples == (m->width / 20) * (m->height / 20) && pm->samples > 0 && pm->flag_out && (pm->threads == 256 || pm->threads == 512 || pm->threads == 1024)),
               "the fused prediction + model pass takes the place of the fused resolve + fill-in pass of a tracking prediction only");
-  DMS_REQUIRE(!init || init->blocks == 0 || (fill && !depth_out), "the tracker set-up rides on the fused resolve + fill-in pass only");
+  DMS_REQUIRE(!init || init->blocks == 0 || pm, "the tracker set-up rides on the fused prediction + model pass only");
   DMS_REQUIRE(!m->pending_update, "a deferred update pass is still pending (index_map applies it)");
   DMS_REQUIRE(timeIdx >= 0 && timeIdx < DMS_MAX_SENSORS, "timeIdx out of range");
   // (the project pass divides by fx, fy and 2 maxDepth through exact_arith.hpp: normal numbers far from the ends of the exponent range)
@@ -1380,7 +1371,7 @@ int splat_predict(dms_model* m, const dms_pose_block* pose, const dms_camera* ca
   const dim3 rg(min((n + 255) / 256, 2048));
   if (depth_out) {
     hipLaunchKernelGGL((k_splat_resolve<true, false>), rg, dim3(256), 0, s, a, m->buf[m->cur], m->cap, zbuf, (uchar4*)nullptr,
-                       (float4*)nullptr, (float4*)nullptr, (unsigned short*)nullptr, (float*)depth_out->data, zclean, no_fill, no_init);
+                       (float4*)nullptr, (float4*)nullptr, (unsigned short*)nullptr, (float*)depth_out->data, zclean, no_fill);
   } else if (pm) {
     DMS_REQUIRE(fill->cols == W && fill->rows == H && W <= 2048 && H <= 2048 && pm->maps.v[0].cols == W && pm->maps.v[0].rows == 3 * H &&
                     pm->maps.v[1].cols == W / 2 && pm->maps.v[1].rows == 3 * (H / 2) && pm->maps.v[2].cols == W / 4 && pm->maps.v[2].rows == 3 * (H / 4),
@@ -1399,12 +1390,11 @@ int splat_predict(dms_model* m, const dms_pose_block* pose, const dms_camera* ca
                     fill->ex_normal == (const float4*)out->normal.data && fill->cols == W && fill->rows == H &&
                     (!fill->dense_cnt || (fill->sample_mask && W <= 2048 && H <= 2048)) && fill->mirror_words <= 256,
                 "fill-in arguments do not describe this prediction");
-    const TrackInitArgs& ti = (init && init->blocks > 0) ? *init : no_init;
-    hipLaunchKernelGGL((k_splat_resolve<false, true>), dim3(rg.x + ti.blocks), dim3(256), 0, s, a, m->buf[m->cur], m->cap, zbuf, (uchar4*)out->image.data,
-                       (float4*)out->vertex.data, (float4*)out->normal.data, (unsigned short*)out->time.data, (float*)nullptr, zclean, *fill, ti);
+    hipLaunchKernelGGL((k_splat_resolve<false, true>), rg, dim3(256), 0, s, a, m->buf[m->cur], m->cap, zbuf, (uchar4*)out->image.data,
+                       (float4*)out->vertex.data, (float4*)out->normal.data, (unsigned short*)out->time.data, (float*)nullptr, zclean, *fill);
   } else {
     hipLaunchKernelGGL((k_splat_resolve<false, false>), rg, dim3(256), 0, s, a, m->buf[m->cur], m->cap, zbuf, (uchar4*)out->image.data,
-                       (float4*)out->vertex.data, (float4*)out->normal.data, (unsigned short*)out->time.data, (float*)nullptr, zclean, no_fill, no_init);
+                       (float4*)out->vertex.data, (float4*)out->normal.data, (unsigned short*)out->time.data, (float*)nullptr, zclean, no_fill);
   }
   DMS_CHECK_LAUNCH();
   return DMS_OK;

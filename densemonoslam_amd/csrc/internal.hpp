@@ -144,7 +144,6 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
                            float icpWeight, int pyramid, int fastOdom, int so3, int interMap, hipStream_t s, FrameState* frame = nullptr,
                            float weightMultiplier = 1.f);
 int odometry_result_pose(dms_odometry* o, float* pose16_dev, hipStream_t s);
-int odometry_early_init_args(dms_odometry* o, const TrackFold* fold, TrackInitArgs* ti);
 int odometry_initModel_fused(dms_odometry* o, const void* vA, const void* nA, const void* iA, const void* vB, const void* nB,
                              const void* iB, const int* flag_dev, int force_b_img, const float* pose16_dev, hipStream_t s,
                              int defer_last_step = 0, unsigned* dense_cnt = nullptr, int dense_samples = 0, const TrackFold* fold = nullptr);

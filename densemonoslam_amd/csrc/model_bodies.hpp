@@ -228,12 +228,12 @@ __device__ __forceinline__ void model_pyr_step1_body(int tx, int ty, int bx, int
   model_pyr_step1_taps<BYV>(tx, ty, bx, by, SourceTaps(m, cols0, cutOff), rows0, cols0, ddst, idst);
 }
 
-// BOTH pyramid steps of the model depth / intensity images for a tile of LEVEL-2 pixels, straight from the sources (round 6): the
+// BOTH pyramid steps of the model depth / intensity images for a tile of LEVEL-2 pixels, straight from the level-0 taps (round 6): the
 // block converts the level-0 window its outputs depend on into LDS (as model_pyr_step1_body does), takes the first step into a
 // level-1 tile in LDS - the same float_half / u8_half on the same values, so the tile holds exactly what model_pyr_step1_body
 // stores to the level-1 images - and the second step from that tile.  The pyramid's last step then needs no launch boundary after
-// the first one (it rides on the tracker's first launch otherwise: k_so3_level's rider blocks).  16 x 8 level-2 pixels per block
-// of NT threads: level-1 window 35 x 19, level-0 window 73 x 41.
+// the first one (k_so3_level's rider blocks under fused_model_prediction).  16 x 8 level-2 pixels per block of NT threads: level-1
+// window 35 x 19, level-0 window 73 x 41.
 template <int NT, class Taps>
 __device__ __forceinline__ void model_pyr_step2_taps(int t, int bx, int by, const Taps& src, int rows0, int cols0, int rows1, int cols1, View<float> ddst2,
                                                      View<unsigned char> idst2) {
@@ -279,11 +279,6 @@ __device__ __forceinline__ void model_pyr_step2_taps(int t, int bx, int by, cons
     ddst2.at(y, x) = live::float_half(dt, x, y, cols1, rows1);
     idst2.at(y, x) = live::u8_half(ct, x, y, cols1, rows1);
   }
-}
-template <int NT>
-__device__ __forceinline__ void model_pyr_step2_body(int t, int bx, int by, const ModelSrc& m, int rows0, int cols0, float cutOff, int rows1, int cols1,
-                                                     View<float> ddst2, View<unsigned char> idst2) {
-  model_pyr_step2_taps<NT>(t, bx, by, SourceTaps(m, cols0, cutOff), rows0, cols0, rows1, cols1, ddst2, idst2);
 }
 
 }  // namespace dms

@@ -88,26 +88,27 @@ struct dms_odometry {
   bool fell_back = false;     // a resident kernel timed out at a grid-wide wait: this handle has switched to launch-per-phase
   // what persistent_shape() gave each level of the last tracker call (dms_odometry_get_level_shape); 0 blocks: launch-per-phase
   int last_shape_P[DMS_NUM_PYRS] = {1, 1, 1}, last_shape_nb[DMS_NUM_PYRS] = {0, 0, 0};
-  // the model pyramid's last step (level 1 -> 2 of lastDepth / lastImage), left to the next track call's first kernel
-  bool deferred_pyr = false;
-  // the set-up of the next track call ran inside the model pyramid kernel (odometry_initModel_fused, fold_init): that call then
-  // launches no kernel of its own before the SO3 level, which also carries the deferred pyramid step; the promised parameters
-  bool init_folded = false;
-  // fused_model_prediction (odometry_model_views_begin): the caller's kernel wrote the model maps and level 0 of the depth /
-  // intensity pyramid; the next track call's SO3 launch carries BOTH pyramid steps from those planes and empties the z-buffer cells
-  // that kernel had to leave alone
-  bool pyr_from_planes = false;
-  unsigned long long* rider_zbuf = nullptr;
-  const int* rider_cells = nullptr;
-  int rider_n_cells = 0;
-  // round 6: the call's set-up enqueued AHEAD, as rider blocks of the frame's first kernel (odometry_early_init_args), so that the SO3
-  // stage can run inside the model pyramid launch (k_so3_model) instead of after it
-  bool early_init = false, so3_in_model = false;
-  bool so3_beside_model = false;  // DMS_SO3_BESIDE_MODEL=1: SO3 stage and model pyramid in ONE launch (k_so3_model).  Built, the same bits, 7.6 us less kernel time per
-                                  // frame - and no faster frame (the resident levels then wait for the prep stream's kernels instead): off
-  int folded_so3 = 0, folded_first_level = 0;
-  const float* folded_prior = nullptr;
-  unsigned* dense_cnt_zero = nullptr;  // the frame step's 16 dense counters (fill.hpp), read by the model pyramid kernel: zeroed by the next track call's first kernel
+  // What the kernel that prepared the model side has left to the NEXT track call on this handle (frame step).  Two writers, each
+  // overwriting the whole record: odometry_initModel_fused, and odometry_model_views_begin through fold_init_args.  One reader:
+  // odometry_track_enqueue takes the record and leaves "nothing prepared" behind, whether the call then succeeds or not.
+  struct NextCall {
+    enum Kind {
+      nothing,       // the call launches its own set-up (k_track_init)
+      deferred_pyr,  // ... which also carries the model pyramid's last step, level 1 -> 2 of lastDepth / lastImage (k_track_init_pyr)
+      folded,        // the set-up ran inside the model pyramid kernel: the call launches nothing before its resident SO3 level, which
+                     // carries the deferred pyramid step
+      folded_planes  // fused_model_prediction: the set-up ran inside the caller's kernel, which wrote the model maps and level 0 of the
+                     // depth / intensity pyramid; the SO3 launch carries BOTH pyramid steps from those planes and empties the z-buffer
+                     // cells that kernel had to leave alone
+    } kind = nothing;
+    int so3 = 0, first_level = 0;  // folded*: the call the set-up was made for ...
+    const float* prior = nullptr;  // ... and its prior pose block
+    unsigned* dense_cnt_zero = nullptr;  // deferred_pyr, folded: the frame step's 16 dense counters (fill.hpp), read by the model pyramid
+                                         // kernel and zeroed by the call's first kernel
+    unsigned long long* zbuf = nullptr;  // folded_planes: the z-buffer and its n_cells cells to empty
+    const int* cells = nullptr;
+    int n_cells = 0;
+  } next_call;
   int inject_timeouts = 0;    // dms_odometry_inject_timeout: calls left that start with the timeout flag set
   int width, height;
   float cx, cy, fx, fy, distThres, angleThres;
@@ -141,9 +142,6 @@ struct dms_odometry {
   // the later the last arrival can be after one's own, the longer the pause pays: ~0.4 us on the 150 / 200-block levels, next to
   // nothing on 38 blocks (measured: level 2 is best at 0 - 8 units, levels 1 and 0 at 12 - 20)
   bool long_levels_resident = true;   // levels of more than kArRing iterations (inter-map calls: 50) as resident launches too (DMS_TRACK_LONG_RESIDENT=0: launch-per-phase, as before round 6)
-  bool fuse_coarse = false;           // SO3 + level 2 + level 1 in one resident launch (k_track_coarse; DMS_TRACK_FUSE=1).  Built and bit-identical, but SLOWER on the MI355X: off
-  unsigned* rider_cnt = nullptr;      // device: rider blocks of k_track_coarse launches that have finished (runs over the life of the handle)
-  unsigned rider_issued = 0;          // host: rider blocks enqueued so far
   int first_delay_lvl[4] = {-1, -1, -1, -1};  // per stage (levels 0, 1, 2, SO3): DMS_AR_FIRST_DELAY_BY_LEVEL="l0,l1,l2,so3" (-1 = the rule)
   int first_delay_for(int nb, int stage = -1) const {
     if (stage >= 0 && stage < 4 && first_delay_lvl[stage] >= 0) return first_delay_lvl[stage];
@@ -845,7 +843,6 @@ struct LevelArgs {
   float fx, fy, cx, cy;  // full-resolution intrinsics
   unsigned long long* ar;    // kArSetsPerKernel word sets of kArWords, zero on entry: one per iteration, then the retry pool
   int first_delay;           // see ar_wait (units of 64 cycles)
-  unsigned* zero16;          // the frame step's 16 dense counters, re-armed by the call's first Gauss-Newton launch when no earlier kernel of the call could (k_so3_model reads them)
   long long* prof;           // optional [3][16] per-level phase clocks of block 0 (null = off)
   // last level of the call: block 0 also does what k_track_finalize does (jump gate, result block,
   // pose write-back, frame bookkeeping) instead of a one-lane launch of its own
@@ -944,12 +941,10 @@ __device__ __forceinline__ constexpr unsigned so3_diag_mask() {
 // EXIT: leave the level after an iteration without any correspondence (below).  A template parameter because the
 // mere presence of that exit costs the frame-to-model tracker ~1 % (codegen of the resident loop); the frame step
 // instantiates it for the model-to-model pass only.
-// The level as a stage: `st` is the call's state block in HBM (the sticky timeout flag lives there), `sv` the state the stage reads
-// at its start and leaves at its end - the same block for the stand-alone kernel (block 0 writes it back for the next launch), the
-// block's own LDS copy when several stages run in one launch (k_track_coarse: FUSED; every block holds the same bits, so every
-// block keeps its copy up to date and nothing crosses blocks between two stages).  nb = blocks taking part in the all-reduces.
-template <bool ICP, bool RGB, int P, bool EXIT, bool FUSED>
-__device__ __forceinline__ void gn_level_body(TrackState* st, TrackState* sv, const GnArgs& a, const LevelArgs& L, const int nb) {
+// The level as a stage: `st` is the call's state block in HBM, which every block reads at the start of the stage and block 0 writes
+// back at its end for the next launch (the sticky timeout flag lives there too).  nb = blocks taking part in the all-reduces.
+template <bool ICP, bool RGB, int P, bool EXIT>
+__device__ __forceinline__ void gn_level_body(TrackState* st, const GnArgs& a, const LevelArgs& L, const int nb) {
   constexpr bool kFma = kTrackerFma;
   __shared__ sc::GnLocal s;
   __shared__ int s_redi[kPWaves][2];
@@ -982,34 +977,33 @@ __device__ __forceinline__ void gn_level_body(TrackState* st, TrackState* sv, co
     }
   };
 
-  if (L.zero16 && blockIdx.x == 0 && tid >= 96 && tid < 112) L.zero16[(tid - 96) * 16] = 0u;
   if (L.finalize && L.frame && blockIdx.x == 0 && tid >= 64 && tid < 80) s_held[16 + tid - 64] = L.frame->lastPose[tid - 64];  // for the finalize step
   // (the pose block's bottom row is not the tracker's to write, see the finalize step: it is carried through)
   if (L.finalize && L.frame && blockIdx.x == 0 && tid >= 80 && tid < 84) s_held[12 + tid - 80] = L.frame->cur.pose[12 + tid - 80];
   if (tid == 0) {
     s_none = 0;
     s_retries = 0;
-    s_done = sv->level_done[L.level];
-    for (int i = 0; i < 16; ++i) s.resultRt[i] = sv->resultRt[i];
+    s_done = st->level_done[L.level];
+    for (int i = 0; i < 16; ++i) s.resultRt[i] = st->resultRt[i];
     for (int i = 0; i < 9; ++i) {
-      s.Rprev[i] = sv->Rprev[i];
-      s.Rprev_inv[i] = sv->Rprev_inv[i];
-      s.Rcurr[i] = sv->Rcurr[i];
-      s.krkinv[i] = sv->krkinv[i];
+      s.Rprev[i] = st->Rprev[i];
+      s.Rprev_inv[i] = st->Rprev_inv[i];
+      s.Rcurr[i] = st->Rcurr[i];
+      s.krkinv[i] = st->krkinv[i];
     }
     for (int i = 0; i < 3; ++i) {
-      s.tprev[i] = sv->tprev[i];
-      s.tcurr[i] = sv->tcurr[i];
-      s.kt[i] = sv->kt[i];
+      s.tprev[i] = st->tprev[i];
+      s.tcurr[i] = st->tcurr[i];
+      s.kt[i] = st->kt[i];
     }
-    s.lastRGBError = sv->lastRGBError;
-    s.lastRGBCount = sv->lastRGBCount;
-    s.lastICPError = sv->lastICPError;
-    s.lastICPCount = sv->lastICPCount;
-    s.iters_run = sv->iters_run[L.level];
-    for (int i = 0; i < 36; ++i) s.lastA[i] = sv->lastA[i];
-    for (int i = 0; i < 6; ++i) s.lastb[i] = sv->lastb[i];
-    level_exponents(sv, a, true, s_E[0], s_E[1]);
+    s.lastRGBError = st->lastRGBError;
+    s.lastRGBCount = st->lastRGBCount;
+    s.lastICPError = st->lastICPError;
+    s.lastICPCount = st->lastICPCount;
+    s.iters_run = st->iters_run[L.level];
+    for (int i = 0; i < 36; ++i) s.lastA[i] = st->lastA[i];
+    for (int i = 0; i < 6; ++i) s.lastb[i] = st->lastb[i];
+    level_exponents(st, a, true, s_E[0], s_E[1]);
     // camera matrices of this level and of the next one that runs, for the scalar section (thread 0 uses them)
     // (kept in LDS: 24 more live registers per lane would spill the 256-register pixel loop)
     s_k[0] = sc::kpre_of(L.fx, L.fy, L.cx, L.cy, L.level);
@@ -1025,9 +1019,9 @@ __device__ __forceinline__ void gn_level_body(TrackState* st, TrackState* sv, co
 #pragma unroll
   for (int p = 0; p < P; ++p) {
     idx[p] = (blockIdx.x * P + p) * kPB + tid;
-    // threads past the end shadow a pixel of the image and are masked.  (Not pixel 0 for all of them: in k_track_coarse whole blocks lie
-    // past a small level's image, and tens of thousands of lanes loading one address queue up on its cache line - measured: +5 us
-    // at the start of level 2 and +0.7 us per pass.)
+    // threads past the end shadow a pixel of the image and are masked.  (Not pixel 0 for all of them: where whole blocks lie past a
+    // small level's image, tens of thousands of lanes loading one address queue up on its cache line - measured on a grid larger
+    // than the level: +5 us at the start of level 2 and +0.7 us per pass.)
     const int ic = idx[p] < N ? idx[p] : idx[p] % N;
     py[p] = ic / a.cols;
     px[p] = ic - py[p] * a.cols;
@@ -1328,31 +1322,31 @@ __device__ __forceinline__ void gn_level_body(TrackState* st, TrackState* sv, co
 
   // ---- block 0 hands the state to the next kernel on the stream ----
   __syncthreads();
-  if ((FUSED || blockIdx.x == 0) && tid == 0) {
-    if (ended) sv->level_done[L.level] = 1;
-    for (int i = 0; i < 16; ++i) sv->resultRt[i] = s.resultRt[i];
+  if (blockIdx.x == 0 && tid == 0) {
+    if (ended) st->level_done[L.level] = 1;
+    for (int i = 0; i < 16; ++i) st->resultRt[i] = s.resultRt[i];
     for (int i = 0; i < 9; ++i) {
-      sv->Rcurr[i] = s.Rcurr[i];
-      sv->krkinv[i] = s.krkinv[i];
+      st->Rcurr[i] = s.Rcurr[i];
+      st->krkinv[i] = s.krkinv[i];
     }
     for (int i = 0; i < 3; ++i) {
-      sv->tcurr[i] = s.tcurr[i];
-      sv->kt[i] = s.kt[i];
+      st->tcurr[i] = s.tcurr[i];
+      st->kt[i] = s.kt[i];
     }
-    sv->lastRGBError = s.lastRGBError;
-    sv->lastRGBCount = s.lastRGBCount;
-    sv->lastICPError = s.lastICPError;
-    sv->lastICPCount = s.lastICPCount;
-    sv->iters_run[L.level] = s.iters_run;
-    for (int i = 0; i < 36; ++i) sv->lastA[i] = s.lastA[i];
-    for (int i = 0; i < 6; ++i) sv->lastb[i] = s.lastb[i];
+    st->lastRGBError = s.lastRGBError;
+    st->lastRGBCount = s.lastRGBCount;
+    st->lastICPError = s.lastICPError;
+    st->lastICPCount = s.lastICPCount;
+    st->iters_run[L.level] = s.iters_run;
+    for (int i = 0; i < 36; ++i) st->lastA[i] = s.lastA[i];
+    for (int i = 0; i < 6; ++i) st->lastb[i] = s.lastb[i];
     for (int c2 = 0; c2 < 7; ++c2) {
-      sv->E_icp[c2] = s_E[0][c2];
-      sv->E_rgb[c2] = s_E[1][c2];
+      st->E_icp[c2] = s_E[0][c2];
+      st->E_rgb[c2] = s_E[1][c2];
     }
-    sv->have_E = 1;
-    sv->canon_retries += s_retries;
-    if (L.finalize && blockIdx.x == 0) {  // == k_track_finalize, from the values this thread holds
+    st->have_E = 1;
+    st->canon_retries += s_retries;
+    if (L.finalize) {  // == k_track_finalize, from the values this thread holds
       float tc[3], Rc[9];
       for (int i = 0; i < 3; ++i) tc[i] = s.tcurr[i];
       for (int i = 0; i < 9; ++i) Rc[i] = s.Rcurr[i];
@@ -1362,12 +1356,12 @@ __device__ __forceinline__ void gn_level_body(TrackState* st, TrackState* sv, co
       // that are not the sums of the image: the prior pose is kept and the frame step fuses nothing
       const bool timed_out = __hip_atomic_load(&st->sync_timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
       if (timed_out || (L.fin_rgb && (double)n > 0.3)) {  // RGBDOdometry.cpp:589-593
-        for (int i = 0; i < 9; ++i) Rc[i] = sv->Rcurr[i] = s.Rprev[i];
-        for (int i = 0; i < 3; ++i) tc[i] = sv->tcurr[i] = s.tprev[i];
-        if (!timed_out) sv->rejected_jump = 1;
+        for (int i = 0; i < 9; ++i) Rc[i] = st->Rcurr[i] = s.Rprev[i];
+        for (int i = 0; i < 3; ++i) tc[i] = st->tcurr[i] = s.tprev[i];
+        if (!timed_out) st->rejected_jump = 1;
       }
-      for (int i = 0; i < 3; ++i) sv->out_trans[i] = tc[i];
-      for (int i = 0; i < 9; ++i) sv->out_rot[i] = Rc[i];
+      for (int i = 0; i < 3; ++i) st->out_trans[i] = tc[i];
+      for (int i = 0; i < 9; ++i) st->out_rot[i] = Rc[i];
       // The frame step's pose block IS context.currPose(): the reference assigns the tracker's result to its top three rows only
       // (`currPose.topRightCorner(3, 1) = trans; currPose.topLeftCorner(3, 3) = rot`, ElasticFusion.cpp:246-247), so a bottom row
       // that is not exactly (0 0 0 1) - after a map merge, currPose = relativeTransform * currPose with relativeTransform =
@@ -1408,13 +1402,13 @@ __device__ __forceinline__ void gn_level_body(TrackState* st, TrackState* sv, co
 
 template <bool ICP, bool RGB, int P, bool EXIT>
 __global__ __launch_bounds__(kPB) void k_gn_level(TrackState* st, GnArgs a, LevelArgs L) {
-  gn_level_body<ICP, RGB, P, EXIT, false>(st, st, a, L, (int)gridDim.x);
+  gn_level_body<ICP, RGB, P, EXIT>(st, a, L, (int)gridDim.x);
 }
 
 // Independent work riding on the SO3 launch when the call's set-up was folded into the model pyramid kernel (frame step):
 // the pyramid's deferred last step in gx * gy blocks of 64 x 8 pixels behind the nb_so3 resident blocks (gx = 0: none),
 // and the re-arming of the frame step's dense counters.
-// fused_model_prediction (planes != 0, k_so3_level only): the frame's prediction kernel wrote level 0 of the depth / intensity pyramid
+// fused_model_prediction (planes != 0): the frame's prediction kernel wrote level 0 of the depth / intensity pyramid
 // itself, and BOTH steps ride here from those planes (d0, i0), independent of each other: g2x * g2y blocks of 16 x 8 level-2 pixels
 // (model_pyr_step2_taps: both steps in LDS) first, then gx * gy blocks of 64 x 8 level-1 pixels (model_pyr_step1_taps) into ddst /
 // idst, then ONE block that empties the n_cells z-buffer cells that kernel had to leave for its other blocks to read.
@@ -1441,27 +1435,11 @@ static inline int so3_rider_blocks(const So3Extra& ex) { return ex.planes ? ex.g
 // with one all-reduce per iteration.  The state block is copied into LDS
 // and the unchanged scalar code runs on the copy; block 0 writes it back at the end.
 // ---------------------------------------------------------------------------------------
-struct So3Args {
-  const unsigned char* lastImage;
-  size_t last_pitch;
-  const unsigned char* nextImage;
-  size_t next_pitch;
-  int cols, rows;
-  unsigned long long* ar;
-  SolveCam cam;
-  int first_gn_level, max_iter, exp_bias, first_delay;
-};
-
-// The SO3 stage: `s` is the block's LDS copy of the call's state (every block holds the same bits); stand-alone, it is loaded from
-// `st` at the start and block 0 writes it back at the end; inside k_track_coarse (FUSED) it simply stays where it is for the next stage.
-template <bool FUSED>
-__device__ __forceinline__ void so3_body(TrackState* st, TrackState& s, const So3Args& q, const int nb) {
-  const unsigned char* lastImage = q.lastImage;
-  const unsigned char* nextImage = q.nextImage;
-  const size_t last_pitch = q.last_pitch, next_pitch = q.next_pitch;
-  const int cols = q.cols, rows = q.rows, first_gn_level = q.first_gn_level, max_iter = q.max_iter, exp_bias = q.exp_bias, first_delay = q.first_delay;
-  unsigned long long* ar = q.ar;
-  const SolveCam cam = q.cam;
+// The SO3 stage: `s` is the block's LDS copy of the call's state (every block holds the same bits), loaded from `st` at the start;
+// block 0 writes it back at the end.
+__device__ __forceinline__ void so3_body(TrackState* st, TrackState& s, const unsigned char* lastImage, size_t last_pitch, const unsigned char* nextImage,
+                                         size_t next_pitch, int cols, int rows, unsigned long long* ar, SolveCam cam, int first_gn_level, int max_iter,
+                                         int exp_bias, int first_delay, const int nb) {
   __shared__ int s_viol;
   __shared__ int s_E[4];
   __shared__ double s_bias[2][32];
@@ -1469,11 +1447,7 @@ __device__ __forceinline__ void so3_body(TrackState* st, TrackState& s, const So
   __shared__ float s_sums[32];
   int eb_mine = 0;  // wave 0, lane k < 11: bound exponent of value k
   const int tid = threadIdx.x;
-  if (!FUSED) {
-    const int* src = reinterpret_cast<const int*>(st);
-    int* dst = reinterpret_cast<int*>(&s);
-    for (int i = tid; i < (int)(sizeof(TrackState) / 4); i += kPB) dst[i] = src[i];
-  }
+  for (int i = tid; i < (int)(sizeof(TrackState) / 4); i += kPB) reinterpret_cast<int*>(&s)[i] = reinterpret_cast<const int*>(st)[i];
   if (tid == 0) {
     int E[4];
     canon::static_so3(cols * rows, E);
@@ -1553,7 +1527,7 @@ __device__ __forceinline__ void so3_body(TrackState* st, TrackState& s, const So
     ++it;
   }
   __syncthreads();
-  if (FUSED || blockIdx.x == 0) {
+  if (blockIdx.x == 0) {
     if (tid == 0) {
       if (failed) __hip_atomic_store(&st->sync_timeout, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       s.sync_timeout = __hip_atomic_load(&st->sync_timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1566,11 +1540,9 @@ __device__ __forceinline__ void so3_body(TrackState* st, TrackState& s, const So
       }
     }
     __syncthreads();
-    if (!FUSED) {
-      const int* src = reinterpret_cast<const int*>(&s);
-      int* dst = reinterpret_cast<int*>(st);
-      for (int k = tid; k < (int)(sizeof(TrackState) / 4); k += kPB) dst[k] = src[k];
-    }
+    const int* src = reinterpret_cast<const int*>(&s);
+    int* dst = reinterpret_cast<int*>(st);
+    for (int k = tid; k < (int)(sizeof(TrackState) / 4); k += kPB) dst[k] = src[k];
   }
 }
 
@@ -1600,120 +1572,7 @@ __global__ __launch_bounds__(kPB) void k_so3_level(TrackState* st, const unsigne
   }
   if (ex.zero16 && blockIdx.x == 0 && threadIdx.x < 16) ex.zero16[threadIdx.x * 16] = 0u;  // the frame step's dense counters (read before this launch)
   __shared__ TrackState s;
-  const So3Args q = {lastImage, last_pitch, nextImage, next_pitch, cols, rows, ar, cam, first_gn_level, max_iter, exp_bias, first_delay};
-  so3_body<false>(st, s, q, ex.nb_so3);
-}
-
-// ---------------------------------------------------------------------------------------
-// SO3 BESIDE the model pyramid (round 6).  The SO3 pre-alignment compares two LIVE image pyramids and starts from the prior pose: it
-// needs nothing of the model prediction - yet it ran after the model pyramid kernel, a launch of ~16 us on the frame's critical path
-// behind one of ~14.  Here the resident SO3 blocks are the first blocks of ONE launch whose other blocks are the model pyramid's
-// groups (model_bodies.hpp, as 64 x 8 blocks): the two halves run side by side, the launch ends when the longer one does.  What made
-// the old order necessary is arranged elsewhere: the call's set-up (state block, all-reduce words, timeout flag) rides on the
-// frame's FIRST kernel (the tracking prediction's resolve pass: odometry_early_init_args), so it is complete - across a kernel
-// boundary - before this launch starts; the pyramid's last step, which rode on the SO3 launch, is taken straight from the sources
-// (model_pyr_step2_body); the dense counters this launch reads are re-armed by the first Gauss-Newton launch (LevelArgs::zero16).
-struct ModelGroups {
-  ModelSrc m;
-  int g0x, g0y, g12x, g12y, gsx, gsy, g2x, g2y;
-  int rows0, cols0, rows1, cols1, rows2, cols2;
-  float cutOff;
-  View<float> v0, n0, depth0, v1, n1, v2, n2, depth1, depth2;
-  View<unsigned char> inten0, inten1, inten2;
-};
-
-__global__ __launch_bounds__(kPB) void k_so3_model(TrackState* st, So3Args q, int nb_so3, ModelGroups G) {
-  if ((int)blockIdx.x < nb_so3) {
-    __shared__ TrackState s;
-    so3_body<false>(st, s, q, nb_so3);
-    return;
-  }
-  const int t = (int)threadIdx.x, tx = t & 63, ty = t >> 6;
-  constexpr int BYv = kPB / 64;
-  const int b = (int)blockIdx.x - nb_so3;
-  if (G.m.dense_cnt && b == 0 && t == 0) *G.m.flag_out = model_use_b(G.m) ? 1 : 0;
-  const int nb12 = G.g12x * G.g12y, nbs = G.gsx * G.gsy, nb2 = G.g2x * G.g2y;
-  if (b < nb12) {
-    model_levels12_body(tx, ty, BYv, b % G.g12x, b / G.g12x, G.m, G.cols0, G.rows1, G.cols1, G.rows2, G.cols2, G.v1, G.n1, G.v2, G.n2);
-  } else if (b < nb12 + nbs) {
-    const int c = b - nb12;
-    model_pyr_step1_body<BYv>(tx, ty, c % G.gsx, c / G.gsx, G.m, G.rows0, G.cols0, G.cutOff, G.depth1, G.inten1);
-  } else if (b < nb12 + nbs + nb2) {
-    const int c = b - nb12 - nbs;
-    model_pyr_step2_body<kPB>(t, c % G.g2x, c / G.g2x, G.m, G.rows0, G.cols0, G.cutOff, G.rows1, G.cols1, G.depth2, G.inten2);
-  } else {
-    const int c = b - nb12 - nbs - nb2;
-    model_level0_body(tx, ty, BYv, c % G.g0x, c / G.g0x, G.m, G.rows0, G.cols0, G.v0, G.n0, G.depth0, G.inten0, G.cutOff);
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// The coarse half of a call in ONE resident launch (round 6): SO3 pre-alignment, level 2, level 1.  Every dependent launch on a
-// stream costs ~3.5 us of dispatch on this device plus the stage's own hand-off through HBM (state written back by block 0, reloaded
-// by every block of the next launch, ~2 us) - 92 us of launches for a quarter of level 0's pixel work.  The stages need nothing from
-// each other but the state block, and every block already holds it bit for bit (each block solves on identical totals): so the
-// stages simply follow one another inside one launch, the state stays in LDS, and the blocks never meet between two stages (each
-// stage's all-reduces have word sets of their own).  Grid = the largest stage's (level 1); a stage with fewer pixels leaves the
-// blocks past its image empty-handed - they still arrive in its all-reduces (with zeros).  Level 0 keeps its launch (three pixels
-// per thread on a larger grid).  The rider blocks of the SO3 launch (So3Extra: the model pyramid's deferred last step, which LEVEL 2
-// reads) are riders of this launch: they release their output and count themselves in, and the resident blocks wait for that count
-// between the SO3 stage and level 2 (long complete by then: a formality with a bounded spin).
-struct CoarseArgs {
-  So3Args so3;
-  GnArgs a2, a1;
-  LevelArgs L2, L1;
-  int run_so3, run_l2, run_l1;
-  unsigned* rider_cnt;     // counts rider blocks that have finished, over the life of the handle
-  unsigned rider_target;   // its value once this launch's riders are done
-};
-
-template <bool ICP, bool RGB, int P1, bool EXIT>
-__global__ __launch_bounds__(kPB) void k_track_coarse(TrackState* st, CoarseArgs F, So3Extra ex) {
-  if ((int)blockIdx.x >= ex.nb_so3) {
-    const int c = (int)blockIdx.x - ex.nb_so3, by = c / ex.gx, bx = c - by * ex.gx;
-    model_pyr_step_pixel(bx * 64 + (int)(threadIdx.x & 63), by * (kPB / 64) + (int)(threadIdx.x >> 6), ex.dsrc, ex.ddst, ex.isrc, ex.idst);
-    __threadfence();  // (release: the stores above reach memory every XCD reads from)
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(F.rider_cnt, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    return;
-  }
-  if (ex.zero16 && blockIdx.x == 0 && threadIdx.x < 16) ex.zero16[threadIdx.x * 16] = 0u;
-  __shared__ TrackState s;
-  const int tid = threadIdx.x, nb = ex.nb_so3;
-  {
-    const int* src = reinterpret_cast<const int*>(st);
-    int* dst = reinterpret_cast<int*>(&s);
-    for (int i = tid; i < (int)(sizeof(TrackState) / 4); i += kPB) dst[i] = src[i];
-  }
-  __syncthreads();
-  if (F.run_so3) so3_body<true>(st, s, F.so3, nb);
-  __syncthreads();
-  if (ex.gx > 0) {  // level 2 reads what this launch's rider blocks wrote
-    if (tid == 0) {
-      unsigned spins = 0;
-      // (wrap-safe comparison: the counter runs over the life of the handle)
-      while ((int)(__hip_atomic_load(F.rider_cnt, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) - F.rider_target) < 0) {
-        if (++spins > kSpinLimit) {
-          __hip_atomic_store(&st->sync_timeout, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // never hang the device
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-    }
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  }
-  if (F.run_l2) gn_level_body<ICP, RGB, 1, EXIT, true>(st, &s, F.a2, F.L2, nb);
-  __syncthreads();
-  if (F.run_l1) gn_level_body<ICP, RGB, P1, EXIT, true>(st, &s, F.a1, F.L1, nb);
-  __syncthreads();
-  if (blockIdx.x == 0) {  // the state goes back to HBM for the level-0 launch
-    if (tid == 0) s.sync_timeout = __hip_atomic_load(&st->sync_timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const int* src = reinterpret_cast<const int*>(&s);
-    int* dst = reinterpret_cast<int*>(st);
-    for (int k = tid; k < (int)(sizeof(TrackState) / 4); k += kPB) dst[k] = src[k];
-  }
+  so3_body(st, s, lastImage, last_pitch, nextImage, next_pitch, cols, rows, ar, cam, first_gn_level, max_iter, exp_bias, first_delay, ex.nb_so3);
 }
 
 __global__ void k_track_finalize(TrackState* st, int rgb, float* __restrict__ pose16_out, FrameState* frame, float weightMultiplier) {
@@ -1787,7 +1646,6 @@ void layout(dms_odometry* o, Carver& c) {
   o->part_so3 = (long long*)c.take((size_t)kRecWords * kMaxPartialBlocks * 8);
   o->part_cnt = (int*)c.take((size_t)2 * kMaxPartialBlocks * 4);
   o->tickets = (unsigned*)c.take(64);
-  o->rider_cnt = (unsigned*)c.take(64);
   o->ar = (unsigned long long*)c.take((size_t)kArSets * kArWords * 8);
   o->prof = (long long*)c.take((3 * 16 + 256 * 8) * 8);
   o->state = (TrackState*)c.take(sizeof(TrackState));
@@ -1910,10 +1768,6 @@ int dms_odometry_create(dms_odometry** out, int width, int height, float cx, flo
     if (e && atoi(e) >= 0 && atoi(e) <= 1000) o->first_delay = atoi(e);
     e = getenv("DMS_TRACK_LONG_RESIDENT");
     if (e) o->long_levels_resident = atoi(e) != 0;
-    e = getenv("DMS_SO3_BESIDE_MODEL");
-    if (e) o->so3_beside_model = atoi(e) != 0;
-    e = getenv("DMS_TRACK_FUSE");
-    if (e) o->fuse_coarse = atoi(e) != 0;
     e = getenv("DMS_AR_FIRST_DELAY_BY_LEVEL");  // "l0,l1,l2,so3" in the same units (-1 keeps the rule for that stage): the per-level sweep
     if (e) {
       int v[4] = {-1, -1, -1, -1};
@@ -2039,10 +1893,10 @@ int dms_odometry_inject_timeout(dms_odometry* o, int calls) {
 
 int dms_odometry_set_exec(dms_odometry* o, int resident, int early_exit, int coarse_launch) {
   DMS_REQUIRE(o, "null argument");
+  DMS_REQUIRE(coarse_launch <= 0, "the coarse launch was removed (SO3 + level 2 + level 1 in one resident launch: same bits, slower): pass -1 or 0");
   // resident = 1 on a handle whose device cannot hold a resident kernel's blocks at once (max_resident_blocks = 0) stays off
   if (resident >= 0) o->resident = resident != 0 && o->max_resident_blocks > 0;
   if (early_exit >= 0) o->early_exit_force = early_exit ? 1 : 0;  // -1: unchanged (keeps a DMS_TRACK_EARLY_EXIT choice made at creation)
-  if (coarse_launch >= 0) o->fuse_coarse = coarse_launch != 0;
   return DMS_OK;
 }
 
@@ -2347,21 +2201,6 @@ static void launch_gn_level(int P, int nb, hipStream_t s, TrackState* st, const 
     launch_gn_level_f<ICP, RGB, false>(P, nb, s, st, a, L, done);
 }
 
-template <bool ICP, bool RGB>
-static void launch_track_coarse(int P1, bool early_exit, int grid, hipStream_t s, TrackState* st, const CoarseArgs& F, const So3Extra& ex) {
-  if (P1 == 1) {
-    if (early_exit)
-      hipLaunchKernelGGL((k_track_coarse<ICP, RGB, 1, true>), dim3(grid), dim3(kPB), 0, s, st, F, ex);
-    else
-      hipLaunchKernelGGL((k_track_coarse<ICP, RGB, 1, false>), dim3(grid), dim3(kPB), 0, s, st, F, ex);
-  } else {
-    if (early_exit)
-      hipLaunchKernelGGL((k_track_coarse<ICP, RGB, 2, true>), dim3(grid), dim3(kPB), 0, s, st, F, ex);
-    else
-      hipLaunchKernelGGL((k_track_coarse<ICP, RGB, 2, false>), dim3(grid), dim3(kPB), 0, s, st, F, ex);
-  }
-}
-
 static inline int budget_of(const dms_odometry* o) {
   return (o->budget_cap > 0 && o->budget_cap < o->max_resident_blocks) ? o->budget_cap : o->max_resident_blocks;
 }
@@ -2376,7 +2215,11 @@ static int so3_resident_blocks(const dms_odometry* o) {
 int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot, const float* prior_pose16_dev, int rgbOnly,
                            float icpWeight, int pyramid, int fastOdom, int so3, int interMap, hipStream_t s, FrameState* frame,
                            float weightMultiplier) {
-  DMS_REQUIRE(o && ((trans && rot) || prior_pose16_dev), "null argument");
+  DMS_REQUIRE(o, "null argument");
+  // what an earlier kernel has prepared for this call; taken before anything can fail, so that no error return leaves a promise behind
+  const dms_odometry::NextCall nc = o->next_call;
+  o->next_call = dms_odometry::NextCall();
+  DMS_REQUIRE((trans && rot) || prior_pose16_dev, "null argument");
   const bool icp = !rgbOnly && icpWeight > 0;
   const bool rgb = rgbOnly || icpWeight < 100;
   DMS_REQUIRE(icp || rgb, "neither ICP nor RGB term active");
@@ -2404,30 +2247,17 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
       break;
     }
 
-  // set-up already done inside the model pyramid kernel (frame step): nothing to launch here; the SO3 launch below carries the
-  // deferred pyramid step and re-arms the dense counters
-  const bool folded = o->init_folded;
+  // set-up already done inside the kernel that prepared the model side (frame step): nothing to launch here; the SO3 launch below
+  // carries the pyramid steps left to it and re-arms the dense counters
+  typedef dms_odometry::NextCall NextCall;
   So3Extra ex;
   memset(&ex, 0, sizeof(ex));
-  const bool so3_ran = o->so3_in_model;  // the SO3 stage of this call ran inside the model pyramid launch (k_so3_model)
-  unsigned* first_gn_zero16 = nullptr;
-  if (so3_ran) {
-    o->so3_in_model = false;
-    o->early_init = false;
-    DMS_REQUIRE(so3 && o->folded_so3 == 1 && o->folded_first_level == first_level && o->folded_prior == prior_pose16_dev && prior_pose16_dev && !o->deferred_pyr,
-                "track call differs from the one its early set-up and SO3 stage were prepared for");
-    first_gn_zero16 = o->dense_cnt_zero;
-    o->dense_cnt_zero = nullptr;
-  } else if (folded) {
-    o->init_folded = false;
-    DMS_REQUIRE(so3 && so3_resident_blocks(o) > 0 && o->folded_so3 == (so3 ? 1 : 0) && o->folded_first_level == first_level &&
-                    o->folded_prior == prior_pose16_dev && prior_pose16_dev,
+  if (nc.kind == NextCall::folded || nc.kind == NextCall::folded_planes) {
+    DMS_REQUIRE(so3 && so3_resident_blocks(o) > 0 && nc.so3 == (so3 ? 1 : 0) && nc.first_level == first_level && nc.prior == prior_pose16_dev &&
+                    prior_pose16_dev,
                 "track call differs from the one its folded set-up was prepared for");
-    ex.zero16 = o->dense_cnt_zero;
-    o->dense_cnt_zero = nullptr;
-    if (o->pyr_from_planes) {
-      o->pyr_from_planes = false;
-      DMS_REQUIRE(!o->fuse_coarse && !o->deferred_pyr, "the pyramid steps from the level-0 planes ride on the SO3 launch only");
+    ex.zero16 = nc.dense_cnt_zero;
+    if (nc.kind == NextCall::folded_planes) {
       dms_image2d d0 = o->lastDepth[0].img(), d1 = o->lastDepth[1].img(), d2 = o->lastDepth[2].img();
       dms_image2d i0 = o->lastImage[0].img(), i1 = o->lastImage[1].img(), i2 = o->lastImage[2].img();
       ex.planes = 1;
@@ -2441,11 +2271,10 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
       ex.idst = view<unsigned char>(&i1);
       ex.ddst2 = view<float>(&d2);
       ex.idst2 = view<unsigned char>(&i2);
-      ex.zbuf = o->rider_zbuf;
-      ex.cells = o->rider_cells;
-      ex.n_cells = o->rider_n_cells;
-    } else if (o->deferred_pyr) {
-      o->deferred_pyr = false;
+      ex.zbuf = nc.zbuf;
+      ex.cells = nc.cells;
+      ex.n_cells = nc.n_cells;
+    } else {
       dms_image2d d1 = o->lastDepth[1].img(), d2 = o->lastDepth[2].img(), i1 = o->lastImage[1].img(), i2 = o->lastImage[2].img();
       ex.gx = (d2.cols + 63) / 64;
       ex.gy = (d2.rows + kPB / 64 - 1) / (kPB / 64);
@@ -2459,18 +2288,15 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
     // all-reduce words of the call's resident kernels (resident mode only)
     const int zero_pairs = o->resident ? (int)((size_t)kArSets * kArWords / 2) : 0;
     const int ni = o->resident ? 16 : 1;
-    unsigned* zero16 = o->dense_cnt_zero;
-    o->dense_cnt_zero = nullptr;
-    if (o->deferred_pyr) {
-      o->deferred_pyr = false;
+    if (nc.kind == NextCall::deferred_pyr) {
       dms_image2d d1 = o->lastDepth[1].img(), d2 = o->lastDepth[2].img(), i1 = o->lastImage[1].img(), i2 = o->lastImage[2].img();
       const int gx = (d2.cols + 63) / 64, gy = (d2.rows + 3) / 4;
       hipLaunchKernelGGL(k_track_init_pyr, dim3(gx * gy + ni), dim3(64, 4), 0, s, o->state, prior, prior_pose16_dev, o->fx, o->fy, o->cx, o->cy,
-                         so3 ? 1 : 0, first_level, o->ar, zero_pairs, o->inject_timeouts > 0 ? 1 : 0, zero16, gx, gy, ni, view<const float>(&d1),
-                         view<float>(&d2), view<const unsigned char>(&i1), view<unsigned char>(&i2));
+                         so3 ? 1 : 0, first_level, o->ar, zero_pairs, o->inject_timeouts > 0 ? 1 : 0, nc.dense_cnt_zero, gx, gy, ni,
+                         view<const float>(&d1), view<float>(&d2), view<const unsigned char>(&i1), view<unsigned char>(&i2));
     } else {
       hipLaunchKernelGGL(k_track_init, dim3(ni), dim3(256), 0, s, o->state, prior, prior_pose16_dev, o->fx, o->fy, o->cx, o->cy, so3 ? 1 : 0,
-                         first_level, o->ar, zero_pairs, o->inject_timeouts > 0 ? 1 : 0, zero16);
+                         first_level, o->ar, zero_pairs, o->inject_timeouts > 0 ? 1 : 0, nc.dense_cnt_zero);
     }
     DMS_CHECK_LAUNCH();
     if (o->inject_timeouts > 0) o->inject_timeouts -= 1;
@@ -2543,7 +2369,6 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
     L.cy = o->cy;
     L.ar = o->ar + (size_t)(1 + l) * kArSetsPerKernel * kArWords;
     L.first_delay = o->first_delay_for(pnb, l);
-    L.zero16 = nullptr;
     L.prof = (o->profiling && !o->profiling_level0_only) ? o->prof : nullptr;
     // on for trackers that ask for it (the frame step's model-to-model pass) unless forced either way
     L.early_exit = o->early_exit_force >= 0 ? o->early_exit_force : (o->early_exit ? 1 : 0);
@@ -2563,44 +2388,7 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
     o->last_shape_nb[l] = pnb;
   };
 
-  // SO3 + level 2 + level 1 in one resident launch (k_track_coarse) when all three are resident stages of this call and their shapes
-  // fit one grid: level 1's, with one pixel per thread at level 2
-  bool coarse = false;
-  int cP1 = 1, cnb = 0;
-  if (o->fuse_coarse && o->resident && so3 && !so3_ran && iterations[2] > 0 && iterations[1] > 0 && iterations[2] <= kArRing && iterations[1] <= kArRing) {
-    int P2 = 1, nb2 = 0;
-    level_shape(2, P2, nb2);
-    level_shape(1, cP1, cnb);
-    const int nbs = so3_resident_blocks(o);
-    coarse = nbs > 0 && nb2 > 0 && cnb > 0 && P2 == 1 && cP1 <= 2 && nb2 <= cnb && nbs <= cnb;
-  }
-  if (coarse) {
-    const Buf& li = o->lastNextImage[2];
-    const Buf& ni = o->nextImage[2];
-    CoarseArgs F;
-    memset(&F, 0, sizeof(F));
-    F.so3 = {(const unsigned char*)li.p, li.pitch, (const unsigned char*)ni.p, ni.pitch, ni.cols, ni.rows, o->ar, SolveCam{o->fx, o->fy, o->cx, o->cy},
-             first_level, 10, o->exp_bias + o->depth_bias, o->first_delay_for(cnb, 3)};
-    F.a2 = gn_args_of(2);
-    F.a1 = gn_args_of(1);
-    F.L2 = level_args_of(2, cnb);
-    F.L1 = level_args_of(1, cnb);
-    F.run_so3 = F.run_l2 = F.run_l1 = 1;
-    F.rider_cnt = o->rider_cnt;
-    o->rider_issued += (unsigned)(ex.gx * ex.gy);
-    F.rider_target = o->rider_issued;
-    ex.nb_so3 = cnb;
-    persist.begin();
-    StageTimer t(o->clock, s, "track_coarse", timed(o));
-    const bool ee = F.L1.early_exit != 0;
-    if (icp && rgb)
-      launch_track_coarse<true, true>(cP1, ee, cnb + ex.gx * ex.gy, s, o->state, F, ex);
-    else if (icp)
-      launch_track_coarse<true, false>(cP1, ee, cnb + ex.gx * ex.gy, s, o->state, F, ex);
-    else
-      launch_track_coarse<false, true>(cP1, ee, cnb + ex.gx * ex.gy, s, o->state, F, ex);
-    DMS_CHECK_LAUNCH();
-  } else if (so3 && !so3_ran) {
+  if (so3) {
     const int L = 2;
     const Buf& li = o->lastNextImage[L];
     const Buf& ni = o->nextImage[L];
@@ -2629,7 +2417,6 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
 
   bool finalized_in_kernel = false;
   for (int l = DMS_NUM_PYRS - 1; l >= 0; --l) {
-    if (coarse && l >= 1) continue;  // (ran inside k_track_coarse; resident levels rebuild the cloud point themselves)
     int pP = 1, pnb = 0;
     level_shape(l, pP, pnb);
     const bool persistent = pnb > 0;
@@ -2643,11 +2430,7 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
     const int nb = track_blocks_for(a.cols * a.rows);
     const int level_below = level_below_of(l);
     if (persistent) {
-      LevelArgs L = level_args_of(l, pnb);
-      if (first_gn_zero16) {
-        L.zero16 = first_gn_zero16;
-        first_gn_zero16 = nullptr;
-      }
+      const LevelArgs L = level_args_of(l, pnb);
       if (l == 0) finalized_in_kernel = true;
       persist.begin();
       static const char* const kLevelTimer[3] = {"gn_level0", "gn_level1", "gn_level2"};
@@ -2705,9 +2488,6 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
     }
   }
 
-  if (first_gn_zero16) {  // (no resident level took it: launch-per-phase levels)
-    DMS_HIP(hipMemsetAsync(first_gn_zero16, 0, 16 * 16 * sizeof(unsigned), s));  // (the 16 counters, 64 bytes apart)
-  }
   if (!finalized_in_kernel) {
     StageTimer t(o->clock, s, "track_finalize", timed(o));
     // frame step (frame state given): the result is written back into the pose block the prior came from;
@@ -2975,16 +2755,9 @@ int odometry_next_buffers(dms_odometry* o, int level, dms_image2d* nextImage, dm
   return DMS_OK;
 }
 
-// The set-up of the frame step's NEXT tracker call as a block group of an EARLIER kernel of the frame (the tracking prediction's
-// resolve pass, fusion_map.hip): fills `ti` and returns 1 when this handle can take it (resident SO3 stage, the call odometry_initModel_fused
-// + odometry_track_enqueue are about to make), 0 otherwise (ti->blocks = 0: the set-up stays folded into the model pyramid kernel).
-// With the set-up done a kernel boundary ahead, odometry_initModel_fused runs the SO3 stage beside the model pyramid (k_so3_model).
-int odometry_early_init_args(dms_odometry* o, const TrackFold* fold, TrackInitArgs* ti) {
-  if (!o) return 0;
-  if (!fold && o->early_init && ti->inject_timeout) o->inject_timeouts += 1;  // (cancelled: the injected fault goes to the call's real set-up)
-  memset(ti, 0, sizeof(*ti));
-  o->early_init = false;
-  if (!fold || !o->so3_beside_model || !o->resident || !fold->prior_pose16 || !fold->so3 || fold->interMap || so3_resident_blocks(o) <= 0) return 0;
+// the set-up of the track call `fold` describes as a block group of the kernel that prepares the call's model side: fills `ti` and
+// returns the promise the call is checked against (odometry_track_enqueue), for the writer to complete and store
+static dms_odometry::NextCall fold_init_args(dms_odometry* o, const TrackFold* fold, TrackInitArgs* ti, dms_odometry::NextCall::Kind kind) {
   const int it1 = fold->pyramid ? 5 : 0, it2 = fold->pyramid ? 4 : 0;
   ti->st = o->state;
   ti->prior_pose16 = fold->prior_pose16;
@@ -2999,40 +2772,18 @@ int odometry_early_init_args(dms_odometry* o, const TrackFold* fold, TrackInitAr
   ti->inject_timeout = o->inject_timeouts > 0 ? 1 : 0;
   if (o->inject_timeouts > 0) o->inject_timeouts -= 1;
   ti->blocks = 16;
-  o->early_init = true;
-  o->folded_so3 = 1;
-  o->folded_first_level = ti->first_level;
-  o->folded_prior = fold->prior_pose16;
-  return 1;
-}
-
-// the set-up of the track call `fold` describes as a block group of the kernel that prepares the call's model side: fills `ti` and
-// records the promise the call is checked against (odometry_track_enqueue)
-static void fold_init_args(dms_odometry* o, const TrackFold* fold, TrackInitArgs* ti) {
-  const int it1 = fold->pyramid ? 5 : 0, it2 = fold->pyramid ? 4 : 0;
-  ti->st = o->state;
-  ti->prior_pose16 = fold->prior_pose16;
-  ti->fx = o->fx;
-  ti->fy = o->fy;
-  ti->cx = o->cx;
-  ti->cy = o->cy;
-  ti->so3 = 1;
-  ti->first_level = it2 > 0 ? 2 : (it1 > 0 ? 1 : 0);
-  ti->sync_words = o->ar;
-  ti->n_sync = (int)((size_t)kArSets * kArWords / 2);
-  ti->inject_timeout = (!o->early_init && o->inject_timeouts > 0) ? 1 : 0;
-  if (!o->early_init && o->inject_timeouts > 0) o->inject_timeouts -= 1;
-  ti->blocks = 16;
-  o->init_folded = true;
-  o->folded_so3 = 1;
-  o->folded_first_level = ti->first_level;
-  o->folded_prior = fold->prior_pose16;
+  dms_odometry::NextCall nc;
+  nc.kind = kind;
+  nc.so3 = 1;
+  nc.first_level = ti->first_level;
+  nc.prior = fold->prior_pose16;
+  return nc;
 }
 
 int odometry_model_views_begin(dms_odometry* o, const TrackFold* fold, ModelMapViews* mv, TrackInitArgs* ti, unsigned long long* zbuf,
                                const int* cells, int n_cells) {
   if (!o || !fold || !mv || !ti || !zbuf || !cells) return 0;
-  if (!o->resident || o->fuse_coarse || o->so3_beside_model || !fold->prior_pose16 || !fold->so3 || fold->interMap || so3_resident_blocks(o) <= 0) return 0;
+  if (!o->resident || !fold->prior_pose16 || !fold->so3 || fold->interMap || so3_resident_blocks(o) <= 0) return 0;
   for (int i = 0; i < DMS_NUM_PYRS; ++i) {
     dms_image2d v = o->vmaps_g_prev[i].img(), n = o->nmaps_g_prev[i].img();
     mv->v[i] = view<float>(&v);
@@ -3043,15 +2794,11 @@ int odometry_model_views_begin(dms_odometry* o, const TrackFold* fold, ModelMapV
   mv->inten0 = view<unsigned char>(&i0);
   mv->cutOff = o->maxDepthRGB;
   memset(ti, 0, sizeof(*ti));
-  o->early_init = false;
-  o->so3_in_model = false;
-  o->deferred_pyr = false;
-  o->dense_cnt_zero = nullptr;
-  fold_init_args(o, fold, ti);
-  o->pyr_from_planes = true;
-  o->rider_zbuf = zbuf;
-  o->rider_cells = cells;
-  o->rider_n_cells = n_cells;
+  dms_odometry::NextCall nc = fold_init_args(o, fold, ti, dms_odometry::NextCall::folded_planes);
+  nc.zbuf = zbuf;
+  nc.cells = cells;
+  nc.n_cells = n_cells;
+  o->next_call = nc;
   return 1;
 }
 
@@ -3074,80 +2821,20 @@ int odometry_initModel_fused(dms_odometry* o, const void* vA, const void* nA, co
     d[i] = o->lastDepth[i].img();
     im[i] = o->lastImage[i].img();
   }
-  o->deferred_pyr = defer_last_step != 0;
   // dense_cnt: the source choice comes from the 16 counters of the prediction's resolve pass instead of *flag_dev, which then
   // receives the decision; the next odometry_track_enqueue on this object zeroes the counters
   DMS_REQUIRE(!dense_cnt || defer_last_step, "dense counters are zeroed by the track call that takes the deferred pyramid step");
-  o->dense_cnt_zero = dense_cnt;
   TrackInitArgs ti;
   memset(&ti, 0, sizeof(ti));
-  o->init_folded = false;
-  o->pyr_from_planes = false;
-  if (fold && fold->prior_pose16 && fold->so3 && !fold->interMap && defer_last_step && so3_resident_blocks(o) > 0) fold_init_args(o, fold, &ti);
-  if (o->early_init && o->init_folded) {
-    // The set-up ran a kernel ahead: the resident SO3 stage goes beside the model pyramid's groups in ONE launch (k_so3_model), the
-    // pyramid's last step comes straight from the sources in that launch, nothing is deferred.
-    o->init_folded = false;
-    o->deferred_pyr = false;
-    o->so3_in_model = true;
-    ModelGroups G;
-    memset(&G, 0, sizeof(G));
-    G.m.vA = (const float4*)vA;
-    G.m.nA = (const float4*)nA;
-    G.m.iA = (const uchar4*)iA;
-    G.m.vB = (const float4*)vB;
-    G.m.nB = (const float4*)nB;
-    G.m.iB = (const uchar4*)iB;
-    G.m.flag = flag_dev;
-    G.m.dense_cnt = dense_cnt;
-    G.m.dense_samples = dense_samples;
-    G.m.flag_out = const_cast<int*>(flag_dev);
-    G.m.force_b_img = force_b_img;
-    G.m.pose16 = pose16_dev;
-    G.rows0 = v[0].rows / 3;
-    G.cols0 = v[0].cols;
-    G.rows1 = v[1].rows / 3;
-    G.cols1 = v[1].cols;
-    G.rows2 = v[2].rows / 3;
-    G.cols2 = v[2].cols;
-    DMS_REQUIRE(G.rows1 == G.rows0 / 2 && G.cols1 == G.cols0 / 2 && G.rows2 == G.rows1 / 2 && G.cols2 == G.cols1 / 2, "pyramid shapes");
-    constexpr int BYv = kPB / 64;
-    G.g0x = (G.cols0 + 63) / 64;
-    G.g0y = (G.rows0 + BYv - 1) / BYv;
-    G.g12x = ((G.cols1 + 1) / 2 + 15) / 16;
-    G.g12y = ((G.rows1 + 1) / 2 + BYv - 1) / BYv;
-    G.gsx = (d[1].cols + 63) / 64;
-    G.gsy = (d[1].rows + BYv - 1) / BYv;
-    G.g2x = (d[2].cols + 15) / 16;
-    G.g2y = (d[2].rows + 7) / 8;
-    G.cutOff = o->maxDepthRGB;
-    G.v0 = view<float>(&v[0]);
-    G.n0 = view<float>(&n[0]);
-    G.depth0 = view<float>(&d[0]);
-    G.inten0 = view<unsigned char>(&im[0]);
-    G.v1 = view<float>(&v[1]);
-    G.n1 = view<float>(&n[1]);
-    G.v2 = view<float>(&v[2]);
-    G.n2 = view<float>(&n[2]);
-    G.depth1 = view<float>(&d[1]);
-    G.inten1 = view<unsigned char>(&im[1]);
-    G.depth2 = view<float>(&d[2]);
-    G.inten2 = view<unsigned char>(&im[2]);
-    const Buf& li = o->lastNextImage[2];
-    const Buf& ni = o->nextImage[2];
-    const int nbs = so3_resident_blocks(o);
-    const So3Args q = {(const unsigned char*)li.p, li.pitch, (const unsigned char*)ni.p, ni.pitch, ni.cols, ni.rows, o->ar, SolveCam{o->fx, o->fy, o->cx, o->cy},
-                       o->folded_first_level, 10, o->exp_bias + o->depth_bias, o->first_delay_for(nbs, 3)};
-    PersistSection persist(s, budget_of(o), o->unchained_ok);
-    persist.begin();
-    StageTimer t(o->clock, s, "so3_model", timed(o));
-    hipLaunchKernelGGL(k_so3_model, dim3(nbs + G.g12x * G.g12y + G.gsx * G.gsy + G.g2x * G.g2y + G.g0x * G.g0y), dim3(kPB), 0, s, o->state, q, nbs, G);
-    DMS_CHECK_LAUNCH();
-    return DMS_OK;
-  }
-  o->early_init = false;
-  return modelPyramidFused(vA, nA, iA, vB, nB, iB, flag_dev, force_b_img, pose16_dev, v, n, d, im, o->maxDepthRGB, s, o->deferred_pyr, dense_cnt,
-                           dense_samples, const_cast<int*>(flag_dev), o->init_folded ? &ti : nullptr);
+  dms_odometry::NextCall nc;
+  if (fold && fold->prior_pose16 && fold->so3 && !fold->interMap && defer_last_step && so3_resident_blocks(o) > 0)
+    nc = fold_init_args(o, fold, &ti, dms_odometry::NextCall::folded);
+  else if (defer_last_step)
+    nc.kind = dms_odometry::NextCall::deferred_pyr;
+  nc.dense_cnt_zero = dense_cnt;
+  o->next_call = nc;
+  return modelPyramidFused(vA, nA, iA, vB, nB, iB, flag_dev, force_b_img, pose16_dev, v, n, d, im, o->maxDepthRGB, s, defer_last_step != 0, dense_cnt,
+                           dense_samples, const_cast<int*>(flag_dev), nc.kind == dms_odometry::NextCall::folded ? &ti : nullptr);
 }
 
 // initICP(vertex map, normal map) + initRGB(image) of the live side in the fused form (RGBDOdometry.cpp:118-137,

@@ -238,13 +238,13 @@ int dms_odometry_create(dms_odometry** out, int width, int height, float cx, flo
                         float fx, float fy, float distThresh, float angleThresh);
 int dms_odometry_destroy(dms_odometry* o);
 /* Execution switches of one tracker (no reference counterpart).  They are read from the environment ONCE, when the
- * handle is created - DMS_TRACK_MODE=launches, DMS_TRACK_EARLY_EXIT=0|1, DMS_TRACK_FUSE=0|1 - and changed only here (-1 = keep):
+ * handle is created - DMS_TRACK_MODE=launches, DMS_TRACK_EARLY_EXIT=0|1 - and changed only here (-1 = keep):
  *   resident       1 = one resident kernel per pyramid level (default; ignored where the device cannot hold a resident kernel's blocks
  *                  at once), 0 = three launches per iteration
  *   early_exit     1 / 0 = force the resident-kernel variant that leaves a level after an iteration without any correspondence on / off
  *                  (the handle's default - on for the frame step's model-to-model tracker - or what DMS_TRACK_EARLY_EXIT chose)
- *   coarse_launch  1 = SO3 pre-alignment, level 2 and level 1 as stages of ONE resident launch where their shapes fit one grid
- *                  (round 6; same bits, slower on the MI355X than a launch per stage: default 0)
+ *   coarse_launch  -1 or 0.  The launch shape that 1 selected (SO3 pre-alignment, level 2 and level 1 in one resident launch) was removed:
+ *                  a value above 0 changes nothing and returns DMS_ERR_INVALID_ARG, and dms_last_error says so.
  * Every cross-pixel sum of the tracker is the order-free integer sum of csrc/canon.hpp in every execution mode: poses do not depend on
  * these switches, on the grid size or on the run. */
 int dms_odometry_set_exec(dms_odometry* o, int resident, int early_exit, int coarse_launch);
@@ -271,12 +271,9 @@ int dms_odometry_get_mode(dms_odometry* o, int* resident, int* max_resident_bloc
 /* Launch shape of pyramid level `level` in the last tracker call enqueued on this handle: the pixels per thread (1 - 5) and the
  * block count that the shape rule gave the level from its pixel count and the handle's residency bound.  blocks = 0 /
  * resident = 0: the level ran (or, with no iterations, would have run) launch-per-phase.  Read-only; any output may be null.
- * It is the rule's answer for the level, which is the grid of the level's own resident kernel except that
- *  - with the coarse launch (DMS_TRACK_FUSE=1 / dms_odometry_set_exec) levels 2 and 1 run inside ONE kernel on level 1's grid:
- *    level 2 then reports the shape it would have on its own, not the larger grid it ran on;
- *  - a synchronous call that used up a resident launch's retry pool is repeated launch-per-phase, and that repeat is the last
- *    call enqueued: every level reports 0 blocks although the handle is still resident (dms_odometry_get_mode) and the next
- *    call runs resident again. */
+ * It is the rule's answer for the level, which is the grid of the level's own resident kernel, with one exception: a synchronous
+ * call that used up a resident launch's retry pool is repeated launch-per-phase, and that repeat is the last call enqueued: every
+ * level reports 0 blocks although the handle is still resident (dms_odometry_get_mode) and the next call runs resident again. */
 int dms_odometry_get_level_shape(dms_odometry* o, int level, int* pixels_per_thread, int* blocks, int* resident);
 /* Fault injection for tests: the next `calls` tracking calls behave as if a resident kernel had timed out at a
  * grid barrier (DMS_ERR_TIMEOUT from dms_odometry_fetch_result; the frame step keeps the prior pose and fuses nothing). */

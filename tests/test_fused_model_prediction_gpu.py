@@ -25,7 +25,7 @@ PRED_IMAGES = (9, 10, 11, 12, 13, 14, 15)
 
 @pytest.fixture(autouse=True)
 def _no_override(monkeypatch):
-    for v in (SWITCH, "DMS_TRACK_MODE", "DMS_SO3_BESIDE_MODEL", "DMS_TRACK_FUSE", "DMS_PREDICT_MODEL_THREADS"):
+    for v in (SWITCH, "DMS_TRACK_MODE", "DMS_PREDICT_MODEL_THREADS"):
         monkeypatch.delenv(v, raising=False)  # (the switches would override what the cases set)
 
 
@@ -223,8 +223,7 @@ def test_two_phase_form_is_plain(fus):
 
 
 # ---- 5. fallbacks -----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", ["nid_keyframing", "local_loop_closure", "frameToFrameRGB", "so3=0", "DMS_TRACK_MODE=launches",
-                                  "DMS_SO3_BESIDE_MODEL=1"])
+@pytest.mark.parametrize("case", ["nid_keyframing", "local_loop_closure", "frameToFrameRGB", "so3=0", "DMS_TRACK_MODE=launches"])
 def test_fallbacks(fus, case, monkeypatch):
     """Every disqualifying setting takes the two launches (fused == 0) and stays bit-identical to the option off."""
     opts = {}
