@@ -461,6 +461,13 @@ class ElasticFusionT {
     loopSolver_ = on;
     loopSolverRate_ = sampleRate;
   }
+  // opt-in: ORB-triggered global loops are closed inside the library (dms_fusion_set_global_loop_solver, dmslam_deform.h): a frame
+  // that carries orbTcwOld / orbTcwNew becomes one dms_fusion_process_frame, and applyGlobalLoop one dms_fusion_apply_global_loop.  With
+  // closeLoops and the `constrain` callback (no setLoopSolver) such frames keep the two-phase path, as the local block needs the callback.
+  void setGlobalLoopSolver(bool on = true, int maxPoses = 4096) {
+    globalSolver_ = on;
+    globalSolverPoses_ = maxPoses;
+  }
   const int& getFernDeforms() { return fernDeforms; }
   int surfelCount() {  // ElasticFusion.cpp:1107-1116
     int count = 0;
@@ -513,11 +520,16 @@ class ElasticFusionT {
     // Only a caller who opted in ever touches the switch.  A frame that carries an ORB loop keeps the two-phase path: the switch is off
     // for it.  Mixed use has one caveat: lastDeformTime lives in whichever solver closed the loop - the library's for solver frames,
     // the caller's for callback frames - and neither learns of the other's deformations.
-    const bool solver = loopSolver_ && closeLoops && !orb;
+    const bool global = globalSolver_ && FrontEndOptions::get().hybrid_loops && (!closeLoops || loopSolver_);
+    if (globalSolver_ && FrontEndOptions::get().hybrid_loops)
+      check(dms_fusion_set_global_loop_solver(context.fusion, global ? 1 : 0, globalSolverPoses_), "dms_fusion_set_global_loop_solver");
+    const bool orbOneCall = orb && global;
+    const int libFernBefore = orbOneCall ? dms_fusion_get_fern_deforms(context.fusion) : 0;
+    const bool solver = loopSolver_ && closeLoops && (!orb || orbOneCall);
     if (loopSolver_ && closeLoops)
       check(dms_fusion_set_loop_solver(context.fusion, solver ? 1 : 0, loopSolverRate_), "dms_fusion_set_loop_solver");
     const int libDeformsBefore = solver ? dms_fusion_get_deforms(context.fusion) : 0;
-    if (orb || (closeLoops && !solver)) {
+    if ((orb && !orbOneCall) || (closeLoops && !solver)) {
       // the frame step in two halves around the caller's deformation solver (ElasticFusion.cpp:337 / :481)
       check(dms_fusion_process_frame_begin(context.fusion, context.rgb_dev, 3, (const unsigned short*)context.depth_dev, inPose ? prior : nullptr,
                                            weightMultiplier, nullptr),
@@ -562,6 +574,10 @@ class ElasticFusionT {
                                      weightMultiplier, nullptr),
             "processFrame");
       if (solver) deforms += dms_fusion_get_deforms(context.fusion) - libDeformsBefore;  // :485, beside the callback frames' count
+      if (orbOneCall && dms_fusion_get_fern_deforms(context.fusion) > libFernBefore) {
+        fernDeforms += 1;  // :350
+        adoptPoseGraph(context);
+      }
     }
     refresh(context);
     // :571-574 (the tick the frame was processed at; the pose after tracking / loop closure)
@@ -575,6 +591,16 @@ class ElasticFusionT {
     float po[16], pn[16];
     flat(orbTcwOld, po);
     flat(orbTcwNew, pn);
+    if (globalSolver_ && FrontEndOptions::get().hybrid_loops) {  // the whole of :1148-1240 in the library
+      check(dms_fusion_set_global_loop_solver(context.fusion, 1, globalSolverPoses_), "dms_fusion_set_global_loop_solver");
+      const int before = dms_fusion_get_fern_deforms(context.fusion);
+      check(dms_fusion_apply_global_loop(context.fusion, po, pn, nullptr), "applyGlobalLoop");
+      if (dms_fusion_get_fern_deforms(context.fusion) > before) {
+        fernDeforms += 1;  // :1223
+        adoptPoseGraph(context);
+      }
+      return;
+    }
     check(dms_fusion_apply_global_loop_begin(context.fusion, po, pn, nullptr), "applyGlobalLoop");
     const int cap = (Resolution::getInstance().width() / 20) * (Resolution::getInstance().height() / 20);
     std::vector<float> rows((size_t)cap * 7), rawGraph;
@@ -651,6 +677,21 @@ class ElasticFusionT {
   }
 
  private:
+  // the poses an applied global closure corrected (applyGraphToPoses), into the adapter's copy of Context::poseGraph()
+  void adoptPoseGraph(Context& context) {
+    int n = 0;
+    check(dms_fusion_get_pose_graph(context.fusion, nullptr, nullptr, 0, &n), "dms_fusion_get_pose_graph");
+    std::vector<long long> ticks((size_t)n);
+    std::vector<float> poses((size_t)n * 16);
+    if (n) check(dms_fusion_get_pose_graph(context.fusion, ticks.data(), poses.data(), n, &n), "dms_fusion_get_pose_graph");
+    auto& pg = context.poseGraph();
+    for (size_t i = 0, j = 0; i < pg.size() && j < (size_t)n; ++i) {
+      if ((long long)pg[i].first != ticks[j]) continue;  // (a frame of the two-phase path is not in the library's graph)
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) pg[i].second(r, c) = poses[j * 16 + r * 4 + c];
+      ++j;
+    }
+  }
   static void flat(const Mat4& m, float* o) {
     for (int r = 0; r < 4; ++r)
       for (int c = 0; c < 4; ++c) o[r * 4 + c] = m(r, c);
@@ -704,6 +745,8 @@ class ElasticFusionT {
   const int timeDelta;
   const bool closeLoops, iclnuim, reloc;
   bool loopSolver_ = false;
+  bool globalSolver_ = false;
+  int globalSolverPoses_ = 4096;
   int loopSolverRate_ = 5000;
   float confidence, depthCut, icpThresh;  // (changed by the setters below)
   bool fastOdom, so3, frameToFrameRGB;

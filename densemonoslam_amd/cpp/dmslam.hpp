@@ -556,6 +556,53 @@ class DeformationSolver {
     return t;
   }
   dms_deform* h = nullptr;
+
+ protected:
+  explicit DeformationSolver(dms_deform* made) : h(made) {}
+};
+
+// rf.globalDeformation(): a DeformationSolver that also takes relative constraints and poses and solves with fernMatch = true
+// (dms_deform_create_global, include/dmslam_deform.h).  constrain() on it is the band solve, for pools without relative constraints.
+class GlobalDeformationSolver : public DeformationSolver {
+ public:
+  GlobalDeformationSolver(int maxNodes = DMS_DEFORM_MAX_GLOBAL_NODES, int maxConstraints = DMS_DEFORM_MAX_CONSTRAINTS,
+                          int maxRelative = DMS_DEFORM_MAX_RELATIVE, int maxPoses = 4096)
+      : DeformationSolver(make(maxNodes, maxConstraints, maxRelative, maxPoses)) {}
+  // Deformation::sampleGraphFrom: every 5th node of the local solver's graph
+  void sampleGraphFrom(DeformationSolver& local, dms_stream s = nullptr) { check(dms_deform_sample_from(h, local.h, s), "sampleGraphFrom"); }
+  // rows {source xyz, target xyz, source time, target time}: relativeConstraints()'s
+  void addRelativeConstraints(const float* rows8_dev, int n, dms_stream s = nullptr) {
+    check(dms_deform_add_relative_constraints(h, rows8_dev, n, s), "addRelativeConstraints");
+  }
+  void addRelativeConstraintsHost(const float* rows8_host, int n, dms_stream s = nullptr) {
+    check(dms_deform_add_relative_constraints_host(h, rows8_host, n, s), "addRelativeConstraintsHost");
+  }
+  void setPoses(const long long* times_dev, const float* poses16_dev, int n, dms_stream s = nullptr) {
+    check(dms_deform_set_poses(h, times_dev, poses16_dev, n, s), "setPoses");
+  }
+  // the poses, corrected when the last constrainGlobal was applied: (times, row-major 4 x 4 matrices)
+  std::pair<std::vector<long long>, std::vector<float>> poses() {
+    int n = 0;
+    check(dms_deform_get_poses(h, nullptr, nullptr, 0, &n), "poses");
+    std::vector<long long> t((size_t)n);
+    std::vector<float> p((size_t)n * 16);
+    check(dms_deform_get_poses(h, t.data(), p.data(), n, &n), "poses");
+    return std::make_pair(t, p);
+  }
+  // Deformation::constrain(..., fernMatch = true, poseGraph, relaxGraph = true); result().applied = its return value
+  void constrainGlobal(int time, dms_stream s = nullptr) { check(dms_deform_constrain_global(h, time, s), "constrainGlobal"); }
+  int keptRotations() {
+    int k = 0;
+    check(dms_deform_get_kept_rotations(h, &k), "keptRotations");
+    return k;
+  }
+
+ private:
+  static dms_deform* make(int n, int c, int r, int p) {
+    dms_deform* d = nullptr;
+    check(dms_deform_create_global(&d, n, c, r, p), "GlobalDeformationSolver");
+    return d;
+  }
 };
 
 }  // namespace dms

@@ -1,6 +1,7 @@
 // The deformation-graph solver of include/dmslam_deform.h: Deformation::constrain with DeformationGraph::optimiseGraphSparse for
 // absolute and pin constraints (fernMatch = false) on the GPU.  Row and weight arithmetic: deform_rows.hpp (shared with the host
-// build the CPU tests compare against tests/deform_ref.py).
+// build the CPU tests compare against tests/deform_ref.py).  Behind it, the second kind of object (dms_deform_create_global): relative
+// constraints, fernMatch = true and the poses, over a row-envelope block Cholesky; its launches are listed where its kernels begin.
 //
 // One solve is a fixed sequence of launches on the caller's stream; the host reads nothing in between.  A status block in device
 // memory carries the loop state: once an exit test of DeformationGraph.cpp:515 fires (or the system is singular) it sets `done`
@@ -38,6 +39,7 @@ constexpr int NBLK = BW + 1;           // blocks stored per block row: columns i
 constexpr int ROWLEN = NBLK * NVAR;    // 240 doubles per scalar row
 constexpr int BLK = NVAR * NVAR;       // 144
 constexpr int NPAIR = BW * (BW + 1) / 2;
+constexpr int GLOBAL_MAX_POOL = 2 * DMS_DEFORM_MAX_CONSTRAINTS + 2 * DMS_DEFORM_MAX_RELATIVE;  // 8192 pool vertices
 constexpr int GROUPS = 21;             // 21 * 12 = 252 lanes of a 256-block share the constraint sum of g
 
 struct Hdr {
@@ -50,6 +52,7 @@ struct Hdr {
   double last_error;
   double iter_err[3], iter_dn[3];
   long long last_deform;
+  int n_poses, pose_kept, pool_applied;  // objects of dms_deform_create_global
 };
 
 struct Dev {
@@ -67,6 +70,15 @@ struct Dev {
   double *Ac, *Ab, *g, *diag0, *delta, *delta0;
   float* rel;
   int capN, capP;
+  // objects of dms_deform_create_global only: per pool vertex its kind (0 an absolute constraint or pin, 1 the source of a relative
+  // constraint whose target is the next vertex, 2 such a target) and the merged row (rel_merge; the four nodes of an absolute one);
+  // the row envelope; L in the dense lower block triangle; the pool and the poses of the last applied solve
+  int *kind, *mcnt, *mid, *first;
+  double *mc, *Lg;
+  float *pool_out, *pose16, *relstage;
+  long long* ptime;
+  int* pids;
+  double* pw;
 };
 
 __device__ __forceinline__ void identity_node(const Dev& d, int i) {
@@ -161,18 +173,23 @@ __global__ __launch_bounds__(64) void k_weights(Dev d, int P) {
 }
 
 // rows (high word) and non-zeros (low word) of item idx: the 4 N edges in (node, slot) order, then the P constraints
+// (G: an object of dms_deform_create_global, whose constraints are the merged rows; a relative constraint's target vertex has none)
+template <bool G>
 __device__ __forceinline__ unsigned long long item_size(const Dev& d, int idx, int N, int e0) {
   if (idx < 4 * N) {
     const int j = idx / 4, nb = neighbour(j, N, idx % 4);
     if (j < e0 && nb < e0) return 0ull;
     return ((unsigned long long)REG_ROWS << 32) | (unsigned)(REG_ROWS * ((j >= e0 ? 4 : 0) + (nb >= e0 ? 1 : 0)));
   }
-  const int* id = d.ids + K * (idx - 4 * N);
+  const int l = idx - 4 * N;
+  const int* id = G ? d.mid + 2 * K * l : d.ids + K * l;
+  const int m = G ? d.mcnt[l] : K;
   int cnt = 0;
-  for (int i = 0; i < K; ++i) cnt += id[i] >= e0 ? 1 : 0;
+  for (int i = 0; i < m; ++i) cnt += id[i] >= e0 ? 1 : 0;
   return cnt ? (((unsigned long long)CON_ROWS << 32) | (unsigned)(CON_ROWS * 4 * cnt)) : 0ull;
 }
 
+template <bool G>
 __global__ __launch_bounds__(1024) void k_setup(Dev d, int P, int relax) {
   Hdr* h = d.h;
   const int t = threadIdx.x;
@@ -201,7 +218,7 @@ __global__ __launch_bounds__(1024) void k_setup(Dev d, int P, int relax) {
   const int total = 4 * N + P, per = (total + 1023) / 1024;
   const int lo = min(total, t * per), hi = min(total, lo + per);
   unsigned long long sum = 0;
-  for (int i = lo; i < hi; ++i) sum += item_size(d, i, N, e0);
+  for (int i = lo; i < hi; ++i) sum += item_size<G>(d, i, N, e0);
   s_scan[t] = sum;
   __syncthreads();
   for (int off = 1; off < 1024; off <<= 1) {
@@ -212,7 +229,7 @@ __global__ __launch_bounds__(1024) void k_setup(Dev d, int P, int relax) {
   }
   unsigned long long at = s_scan[t] - sum + (((unsigned long long)(ROT_ROWS * E) << 32) | (unsigned)(27 * E));
   for (int i = lo; i < hi; ++i) {
-    const unsigned long long sz = item_size(d, i, N, e0);
+    const unsigned long long sz = item_size<G>(d, i, N, e0);
     int* row = i < 4 * N ? d.edge_row + i : d.con_row + (i - 4 * N);
     int* nz = i < 4 * N ? d.edge_nz + i : d.con_nz + (i - 4 * N);
     *row = sz ? (int)(at >> 32) : -1;
@@ -236,10 +253,12 @@ __global__ __launch_bounds__(1024) void k_setup(Dev d, int P, int relax) {
     h->n_rel = 0;
     h->n_pool = P;
     for (int i = 0; i < 3; ++i) h->iter_err[i] = h->iter_dn[i] = 0.0;
+    if (G) h->pose_kept = 0;
   }
 }
 
 // sparseResidual (:842-949): thread idx < capN: the rotation rows of enabled node idx; then 4 capN edges; then P constraints
+template <bool G>
 __global__ __launch_bounds__(256) void k_residual(Dev d, int P, int respect_done) {
   const Hdr* h = d.h;
   if (!h->initialised || (respect_done == 1 && h->done)) return;
@@ -269,11 +288,26 @@ __global__ __launch_bounds__(256) void k_residual(Dev d, int P, int respect_done
   vertex_position(d.nodes4, d.rot, d.trans, d.src + 3 * idx, ids, w, pos);
   const float* tg = d.tgt + 3 * idx;
   for (int q = 0; q < 3; ++q) d.pos[3 * idx + q] = pos[q];
+  if (G && d.kind[idx] != 0) {
+    // a relative constraint (:923-932) is no term of nonRelativeConstraintError: a zero leaves that float sum's bits as they are
+    d.cnorm[idx] = 0.f;
+    if (d.kind[idx] == 1 && d.con_row[idx] >= 0) {
+      float tp[3];
+      for (int i = 0; i < K; ++i) {
+        ids[i] = d.ids[K * (idx + 1) + i];
+        w[i] = d.w[K * (idx + 1) + i];
+      }
+      vertex_position(d.nodes4, d.rot, d.trans, d.src + 3 * (idx + 1), ids, w, tp);
+      con_residual(pos, tp, d.resid + d.con_row[idx]);
+    }
+    return;
+  }
   d.cnorm[idx] = norm3(pos[0] - tg[0], pos[1] - tg[1], pos[2] - tg[2]);  // nonRelativeConstraintError's term (:1021)
   if (d.con_row[idx] >= 0) con_residual(pos, tg, d.resid + d.con_row[idx]);
 }
 
 // sparseJacobian (:537-840) as CSR, same thread layout
+template <bool G>
 __global__ __launch_bounds__(256) void k_jacobian(Dev d, int P) {
   const Hdr* h = d.h;
   if (!h->initialised || h->done) return;
@@ -325,10 +359,11 @@ __global__ __launch_bounds__(256) void k_jacobian(Dev d, int P) {
   int nz = d.con_nz[idx];
   for (int c = 0; c < 3; ++c) {
     d.indptr[d.con_row[idx] + c] = nz;
-    for (int i = 0; i < K; ++i) {
-      const int a = d.ids[K * idx + i];
+    const int m = G ? d.mcnt[idx] : K;
+    for (int i = 0; i < m; ++i) {
+      const int a = G ? d.mid[2 * K * idx + i] : d.ids[K * idx + i];
       if (a < e0) continue;
-      const double* c4 = d.coef + 16 * idx + 4 * i;
+      const double* c4 = G ? d.mc + 32 * idx + 4 * i : d.coef + 16 * idx + 4 * i;
       for (int q = 0; q < 4; ++q) {
         d.jcols[nz] = (a - e0) * NVAR + 3 * q + c;
         d.jvals[nz++] = c4[q];
@@ -693,12 +728,14 @@ __global__ __launch_bounds__(256) void k_apply(Dev d, int it) {
 }
 
 // squaredNorm / norm in the restatement's order, meanConsErr, and the exit tests of :515
-__global__ __launch_bounds__(256) void k_norms(Dev d, int P, int it) {
+// (G: fernMatch = true, with the exits of :465 and :516; ncons: the divisor of :1025, every constraint, relative ones included)
+template <bool G>
+__global__ __launch_bounds__(256) void k_norms(Dev d, int P, int it, int ncons) {
   Hdr* h = d.h;
   if (!h->initialised || (it > 0 && h->done)) return;
   if (it < 0 && h->status != DMS_DEFORM_SINGULAR) return;  // it = -1: meanConsErr of the reset graph after a singular exit
   __shared__ double s_a[256], s_b[256];
-  __shared__ float s_c[2 * DMS_DEFORM_MAX_CONSTRAINTS];
+  __shared__ float s_c[G ? GLOBAL_MAX_POOL : 2 * DMS_DEFORM_MAX_CONSTRAINTS];
   const int t = threadIdx.x, rows = h->n_rows, unknowns = h->E * NVAR;
   double a = 0.0, b = 0.0;
   for (int i = t; i < rows; i += 256) {
@@ -725,7 +762,7 @@ __global__ __launch_bounds__(256) void k_norms(Dev d, int P, int it) {
   if (t != 0) return;
   float sum = 0.f;
   for (int l = 0; l < P; ++l) sum = sum + s_c[l];
-  const float mce = sum / (float)P;
+  const float mce = sum / (float)(G ? ncons : P);
   const float error = (float)s_a[0];
   h->mce_after = mce;
   if (it < 0) return;
@@ -734,6 +771,13 @@ __global__ __launch_bounds__(256) void k_norms(Dev d, int P, int it) {
     h->mce_before = mce;
     h->error0 = error;
     h->last_error = (double)error;
+    if (G && mce < 0.06) {  // :465: nothing was computed but meanConsErr
+      h->done = 1;
+      h->optimised = 0;
+      h->exit_reason = DMS_DEFORM_EXIT_CONSTRAINTS_MET;
+      h->error = h->error0 = 0.f;
+      h->n_rows = h->nnz = 0;
+    }
     return;
   }
   const double e = (double)error, dn = sqrt(s_b[0]), diff = e - h->last_error;
@@ -749,6 +793,8 @@ __global__ __launch_bounds__(256) void k_norms(Dev d, int P, int it) {
     why = DMS_DEFORM_EXIT_SMALL_ERROR;
   else if (fabs(diff) < 1e-5 * e)
     why = DMS_DEFORM_EXIT_SMALL_CHANGE;
+  else if (G && it == 1 && error > 10.0f)
+    why = DMS_DEFORM_EXIT_ERROR_LARGE;
   else if (it == 3)
     why = DMS_DEFORM_EXIT_ITERATIONS;
   if (why >= 0) {
@@ -788,6 +834,460 @@ __global__ __launch_bounds__(256) void k_finalize(Dev d, int P, int time, int re
   }
 }
 
+// ==== objects of dms_deform_create_global: relative constraints, fernMatch = true, the poses ===========================================
+// The launches of dms_deform_constrain_global: weights (as above), merge, pose weights, setup, residual, norms, jacobian, then per
+// iteration
+//   gassemble  one block per enabled node: its row envelope first[i] (the smallest block column any row of J couples it to) and its
+//              block row of A = J^T J over first[i] .. i, in the dense lower block triangle; g = -J^T r.  One thread per entry, fixed order.
+//   gsolve     ONE workgroup of 1024 threads: right-looking block Cholesky over the row envelope.  At block column k the panel is the
+//              rows i > k with first[i] <= k (an ordered list, rebuilt per column by ballot); every pair of panel rows is inside the
+//              envelope (first[i] <= k < j), so fill never leaves it and a row that does not reach left stays as narrow as it was.
+//              With first[i] = i - 19 this is the band solver's arithmetic.  Tall rows make the panel longer; its trailing update is
+//              spread over all 16 waves.  Then the backward substitution, pushed column by column along each row's envelope.
+// and finalize (the acceptance test of Deformation.cpp:165) and the poses.
+
+// Deformation.cpp:129-140 for a Constraint(..., relative = true): source and target vertex, one behind the other
+__global__ __launch_bounds__(256) void k_add_rel(Dev d, const float* __restrict__ rows8, int n, int base_v) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= n) return;
+  const float* r = rows8 + 8 * (size_t)c;
+  const int v = base_v + 2 * c;
+  for (int q = 0; q < 3; ++q) {
+    d.src[3 * v + q] = r[q];
+    d.tgt[3 * v + q] = r[3 + q];
+    d.src[3 * (v + 1) + q] = r[3 + q];
+    d.tgt[3 * (v + 1) + q] = r[3 + q];
+  }
+  d.vtime[v] = (int)r[6];
+  d.vtime[v + 1] = (int)r[7];
+  d.ttime[v] = d.ttime[v + 1] = r[7];
+  d.rel_idx[v] = d.rel_idx[v + 1] = -1;
+  d.kind[v] = 1;
+  d.kind[v + 1] = 2;
+}
+__global__ __launch_bounds__(256) void k_mark_absolute(Dev d, int base_v, int n) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c < n) d.kind[base_v + c] = 0;
+}
+
+// Deformation::sampleGraphFrom (Deformation.cpp:222-249): every 5th node of the local graph when count / 5 > 4
+__global__ __launch_bounds__(256) void k_sample_from(Dev d, Dev local) {
+  if (!local.h->initialised) return;
+  const int count = local.h->n_nodes;
+  if (count / 5 <= K) return;
+  const int n = min((count + 4) / 5, d.capN), i = blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) {
+    d.h->n_nodes = n;
+    d.h->initialised = 1;
+  }
+  if (i >= n) return;
+  for (int q = 0; q < 4; ++q) d.nodes4[4 * i + q] = local.nodes4[4 * (5 * i) + q];
+  identity_node(d, i);
+}
+
+__global__ __launch_bounds__(64) void k_gmerge(Dev d, int P) {
+  if (!d.h->initialised) return;
+  const int l = blockIdx.x * 64 + threadIdx.x;
+  if (l >= P) return;
+  const int kd = d.kind[l];
+  int* mid = d.mid + 2 * K * l;
+  double* mc = d.mc + 32 * l;
+  if (kd == 0) {
+    for (int i = 0; i < K; ++i) {
+      mid[i] = d.ids[K * l + i];
+      for (int q = 0; q < 4; ++q) mc[4 * i + q] = d.coef[16 * l + 4 * i + q];
+    }
+    d.mcnt[l] = K;
+  } else if (kd == 1) {
+    int m8[2 * K];
+    double c32[8 * K];
+    const int m = rel_merge(d.nodes4, d.src + 3 * l, d.ids + K * l, d.w + K * l, d.src + 3 * (l + 1), d.ids + K * (l + 1), d.w + K * (l + 1), m8, c32);
+    for (int i = 0; i < m; ++i) {
+      mid[i] = m8[i];
+      for (int q = 0; q < 4; ++q) mc[4 * i + q] = c32[4 * i + q];
+    }
+    d.mcnt[l] = m;
+  } else {
+    d.mcnt[l] = 0;
+  }
+}
+
+// setPosesSeq (:133-250): weightVerticesSeq's rule over a pose's translation and time
+__global__ __launch_bounds__(64) void k_gpose_weights(Dev d, int n) {
+  if (!d.h->initialised) return;
+  const int v = blockIdx.x * 64 + threadIdx.x;
+  if (v >= n) return;
+  const float* T = d.pose16 + 16 * v;
+  const float p[3] = {T[3], T[7], T[11]};
+  int ids[K];
+  double w[K];
+  weigh_vertex(d.nodes4, d.h->n_nodes, p, d.ptime[v], ids, w);
+  for (int i = 0; i < K; ++i) {
+    d.pids[K * v + i] = ids[i];
+    d.pw[K * v + i] = w[i];
+  }
+}
+
+__device__ __forceinline__ size_t tri_row(int b, int p) { return (size_t)b * (b + 1) / 2 * BLK + (size_t)p * (b + 1) * NVAR; }
+
+__device__ __forceinline__ int slot_of(const int* mid, int m, int node) {
+  int s = -1;
+  for (int k = 0; k < m; ++k) s = mid[k] == node ? k : s;
+  return s;
+}
+// The pool vertices whose merged row has node i, compacted in pool order into s_l (256 threads) as vertex | node i's slot << 16 |
+// (a relative constraint) << 20; see compact_touching
+__device__ __forceinline__ int compact_rows_with(const Dev& d, int P, int i, int* s_l, int* s_w) {
+  const int t = threadIdx.x, wave = t >> 6, lane = t & 63, chunks = (P + 255) / 256;  // P <= 8192: at most 32 chunks
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int c = 0; c < chunks; ++c) {
+      const int l = c * 256 + t;
+      const int slot = l < P ? slot_of(d.mid + 2 * K * l, d.mcnt[l], i) : -1;
+      const bool touches = slot >= 0;
+      const unsigned long long m = __ballot(touches);
+      if (pass == 0) {
+        if (lane == 0) s_w[c * 4 + wave] = __popcll(m);
+      } else if (touches) {
+        s_l[s_w[c * 4 + wave] + __popcll(m & ((1ull << lane) - 1ull))] = l | (slot << 16) | (d.kind[l] == 1 ? 1 << 20 : 0);
+      }
+    }
+    __syncthreads();
+    if (pass == 0) {
+      if (t == 0) {
+        int run = 0;
+        for (int k = 0; k < chunks * 4; ++k) {
+          const int v = s_w[k];
+          s_w[k] = run;
+          run += v;
+        }
+        s_w[128] = run;
+      }
+      __syncthreads();
+    }
+  }
+  return s_w[128];
+}
+
+__global__ __launch_bounds__(256) void k_gassemble(Dev d, int P, int n_relative) {
+  const Hdr* h = d.h;
+  if (!h->initialised || h->done) return;
+  const int b = blockIdx.x;
+  if (b >= h->E) return;
+  const int N = h->n_nodes, e0 = h->e0, i = e0 + b, t = threadIdx.x;
+  extern __shared__ int s_dyn[];
+  __shared__ int s_w[129];
+  __shared__ int s_first, s_nfar;
+  __shared__ unsigned char s_has[DMS_DEFORM_MAX_GLOBAL_NODES];  // block columns that some relative constraint with node i has a node in
+  __shared__ double s_J[ROT_ROWS][9];
+  int* s_l = s_dyn;        // the rows with node i, in pool order, each with node i's slot
+  int* s_far = s_dyn + P;  // the relative ones among them (at most n_relative), in the same order: only they reach beyond the band
+  for (int c = t; c < DMS_DEFORM_MAX_GLOBAL_NODES; c += 256) s_has[c] = 0;
+  const int cnt = compact_rows_with(d, P, i, s_l, s_w);
+  if (t == 0) s_first = reg_first(i, N, e0);
+  if (t == 64) {
+    int n = 0;
+    for (int c = 0; c < cnt; ++c)
+      if (s_l[c] >> 20) s_far[n++] = s_l[c];
+    s_nfar = n;
+  }
+  if (t < ROT_ROWS) {
+    int c[6];
+    double v[6];
+    for (int q = 0; q < 9; ++q) s_J[t][q] = 0.0;
+    const int m = rot_jacobian(d.rot + 9 * i, t, c, v);
+    for (int k = 0; k < m; ++k) s_J[t][c[k]] = v[k];
+  }
+  __syncthreads();
+  for (int c = t; c < cnt; c += 256) {
+    const int l = s_l[c] & 0xffff;
+    atomicMin(&s_first, con_first(d.mid + 2 * K * l, d.mcnt[l], i, e0));
+  }
+  for (int c = t; c < s_nfar; c += 256) {
+    const int l = s_far[c] & 0xffff;
+    for (int k = 0; k < d.mcnt[l]; ++k)
+      if (d.mid[2 * K * l + k] >= e0) s_has[d.mid[2 * K * l + k] - e0] = 1;
+  }
+  __syncthreads();
+  const int fb = s_first - e0, len = (b - fb + 1) * NVAR;
+  if (t == 0) d.first[b] = fb;
+  const float* gi = d.nodes4 + 4 * i;
+  for (int e = t; e < NVAR * len; e += 256) {
+    const int p = e / len, cc = e % len, jb = fb + cc / NVAR, q = cc % NVAR, jn = e0 + jb;
+    double acc = 0.0;
+    if ((p % 3) == (q % 3)) {
+      if (jn == i) {
+        for (int s = 0; s < K; ++s) {
+          double c4[4];
+          reg_coeffs(gi, d.nodes4 + 4 * neighbour(i, N, s), c4);
+          acc += coeff_at(c4, p) * coeff_at(c4, q);
+        }
+        if (p >= 9 && q == p)
+          for (int j2 = max(0, i - K); j2 <= min(N - 1, i + K); ++j2)
+            for (int s = 0; s < K; ++s)
+              if (j2 != i && neighbour(j2, N, s) == i) acc += (-SQRT_WREG) * (-SQRT_WREG);
+      } else if (i - jn <= K) {
+        const float* gj = d.nodes4 + 4 * jn;
+        for (int s = 0; s < K; ++s) {
+          if (q >= 9 && neighbour(i, N, s) == jn) {
+            double c4[4];
+            reg_coeffs(gi, gj, c4);
+            acc += coeff_at(c4, p) * (-c4[3]);
+          }
+          if (p >= 9 && neighbour(jn, N, s) == i) {
+            double c4[4];
+            reg_coeffs(gj, gi, c4);
+            acc += (-c4[3]) * coeff_at(c4, q);
+          }
+        }
+      }
+      const bool far = b - jb > BW;  // a block the band solver has not: absolute constraints and pins have nothing there
+      const int* lst = far ? s_far : s_l;
+      const int nl = far ? (s_has[jb] ? s_nfar : 0) : cnt;
+      for (int c = 0; c < nl; ++c) {
+        const int l = lst[c] & 0xffff, si = (lst[c] >> 16) & 7, sj = jn == i ? si : slot_of(d.mid + 2 * K * l, d.mcnt[l], jn);
+        if (sj < 0) continue;
+        acc += coeff_at(d.mc + 32 * l + 4 * si, p) * coeff_at(d.mc + 32 * l + 4 * sj, q);
+      }
+    }
+    if (jb == b && p < 9 && q < 9)
+      for (int r = 0; r < ROT_ROWS; ++r) acc += s_J[r][p] * s_J[r][q];
+    d.Lg[tri_row(b, p) + (size_t)jb * NVAR + q] = acc;
+    if (jb == b && p == q) d.diag0[b * NVAR + p] = acc;
+  }
+  if (t < NVAR) {
+    const int p = t;
+    double sum = 0.0;
+    if (p < 9)
+      for (int r = 0; r < ROT_ROWS; ++r) sum += s_J[r][p] * d.resid[ROT_ROWS * b + r];
+    for (int s = 0; s < K; ++s) {
+      double c4[4];
+      reg_coeffs(gi, d.nodes4 + 4 * neighbour(i, N, s), c4);
+      sum += coeff_at(c4, p) * d.resid[d.edge_row[4 * i + s] + p % 3];
+    }
+    if (p >= 9)
+      for (int j2 = max(0, i - K); j2 <= min(N - 1, i + K); ++j2)
+        for (int s = 0; s < K; ++s)
+          if (j2 != i && neighbour(j2, N, s) == i) sum += (-SQRT_WREG) * d.resid[d.edge_row[4 * j2 + s] + (p - 9)];
+    for (int c = 0; c < cnt; ++c) {
+      const int l = s_l[c] & 0xffff;
+      sum += coeff_at(d.mc + 32 * l + 4 * ((s_l[c] >> 16) & 7), p) * d.resid[d.con_row[l] + p % 3];
+    }
+    d.g[b * NVAR + p] = -sum;
+  }
+}
+
+__global__ __launch_bounds__(1024) void k_gsolve(Dev d) {
+  Hdr* h = d.h;
+  if (!h->initialised || h->done) return;
+  const int E = h->E;
+  __shared__ double s_L[NVAR][NVAR];
+  __shared__ double s_y[NVAR];
+  __shared__ int s_f[DMS_DEFORM_MAX_GLOBAL_NODES], s_rows[DMS_DEFORM_MAX_GLOBAL_NODES];
+  __shared__ int s_wc[16];
+  __shared__ int s_bad;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  if (t < E) s_f[t] = d.first[t];
+  if (t == 0) s_bad = 0;
+  __syncthreads();
+  double* L = d.Lg;
+  double* g = d.g;
+  for (int k = 0; k < E; ++k) {
+    const int ldk = (k + 1) * NVAR;
+    double* Dk = L + tri_row(k, 0) + (size_t)k * NVAR;  // the diagonal block: (p, q) at Dk[p * ldk + q]
+    if (t < 64) {  // as the band solver's: lane r < 12 holds row r; L L^T = D by columns, then L y = g_k
+      const int r = lane < NVAR ? lane : 0;
+      double row[NVAR];
+#pragma unroll
+      for (int q = 0; q < NVAR; ++q) row[q] = Dk[r * ldk + q];
+      double self = 1.0;
+      bool bad = false;
+#pragma unroll
+      for (int c = 0; c < NVAR; ++c) {
+        const double dcc = shfl_d(row[c], c);
+        if (!(dcc > 0x1p-40 * d.diag0[k * NVAR + c])) bad = true;
+        const double dd = sqrt(dcc);
+        const double lc = lane == c ? dd : row[c] / dd;
+        row[c] = lc;
+        if (lane == c) self = dd;
+#pragma unroll
+        for (int q = c + 1; q < NVAR; ++q) {
+          const double lqc = shfl_d(lc, q);
+          row[q] -= lc * lqc;
+        }
+      }
+      const double gr = g[k * NVAR + r];
+      double acc = 0.0, yv = 0.0;
+#pragma unroll
+      for (int c = 0; c < NVAR; ++c) {
+        const double yc = shfl_d((gr - acc) / self, c);
+        if (lane == c) yv = yc;
+        acc += row[c] * yc;
+      }
+      if (lane < NVAR) {
+#pragma unroll
+        for (int q = 0; q < NVAR; ++q) {
+          const double v = q <= lane ? row[q] : 0.0;
+          s_L[lane][q] = v;
+          Dk[lane * ldk + q] = v;
+        }
+        s_y[lane] = yv;
+        g[k * NVAR + lane] = yv;
+      }
+      if (bad && lane == 0) s_bad = 1;
+    }
+    // the panel of column k, ascending: rows below k whose envelope reaches it
+    const int cand = k + 1 + t;
+    const bool in = cand < E && s_f[cand] <= k;
+    const unsigned long long bal = __ballot(in);
+    if (lane == 0) s_wc[wave] = __popcll(bal);
+    __syncthreads();
+    if (s_bad) break;
+    int before = 0, m = 0;
+    for (int w2 = 0; w2 < 16; ++w2) {
+      before += w2 < wave ? s_wc[w2] : 0;
+      m += s_wc[w2];
+    }
+    if (in) s_rows[before + __popcll(bal & ((1ull << lane) - 1ull))] = cand;
+    __syncthreads();
+    for (int r = t; r < m * NVAR; r += 1024) {  // row (i, p) of L_ik = A_ik L_kk^-T, and g_i -= L_ik y_k
+      const int i = s_rows[r / NVAR], p = r % NVAR;
+      double* a = L + tri_row(i, p) + (size_t)k * NVAR;
+      double x[NVAR];
+      double dot = 0.0;
+#pragma unroll
+      for (int q = 0; q < NVAR; ++q) {
+        double v = a[q];
+#pragma unroll
+        for (int m2 = 0; m2 < q; ++m2) v -= x[m2] * s_L[q][m2];
+        x[q] = v / s_L[q][q];
+      }
+#pragma unroll
+      for (int q = 0; q < NVAR; ++q) {
+        a[q] = x[q];
+        dot += x[q] * s_y[q];
+      }
+      g[i * NVAR + p] -= dot;
+    }
+    __syncthreads();
+    // A_ij -= L_ik L_jk^T for the pairs j <= i of the panel.  As in the band solver, a batch's loads stand before its first store.
+    const int entries = m * (m + 1) / 2 * BLK;
+    constexpr int TU = 4;
+    for (int base = t; base < entries; base += 1024 * TU) {
+      unsigned oa[TU], oi[TU], oj[TU];  // offsets into L (below 2^24 doubles): the entry, and the two rows' blocks of column k
+      double old[TU];
+#pragma unroll
+      for (int u = 0; u < TU; ++u) {
+        const int idx = base + u * 1024;
+        if (idx < entries) {
+          const int pr = idx / BLK, wi = idx % BLK, p = wi / NVAR, q = wi % NVAR;
+          int bi = (int)((sqrtf(8.f * (float)pr + 1.f) - 1.f) * 0.5f);
+          while ((bi + 1) * (bi + 2) / 2 <= pr) ++bi;
+          while (bi * (bi + 1) / 2 > pr) --bi;
+          const int i = s_rows[bi], j = s_rows[pr - bi * (bi + 1) / 2];
+          oi[u] = (unsigned)tri_row(i, p) + (unsigned)(k * NVAR);
+          oj[u] = (unsigned)tri_row(j, q) + (unsigned)(k * NVAR);
+          oa[u] = (unsigned)tri_row(i, p) + (unsigned)(j * NVAR + q);
+          old[u] = L[oa[u]];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < TU; ++u) {
+        if (base + u * 1024 < entries) {
+          double acc = 0.0;
+#pragma unroll
+          for (int m2 = 0; m2 < NVAR; ++m2) acc += L[oi[u] + m2] * L[oj[u] + m2];
+          L[oa[u]] = old[u] - acc;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (s_bad) {
+    if (t == 0) {
+      h->status = DMS_DEFORM_SINGULAR;
+      h->optimised = 0;
+      h->done = 1;
+      h->iterations += 1;
+    }
+    return;
+  }
+  for (int k = E - 1; k >= 0; --k) {  // L^T x = y: x_k, then y_j -= L_kj^T x_k along row k's envelope
+    const int ldk = (k + 1) * NVAR;
+    const double* Dk = L + tri_row(k, 0) + (size_t)k * NVAR;
+    if (t < 64) {
+      const int c0 = lane < NVAR ? lane : 0;
+      double col[NVAR];
+#pragma unroll
+      for (int m2 = 0; m2 < NVAR; ++m2) col[m2] = m2 >= c0 ? Dk[m2 * ldk + c0] : 0.0;
+      const double self = Dk[c0 * ldk + c0];
+      const double rhs = g[k * NVAR + c0];
+      double acc = 0.0, xv = 0.0;
+#pragma unroll
+      for (int c = NVAR - 1; c >= 0; --c) {
+        const double xc = shfl_d((rhs - acc) / self, c);
+        if (lane == c) xv = xc;
+        acc += col[c] * xc;
+      }
+      if (lane < NVAR) {
+        g[k * NVAR + lane] = xv;
+        s_y[lane] = xv;
+      }
+    }
+    __syncthreads();
+    const int f = s_f[k] * NVAR;
+    for (int c = f + t; c < k * NVAR; c += 1024) {
+      double acc = 0.0;
+#pragma unroll
+      for (int p = 0; p < NVAR; ++p) acc += L[tri_row(k, p) + c] * s_y[p];
+      g[c] -= acc;
+    }
+    __syncthreads();
+  }
+  for (int idx = t; idx < E * NVAR; idx += 1024) d.delta[idx] = g[idx];
+}
+
+// Deformation.cpp:165-201 with fernMatch = true: applied only when optimised && meanConsErr < 0.0003 && error < 0.12; then the node
+// table and the pool.  Not applied: neither is written.  A singular system resets the graph as above.
+__device__ __forceinline__ bool global_accepts(const Hdr* h) {
+  return h->status == DMS_DEFORM_OK && h->optimised && h->mce_after < 0.0003 && h->error < 0.12;
+}
+__global__ __launch_bounds__(256) void k_gfinalize(Dev d, int P) {
+  Hdr* h = d.h;
+  if (!h->initialised) return;
+  const bool singular = h->status == DMS_DEFORM_SINGULAR, apply = global_accepts(h);
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx < h->n_nodes) {
+    if (singular) identity_node(d, idx);
+    if (apply) {
+      float* row = d.table + 16 * idx;
+      for (int q = 0; q < 3; ++q) row[q] = d.nodes4[4 * idx + q];
+      for (int q = 0; q < 9; ++q) row[3 + q] = d.rot[9 * idx + q];
+      for (int q = 0; q < 3; ++q) row[12 + q] = d.trans[3 * idx + q];
+      row[15] = d.nodes4[4 * idx + 3];
+    }
+  }
+  if (apply && idx < P)
+    for (int q = 0; q < 3; ++q) d.pool_out[3 * idx + q] = d.pos[3 * idx + q];
+  if (idx == 0 && apply) h->pool_applied = P;
+}
+// applyGraphToPoses (:102-131), one lane per pose; runs behind k_gfinalize and sets `applied` (nothing of the status block that
+// global_accepts reads is written here)
+__global__ __launch_bounds__(64) void k_gposes(Dev d, int n) {
+  Hdr* h = d.h;
+  if (!h->initialised) return;
+  const bool apply = global_accepts(h);
+  const int v = blockIdx.x * 64 + threadIdx.x;
+  if (v == 0) h->applied = apply ? 1 : 0;
+  if (!apply || v >= n) return;
+  int ids[K];
+  double w[K];
+  for (int i = 0; i < K; ++i) {
+    ids[i] = d.pids[K * v + i];
+    w[i] = d.pw[K * v + i];
+  }
+  if (!pose_apply(d.nodes4, d.rot, d.trans, ids, w, d.pose16 + 16 * v)) atomicAdd(&h->pose_kept, 1);
+}
+
 }  // namespace
 }  // namespace dms
 
@@ -801,14 +1301,17 @@ struct dms_deform {
   int n_pool = 0, n_rel = 0, n_cons = 0;
   int last_pool = 0, last_rel = 0;
   size_t max_rows = 0, max_nnz = 0;
-  hipStream_t last_stream = nullptr;
+  // an object of dms_deform_create_global: relative rows and poses it was made for and holds, and whether it ran the last solve
+  bool global = false, last_global = false;
+  int capR = 0, capPoses = 0, n_relrows = 0, n_poses = 0;
+  hipStream_t last_stream = nullptr, pose_stream = nullptr;  // of the last solve; of the last dms_deform_set_poses
   Hdr* h_hdr = nullptr;  // pinned
   float* h_rel = nullptr;  // pinned, capC rows of 8
 };
 
 static void carve(dms_deform* o, Carver& c) {
   Dev& d = o->dev;
-  const size_t N = (size_t)o->capN, P = (size_t)2 * o->capC;
+  const size_t N = (size_t)o->capN, P = (size_t)2 * o->capC + (size_t)2 * o->capR;
   d.h = c.take<Hdr>(1);
   d.nodes4 = c.take<float>(4 * N);
   d.rot = c.take<float>(9 * N);
@@ -843,6 +1346,19 @@ static void carve(dms_deform* o, Carver& c) {
   d.rel = c.take<float>(8 * (size_t)o->capC);
   d.capN = o->capN;
   d.capP = (int)P;
+  if (!o->global) return;
+  d.kind = c.take<int>(P);
+  d.mcnt = c.take<int>(P);
+  d.mid = c.take<int>(2 * K * P);
+  d.mc = c.take<double>(32 * P);
+  d.first = c.take<int>(N);
+  d.Lg = c.take<double>(N * (N + 1) / 2 * BLK);
+  d.pool_out = c.take<float>(3 * P);
+  d.relstage = c.take<float>(8 * (size_t)o->capR);
+  d.ptime = c.take<long long>((size_t)o->capPoses);
+  d.pose16 = c.take<float>(16 * (size_t)o->capPoses);
+  d.pids = c.take<int>(K * (size_t)o->capPoses);
+  d.pw = c.take<double>(K * (size_t)o->capPoses);
 }
 
 static inline int blocks_of(size_t n, int per) {
@@ -873,6 +1389,9 @@ int deform_fetch(dms_deform* d, dms_deform_result* res, const float** rel8) {
   return DMS_OK;
 }
 
+// the poses of a global object in device memory (16 floats each), corrected by the last applied dms_deform_constrain_global
+const float* deform_poses_device(dms_deform* d) { return d->dev.pose16; }
+
 // rows of `stride` floats {source xyz, target xyz, target time, ...}: the frame step's constraint buffer has 8 per row
 int deform_add_rows(dms_deform* d, const float* rows_dev, int stride, int n, int srcTime, int pin, hipStream_t s) {
   DMS_REQUIRE(d && rows_dev && n >= 0 && stride >= 7, "bad argument");
@@ -883,6 +1402,10 @@ int deform_add_rows(dms_deform* d, const float* rows_dev, int stride, int n, int
   if (n == 0) return DMS_OK;
   hipLaunchKernelGGL(k_add, dim3(blocks_of(n, 256)), dim3(256), 0, s, d->dev, rows_dev, stride, n, d->n_pool, d->n_rel, srcTime, pin ? 1 : 0);
   DMS_CHECK_LAUNCH();
+  if (d->global) {
+    hipLaunchKernelGGL(k_mark_absolute, dim3(blocks_of(pin ? 2 * n : n, 256)), dim3(256), 0, s, d->dev, d->n_pool, pin ? 2 * n : n);
+    DMS_CHECK_LAUNCH();
+  }
   d->n_pool += pin ? 2 * n : n;
   d->n_rel += n;
   d->n_cons += n;
@@ -892,14 +1415,14 @@ int deform_add_rows(dms_deform* d, const float* rows_dev, int stride, int n, int
 
 extern "C" {
 
-int dms_deform_create(dms_deform** out, int max_nodes, int max_constraints) {
-  DMS_REQUIRE(out, "null argument");
-  DMS_REQUIRE(max_nodes > K && max_nodes <= DMS_DEFORM_MAX_NODES, "max_nodes outside [5, DMS_DEFORM_MAX_NODES]");
-  DMS_REQUIRE(max_constraints >= 1 && max_constraints <= DMS_DEFORM_MAX_CONSTRAINTS, "max_constraints outside [1, DMS_DEFORM_MAX_CONSTRAINTS]");
+static int create_object(dms_deform** out, int max_nodes, int max_constraints, bool global, int max_relative, int max_poses) {
   dms_deform* o = new dms_deform();
   o->capN = max_nodes;
   o->capC = max_constraints;
-  const size_t N = (size_t)max_nodes, P = (size_t)2 * max_constraints;
+  o->global = global;
+  o->capR = max_relative;
+  o->capPoses = max_poses;
+  const size_t N = (size_t)max_nodes, P = (size_t)2 * max_constraints + (size_t)2 * max_relative;
   o->max_rows = (ROT_ROWS + REG_ROWS * K) * N + CON_ROWS * P;  // maxRows of :471
   o->max_nnz = 27 * N + (size_t)REG_ROWS * 5 * K * N + (size_t)CON_ROWS * 4 * K * P;
   Carver sz;
@@ -920,6 +1443,22 @@ int dms_deform_create(dms_deform** out, int max_nodes, int max_constraints) {
   carve(o, cv);
   *out = o;
   return DMS_OK;
+}
+
+int dms_deform_create(dms_deform** out, int max_nodes, int max_constraints) {
+  DMS_REQUIRE(out, "null argument");
+  DMS_REQUIRE(max_nodes > K && max_nodes <= DMS_DEFORM_MAX_NODES, "max_nodes outside [5, DMS_DEFORM_MAX_NODES]");
+  DMS_REQUIRE(max_constraints >= 1 && max_constraints <= DMS_DEFORM_MAX_CONSTRAINTS, "max_constraints outside [1, DMS_DEFORM_MAX_CONSTRAINTS]");
+  return create_object(out, max_nodes, max_constraints, false, 0, 0);
+}
+
+int dms_deform_create_global(dms_deform** out, int max_nodes, int max_constraints, int max_relative, int max_poses) {
+  DMS_REQUIRE(out, "null argument");
+  DMS_REQUIRE(max_nodes > K && max_nodes <= DMS_DEFORM_MAX_GLOBAL_NODES, "max_nodes outside [5, DMS_DEFORM_MAX_GLOBAL_NODES]");
+  DMS_REQUIRE(max_constraints >= 1 && max_constraints <= DMS_DEFORM_MAX_CONSTRAINTS, "max_constraints outside [1, DMS_DEFORM_MAX_CONSTRAINTS]");
+  DMS_REQUIRE(max_relative >= 0 && max_relative <= DMS_DEFORM_MAX_RELATIVE, "max_relative outside [0, DMS_DEFORM_MAX_RELATIVE]");
+  DMS_REQUIRE(max_poses >= 0 && max_poses <= DMS_DEFORM_MAX_POSES, "max_poses outside [0, DMS_DEFORM_MAX_POSES]");
+  return create_object(out, max_nodes, max_constraints, true, max_relative, max_poses);
 }
 
 int dms_deform_destroy(dms_deform* d) {
@@ -960,13 +1499,13 @@ int dms_deform_sample_model(dms_deform* d, dms_model* m, int sampleRate, dms_str
 
 int dms_deform_add_constraints(dms_deform* d, const float* rows7_dev, int n, int srcTime, int pin, int relative, dms_stream s) {
   DMS_REQUIRE(d && rows7_dev && n >= 0, "bad argument");
-  DMS_REQUIRE(!relative, "relative constraints are not solved here (they break the band): keep the caller's solver for them");
+  DMS_REQUIRE(!relative, "relative rows have 8 floats and go through dms_deform_add_relative_constraints, on an object of dms_deform_create_global");
   return deform_add_rows(d, rows7_dev, 7, n, srcTime, pin, (hipStream_t)s);
 }
 
 int dms_deform_clear_constraints(dms_deform* d) {
   DMS_REQUIRE(d, "null argument");
-  d->n_pool = d->n_rel = d->n_cons = 0;
+  d->n_pool = d->n_rel = d->n_cons = d->n_relrows = 0;
   return DMS_OK;
 }
 
@@ -976,6 +1515,10 @@ int dms_deform_constrain(dms_deform* d, int time, int relaxGraph, dms_stream str
     set_error("%s: no constraints", __func__);
     return DMS_ERR_STATE;
   }
+  if (d->n_relrows) {
+    set_error("%s: the pool holds relative constraints: dms_deform_constrain_global solves those", __func__);
+    return DMS_ERR_STATE;
+  }
   hipStream_t s = (hipStream_t)stream;
   const Dev& dev = d->dev;
   const int P = d->n_pool, relax = relaxGraph ? 1 : 0;
@@ -983,13 +1526,13 @@ int dms_deform_constrain(dms_deform* d, int time, int relaxGraph, dms_stream str
   const int items = blocks_of((size_t)5 * d->capN + P, 256), node_blocks = d->n_upper > 0 ? d->n_upper : 1;
   hipLaunchKernelGGL(k_weights, dim3(blocks_of(P, 64)), dim3(64), 0, s, dev, P);
   DMS_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_setup, dim3(1), dim3(1024), 0, s, dev, P, relax);
+  hipLaunchKernelGGL(k_setup<false>, dim3(1), dim3(1024), 0, s, dev, P, relax);
   DMS_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_residual, dim3(items), dim3(256), 0, s, dev, P, 0);
+  hipLaunchKernelGGL(k_residual<false>, dim3(items), dim3(256), 0, s, dev, P, 0);
   DMS_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_norms, dim3(1), dim3(256), 0, s, dev, P, 0);
+  hipLaunchKernelGGL(k_norms<false>, dim3(1), dim3(256), 0, s, dev, P, 0, 0);
   DMS_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_jacobian, dim3(items), dim3(256), 0, s, dev, P);
+  hipLaunchKernelGGL(k_jacobian<false>, dim3(items), dim3(256), 0, s, dev, P);
   DMS_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_assemble_const, dim3(node_blocks), dim3(256), slot_lds, s, dev, P);
   DMS_CHECK_LAUNCH();
@@ -1000,22 +1543,133 @@ int dms_deform_constrain(dms_deform* d, int time, int relaxGraph, dms_stream str
     DMS_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_apply, dim3(blocks_of((size_t)d->n_upper * NVAR, 256)), dim3(256), 0, s, dev, it);
     DMS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_residual, dim3(items), dim3(256), 0, s, dev, P, 1);
+    hipLaunchKernelGGL(k_residual<false>, dim3(items), dim3(256), 0, s, dev, P, 1);
     DMS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_norms, dim3(1), dim3(256), 0, s, dev, P, it);
+    hipLaunchKernelGGL(k_norms<false>, dim3(1), dim3(256), 0, s, dev, P, it, 0);
     DMS_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL(k_finalize, dim3(blocks_of((size_t)(d->capN > P ? d->capN : P), 256)), dim3(256), 0, s, dev, P, time, relax);
   DMS_CHECK_LAUNCH();
   // a singular exit has reset the graph: the pool and meanConsErr (:530) are those of the reset graph (both return at once otherwise)
-  hipLaunchKernelGGL(k_residual, dim3(items), dim3(256), 0, s, dev, P, 2);
+  hipLaunchKernelGGL(k_residual<false>, dim3(items), dim3(256), 0, s, dev, P, 2);
   DMS_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_norms, dim3(1), dim3(256), 0, s, dev, P, -1);
+  hipLaunchKernelGGL(k_norms<false>, dim3(1), dim3(256), 0, s, dev, P, -1, 0);
   DMS_CHECK_LAUNCH();
   d->last_stream = s;
   d->last_pool = P;
   d->last_rel = d->n_rel;
+  d->last_global = false;
   d->n_pool = d->n_rel = d->n_cons = 0;  // constraints.clear(), Deformation.cpp:214
+  return DMS_OK;
+}
+
+int dms_deform_sample_from(dms_deform* global, dms_deform* local, dms_stream s) {
+  DMS_REQUIRE(global && local && global->global && !local->global, "needs a global object and a local one");
+  // (the node count lives on the device: the kernel takes the first max_nodes samples, as dms_deform_sample_model does)
+  const int n = (local->n_upper + 4) / 5 < global->capN ? (local->n_upper + 4) / 5 : global->capN;
+  if (n == 0) return DMS_OK;
+  hipLaunchKernelGGL(k_sample_from, dim3(blocks_of(n, 256)), dim3(256), 0, (hipStream_t)s, global->dev, local->dev);
+  DMS_CHECK_LAUNCH();
+  if (n > global->n_upper) global->n_upper = n;
+  return DMS_OK;
+}
+
+static int add_relative(dms_deform* d, const float* rows8, int n, bool on_host, hipStream_t s, const char* who) {
+  DMS_REQUIRE(d && rows8 && n >= 0, "bad argument");
+  DMS_REQUIRE(d->global, "relative constraints need an object of dms_deform_create_global");
+  if (d->n_relrows + n > d->capR) {
+    set_error("%s: %d relative constraints, made for %d", who, d->n_relrows + n, d->capR);
+    return DMS_ERR_CAPACITY;
+  }
+  if (n == 0) return DMS_OK;
+  if (on_host) {  // each row has a place of its own in the staging buffer, so earlier calls still in flight keep theirs
+    float* stage = d->dev.relstage + 8 * (size_t)d->n_relrows;
+    DMS_HIP(hipMemcpyAsync(stage, rows8, (size_t)n * 8 * sizeof(float), hipMemcpyHostToDevice, s));
+    rows8 = stage;
+  }
+  hipLaunchKernelGGL(k_add_rel, dim3(blocks_of(n, 256)), dim3(256), 0, s, d->dev, rows8, n, d->n_pool);
+  DMS_CHECK_LAUNCH();
+  d->n_pool += 2 * n;
+  d->n_relrows += n;
+  return DMS_OK;
+}
+int dms_deform_add_relative_constraints(dms_deform* d, const float* rows8_dev, int n, dms_stream s) {
+  return add_relative(d, rows8_dev, n, false, (hipStream_t)s, __func__);
+}
+int dms_deform_add_relative_constraints_host(dms_deform* d, const float* rows8_host, int n, dms_stream s) {
+  return add_relative(d, rows8_host, n, true, (hipStream_t)s, __func__);
+}
+
+int dms_deform_set_poses(dms_deform* d, const long long* times_dev, const float* poses16_dev, int n, dms_stream s) {
+  DMS_REQUIRE(d && n >= 0 && (n == 0 || (times_dev && poses16_dev)), "bad argument");
+  DMS_REQUIRE(d->global, "poses need an object of dms_deform_create_global");
+  if (n > d->capPoses) {
+    set_error("%s: %d poses, made for %d", __func__, n, d->capPoses);
+    return DMS_ERR_CAPACITY;
+  }
+  if (n) {
+    DMS_HIP(hipMemcpyAsync(d->dev.ptime, times_dev, (size_t)n * sizeof(long long), hipMemcpyDeviceToDevice, (hipStream_t)s));
+    DMS_HIP(hipMemcpyAsync(d->dev.pose16, poses16_dev, (size_t)n * 16 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)s));
+  }
+  d->n_poses = n;
+  d->pose_stream = (hipStream_t)s;
+  return DMS_OK;
+}
+
+int dms_deform_constrain_global(dms_deform* d, int time, dms_stream stream) {
+  DMS_REQUIRE(d, "null argument");
+  DMS_REQUIRE(d->global, "needs an object of dms_deform_create_global");
+  (void)time;  // fernMatch = true: lastDeformTime is neither read (:161) nor advanced (:203)
+  if (d->n_pool == 0) {
+    set_error("%s: no constraints", __func__);
+    return DMS_ERR_STATE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const Dev& dev = d->dev;
+  const int P = d->n_pool, ncons = P - d->n_relrows, np = d->n_poses;
+  const size_t list_lds = ((size_t)(P + d->n_relrows) * 4 + 15) / 16 * 16;
+  const int items = blocks_of((size_t)5 * d->capN + P, 256), node_blocks = d->n_upper > 0 ? d->n_upper : 1;
+  hipLaunchKernelGGL(k_weights, dim3(blocks_of(P, 64)), dim3(64), 0, s, dev, P);
+  DMS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_gmerge, dim3(blocks_of(P, 64)), dim3(64), 0, s, dev, P);
+  DMS_CHECK_LAUNCH();
+  if (np) {
+    hipLaunchKernelGGL(k_gpose_weights, dim3(blocks_of(np, 64)), dim3(64), 0, s, dev, np);
+    DMS_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(k_setup<true>, dim3(1), dim3(1024), 0, s, dev, P, 1);
+  DMS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_residual<true>, dim3(items), dim3(256), 0, s, dev, P, 0);
+  DMS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_norms<true>, dim3(1), dim3(256), 0, s, dev, P, 0, ncons);
+  DMS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_jacobian<true>, dim3(items), dim3(256), 0, s, dev, P);
+  DMS_CHECK_LAUNCH();
+  for (int it = 1; it <= 3; ++it) {
+    hipLaunchKernelGGL(k_gassemble, dim3(node_blocks), dim3(256), list_lds, s, dev, P, d->n_relrows);
+    DMS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_gsolve, dim3(1), dim3(1024), 0, s, dev);
+    DMS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_apply, dim3(blocks_of((size_t)d->n_upper * NVAR, 256)), dim3(256), 0, s, dev, it);
+    DMS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_residual<true>, dim3(items), dim3(256), 0, s, dev, P, 1);
+    DMS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_norms<true>, dim3(1), dim3(256), 0, s, dev, P, it, ncons);
+    DMS_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(k_gfinalize, dim3(blocks_of((size_t)(d->capN > P ? d->capN : P), 256)), dim3(256), 0, s, dev, P);
+  DMS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_residual<true>, dim3(items), dim3(256), 0, s, dev, P, 2);
+  DMS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_norms<true>, dim3(1), dim3(256), 0, s, dev, P, -1, ncons);
+  DMS_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_gposes, dim3(blocks_of(np ? np : 1, 64)), dim3(64), 0, s, dev, np);
+  DMS_CHECK_LAUNCH();
+  d->last_stream = s;
+  d->last_pool = P;
+  d->last_rel = 0;  // no newRelativeCons (:171)
+  d->last_global = true;
+  d->n_pool = d->n_rel = d->n_cons = d->n_relrows = 0;
   return DMS_OK;
 }
 
@@ -1126,8 +1780,42 @@ int dms_deform_get_first_delta(dms_deform* d, double* delta_host, int max_unknow
 
 int dms_deform_get_pool(dms_deform* d, float* xyz_host, int max_vertices, int* n) {
   DMS_REQUIRE(d && n, "null argument");
+  if (d->last_global) {  // of the last APPLIED solve: a solve that is not applied writes no pool
+    if (int rc = fetch_hdr(d)) return rc;
+    return copy_out(d, xyz_host, d->dev.pool_out, 3 * sizeof(float), d->h_hdr->pool_applied, max_vertices, n);
+  }
   if (int rc = sync_last(d)) return rc;
   return copy_out(d, xyz_host, d->dev.pos, 3 * sizeof(float), d->last_pool, max_vertices, n);
+}
+
+int dms_deform_get_poses(dms_deform* d, long long* times_host, float* poses16_host, int max_poses, int* n) {
+  DMS_REQUIRE(d && n && d->global, "needs an object of dms_deform_create_global");
+  if (int rc = sync_last(d)) return rc;
+  if (d->pose_stream != d->last_stream) DMS_HIP(hipStreamSynchronize(d->pose_stream));
+  if (int rc = copy_out(d, times_host, d->dev.ptime, sizeof(long long), d->n_poses, max_poses, n)) return rc;
+  return copy_out(d, poses16_host, d->dev.pose16, 16 * sizeof(float), d->n_poses, max_poses, n);
+}
+
+int dms_deform_get_pose_weights(dms_deform* d, int* ids4_host, double* weights4_host, int max_poses, int* n) {
+  DMS_REQUIRE(d && n && d->global, "needs an object of dms_deform_create_global");
+  if (int rc = sync_last(d)) return rc;
+  const int have = d->last_global ? d->n_poses : 0;
+  if (int rc = copy_out(d, ids4_host, d->dev.pids, K * sizeof(int), have, max_poses, n)) return rc;
+  return copy_out(d, weights4_host, d->dev.pw, K * sizeof(double), have, max_poses, n);
+}
+
+int dms_deform_get_kept_rotations(dms_deform* d, int* kept) {
+  DMS_REQUIRE(d && kept && d->global, "needs an object of dms_deform_create_global");
+  if (int rc = fetch_hdr(d)) return rc;
+  *kept = d->last_global ? d->h_hdr->pose_kept : 0;
+  return DMS_OK;
+}
+
+int dms_deform_get_envelope(dms_deform* d, int* first_host, int max_nodes, int* n) {
+  DMS_REQUIRE(d && n && d->global, "needs an object of dms_deform_create_global");
+  if (int rc = fetch_hdr(d)) return rc;
+  const Hdr& h = *d->h_hdr;
+  return copy_out(d, first_host, d->dev.first, sizeof(int), d->last_global && h.iterations >= 1 ? h.E : 0, max_nodes, n);
 }
 
 }  // extern "C"

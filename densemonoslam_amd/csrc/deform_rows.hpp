@@ -1,5 +1,5 @@
 // Row and weight arithmetic of the deformation graph (the reference's Utils/DeformationGraph.cpp with k = 4), written once for
-// the kernels of deform.hip and for a plain host build (tests/deform_rows_host.cpp, g++): the neighbour rule, the node search and
+// the kernels of deform.hip and for a plain host build (tests/deform_rows_host.cpp, tests/deform_global_host.cpp, g++): the neighbour rule, the node search and
 // weights of one vertex, the residual and Jacobian entries of one rotation, regularisation and constraint row, and
 // computeVertexPosition.  Plain pointers only; no HIP type crosses this header.
 //
@@ -206,6 +206,157 @@ DMS_DR_HD void con_coeffs(const float* src, const float* g, double w, double c4[
 // coefficients are c4: non-zero only where p % 3 == c.
 // (selects, not an indexed load: the four values stay in registers)
 DMS_DR_HD double coeff_at(const double c4[4], int p) { return p < 3 ? c4[0] : p < 6 ? c4[1] : p < 9 ? c4[2] : c4[3]; }
+
+// ---- relative constraints, the row envelope and the poses (fernMatch = true; tests/deform_global_ref.py restates the same) -------
+// FURTHER ORDER RULES
+//   * the merged weight map of a relative constraint is the source vertex's four entries followed by the target vertex's four,
+//     sorted by node id with the reference's bubble sort (it swaps on "greater" only, so it is stable: of a node that both
+//     vertices have, the source's entry comes first);
+//   * an entry of the source side is con_coeffs' ((src - g) * (float)w, w), one of the target side ((g - tgt) * (float)w, -w)
+//     (:720, :728 against :760, :768), each times sqrt(wCon) in double;
+//   * a node that occurs on both sides has ONE entry per column: the source's value val, then OrderedJacobianRow::addTo with the
+//     target's unscaled value: ((val / sqrt(wCon)) + value) * sqrt(wCon) in double;
+//   * the polar factor U V^T of a pose's rotation is taken in double by POLAR_STEPS Newton steps X <- 0.5 (X + X^-T) from the
+//     double copy of the float matrix, X^-T being the cofactor matrix over the determinant: every cofactor a b - c d as written,
+//     det = (X00 C00 + X01 C01) + X02 C02, each entry 0.5 * (X + C / det); the result is rounded to float once.
+constexpr int POLAR_STEPS = 40;          // from a determinant of 2^-20 the smallest singular value doubles for ~20 steps, then converges
+constexpr double POLAR_MIN_DET = 0x1p-20;
+
+// The merged row of a relative constraint (sparseJacobian :692-801) over ALL its nodes, enabled or not: node ids ascending in mid,
+// four coefficients per node in mc (the layout of con_coeffs).  A node is enabled or not on both sides alike, so the caller drops the
+// entries of disabled nodes afterwards.  Returns the number of distinct nodes (4..8).
+DMS_DR_HD int rel_merge(const float* nodes4, const float* src, const int ids_s[K], const double w_s[K], const float* tgt, const int ids_t[K],
+                        const double w_t[K], int mid[2 * K], double mc[8 * K]) {
+  int id[2 * K];
+  double w[2 * K];
+  bool rel[2 * K];
+  for (int a = 0; a < K; ++a) {
+    id[a] = ids_s[a];
+    w[a] = w_s[a];
+    rel[a] = false;
+    id[K + a] = ids_t[a];
+    w[K + a] = w_t[a];
+    rel[K + a] = true;
+  }
+  bool done = false;
+  int size = 2 * K;
+  while (!done) {  // VertexWeightMap::sort
+    done = true;
+    for (int a = 0; a < size - 1; ++a)
+      if (id[a] > id[a + 1]) {
+        done = false;
+        const int ti = id[a];
+        id[a] = id[a + 1];
+        id[a + 1] = ti;
+        const double tw = w[a];
+        w[a] = w[a + 1];
+        w[a + 1] = tw;
+        const bool tr = rel[a];
+        rel[a] = rel[a + 1];
+        rel[a + 1] = tr;
+      }
+    --size;
+  }
+  int m = 0;
+  for (int a = 0; a < 2 * K; ++a) {
+    const float* g = nodes4 + 4 * id[a];
+    const float wf = (float)w[a];
+    double v[4];
+    for (int c = 0; c < 3; ++c) v[c] = rel[a] ? (double)((g[c] - tgt[c]) * wf) : (double)((src[c] - g[c]) * wf);
+    v[3] = rel[a] ? -w[a] : w[a];
+    if (m > 0 && mid[m - 1] == id[a]) {
+      for (int q = 0; q < 4; ++q) mc[4 * (m - 1) + q] = ((mc[4 * (m - 1) + q] / SQRT_WCON) + v[q]) * SQRT_WCON;
+    } else {
+      mid[m] = id[a];
+      for (int q = 0; q < 4; ++q) mc[4 * m + q] = v[q] * SQRT_WCON;
+      ++m;
+    }
+  }
+  return m;
+}
+
+// The smallest enabled node that the regularisation rows couple to enabled node i: its own edges and the edges that end in it
+DMS_DR_HD int reg_first(int i, int n, int e0) {
+  int f = i;
+  for (int s = 0; s < K; ++s) {
+    const int nb = neighbour(i, n, s);
+    if (nb >= e0 && nb < f) f = nb;
+  }
+  const int lo = i - K > 0 ? i - K : 0;
+  for (int j = lo; j < i; ++j)
+    for (int s = 0; s < K; ++s)
+      if (j >= e0 && j < f && neighbour(j, n, s) == i) f = j;
+  return f;
+}
+// The smallest enabled node of a constraint's (merged) nodes when it has node i, else i: first[i] of the row envelope is the minimum
+// of reg_first and of this over every constraint.  mid ascends.
+DMS_DR_HD int con_first(const int* mid, int cnt, int i, int e0) {
+  bool has = false;
+  int f = i;
+  for (int s = 0; s < cnt; ++s) {
+    has = has || mid[s] == i;
+    if (mid[s] >= e0 && mid[s] < f) f = mid[s];
+  }
+  return has ? f : i;
+}
+
+// X^-T step of the polar iteration (see the order rules); X row-major
+DMS_DR_HD double cofactors(const double X[9], double C[9]) {
+  C[0] = X[4] * X[8] - X[5] * X[7];
+  C[1] = X[5] * X[6] - X[3] * X[8];
+  C[2] = X[3] * X[7] - X[4] * X[6];
+  C[3] = X[2] * X[7] - X[1] * X[8];
+  C[4] = X[0] * X[8] - X[2] * X[6];
+  C[5] = X[1] * X[6] - X[0] * X[7];
+  C[6] = X[1] * X[5] - X[2] * X[4];
+  C[7] = X[2] * X[3] - X[0] * X[5];
+  C[8] = X[0] * X[4] - X[1] * X[3];
+  return (X[0] * C[0] + X[1] * C[1]) + X[2] * C[2];
+}
+// The orthogonal polar factor of M (row-major floats) into out; false (out untouched) when M is not finite or |det| < 2^-20
+DMS_DR_HD bool polar_factor(const float M[9], float out[9]) {
+  double X[9], C[9];
+  bool finite = true;
+  for (int e = 0; e < 9; ++e) {
+    X[e] = (double)M[e];
+    finite = finite && (X[e] - X[e] == 0.0);
+  }
+  const double det0 = cofactors(X, C);
+  if (!finite || !(fabs(det0) >= POLAR_MIN_DET)) return false;
+  for (int it = 0; it < POLAR_STEPS; ++it) {
+    const double det = cofactors(X, C);
+    for (int e = 0; e < 9; ++e) X[e] = 0.5 * (X[e] + C[e] / det);
+  }
+  for (int e = 0; e < 9; ++e) out[e] = (float)X[e];
+  return true;
+}
+
+// applyGraphToPoses (:102-131) for one pose (row-major 4 x 4, in place) with setPosesSeq's weights of it (weigh_vertex over its
+// translation and time).  Returns false when the rotation was kept (polar_factor's rule); the translation is written either way.
+DMS_DR_HD bool pose_apply(const float* nodes4, const float* rot9, const float* trans3, const int ids[K], const double w[K], float* pose16) {
+  const float t[3] = {pose16[3], pose16[7], pose16[11]};
+  float moved[3] = {0.f, 0.f, 0.f};
+  float rs[9];  // the weighted rotation sum, column-major as the nodes' rotations
+  for (int e = 0; e < 9; ++e) rs[e] = 0.f;
+  for (int j = 0; j < K; ++j) {
+    const int a = ids[j];
+    const float wf = (float)w[j];
+    float m[3];
+    node_map(rot9 + 9 * a, nodes4 + 4 * a, trans3 + 3 * a, t, m);
+    for (int r = 0; r < 3; ++r) moved[r] = moved[r] + wf * m[r];
+    for (int e = 0; e < 9; ++e) rs[e] = rs[e] + wf * rot9[9 * a + e];
+  }
+  float M[9], U[9];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) M[3 * r + c] = (rs[r] * pose16[c] + rs[3 + r] * pose16[4 + c]) + rs[6 + r] * pose16[8 + c];
+  const bool ok = polar_factor(M, U);
+  for (int r = 0; r < 3; ++r) {
+    pose16[4 * r + 3] = moved[r];
+    if (ok)
+      for (int c = 0; c < 3; ++c) pose16[4 * r + c] = U[3 * r + c];
+  }
+  return ok;
+}
 
 }  // namespace dr
 }  // namespace dms

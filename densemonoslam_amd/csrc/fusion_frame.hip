@@ -260,6 +260,13 @@ struct dms_fusion {
   dms_deform* deform = nullptr;      // created when the solver is first switched on
   int deforms = 0;                   // ElasticFusion::deforms (:485)
   std::vector<float> relative_cons;  // context.relativeCons() (:489-492): rows of 8 floats
+  // dms_fusion_set_global_loop_solver: the frame step closes ORB-triggered global loops itself (ElasticFusion.cpp:292-355, :1148-1240)
+  bool global_solver = false;
+  dms_deform* gdeform = nullptr;     // rf.globalDeformation()
+  int max_poses = 0, fern_deforms = 0;
+  std::vector<long long> pg_ticks;   // Context::poseGraph() (:571-573): the ticks on the host, the poses in device memory
+  long long* pg_ticks_dev = nullptr;
+  float* pg_poses_dev = nullptr;
   // between dms_fusion_process_frame_begin and _end
   bool in_frame = false, cur_bootstrap = false, cur_fuse_now = true;
   int live_set = 0, lastnext_set = 0;  // ring sets of the previous frame's live pyramids and of its lastNextImage
@@ -921,6 +928,9 @@ int dms_fusion_destroy(dms_fusion* f) {
   if (f->h_gloop) (void)hipHostFree(f->h_gloop);
   if (f->odom_m2m) dms_odometry_destroy(f->odom_m2m);
   if (f->deform) dms_deform_destroy(f->deform);
+  if (f->gdeform) dms_deform_destroy(f->gdeform);
+  if (f->pg_ticks_dev) (void)hipFree(f->pg_ticks_dev);
+  if (f->pg_poses_dev) (void)hipFree(f->pg_poses_dev);
   dms_odometry_destroy(f->odom);
   dms_model* const own = f->own_model ? f->own_model : f->model;
   if (f->model && f->model != own) f->model->sharers -= 1;  // (a joined camera: the map's owner outlives it, dmslam_fusion.h)
@@ -1398,6 +1408,10 @@ int dms_fusion_process_frame_begin(dms_fusion* f, const void* rgb_dev, int rgb_c
   DMS_REQUIRE(f && rgb_dev && depth_dev, "null argument");
   DMS_REQUIRE(rgb_channels == 3 || rgb_channels == 4, "rgb_channels must be 3 or 4");
   DMS_REQUIRE(!f->in_frame, "dms_fusion_process_frame_end has not been called for the previous frame");
+  if (f->global_solver && !f->one_call_now && (int)f->pg_ticks.size() >= f->max_poses) {  // (the one-call frame has checked already)
+    set_error("%s: the pose graph holds the %d poses it was made for", __func__, f->max_poses);
+    return DMS_ERR_CAPACITY;
+  }
   f->lazy.pending = false;  // the skipped prediction of the previous frame: from here on the images are this frame's, as they always were
   f->armed_now = f->armed;  // (the arming holds for this frame only, whatever path it takes)
   f->armed = dms_fusion::ArmedBlock();
@@ -1593,8 +1607,72 @@ static int close_local_loop(dms_fusion* f, hipStream_t s, const float** table_de
   return DMS_OK;
 }
 
+// The solve of an ORB-triggered global loop (ElasticFusion.cpp:327-345 / :1193-1211) on the rows global_loop_device left in device
+// memory: the local graph is sampled from the map as it stands and every 5th of its nodes becomes the global graph (what the
+// reference did at the end of the previous frame, :578-581), the frame's rows go in with srcTime = tick and pins, then the kept
+// relative rows, the pose graph as the poses, and the solve.  Two host reads: the row count, and the status.  Applied: *nodes and
+// *table_dev are set, the corrected poses replace the pose graph and fernDeforms is counted.
+static int solve_global_loop(dms_fusion* f, hipStream_t s, const float** table_dev, int* nodes) {
+  *nodes = 0;
+  int rc;
+  DMS_HIP(hipStreamSynchronize(s));
+  const int n = *(const int*)f->h_gloop;
+  if (n <= 0) return DMS_OK;
+  if ((rc = dms_deform_sample_model(f->deform, f->model, f->graph_sample_rate, (dms_stream)s))) return rc;
+  if ((rc = dms_deform_sample_from(f->gdeform, f->deform, (dms_stream)s))) return rc;
+  if ((rc = dms_deform_clear_constraints(f->gdeform))) return rc;
+  if ((rc = deform_add_rows(f->gdeform, (const float*)(f->gloop + 256), 8, n, f->tick, 1, s))) return rc;
+  if (!f->relative_cons.empty() &&
+      (rc = dms_deform_add_relative_constraints_host(f->gdeform, f->relative_cons.data(), (int)(f->relative_cons.size() / 8), (dms_stream)s)))
+    return rc;
+  const int np = (int)f->pg_ticks.size();
+  if (np) DMS_HIP(hipMemcpyAsync(f->pg_ticks_dev, f->pg_ticks.data(), (size_t)np * sizeof(long long), hipMemcpyHostToDevice, s));
+  if ((rc = dms_deform_set_poses(f->gdeform, f->pg_ticks_dev, f->pg_poses_dev, np, (dms_stream)s))) return rc;
+  if ((rc = dms_deform_constrain_global(f->gdeform, f->tick, (dms_stream)s))) return rc;
+  dms_deform_result res;
+  if ((rc = dms_deform_get_result(f->gdeform, &res))) return rc;
+  if (!res.applied || res.nodes <= 0) return DMS_OK;
+  if (np)
+    DMS_HIP(hipMemcpyAsync(f->pg_poses_dev, deform_poses_device(f->gdeform), (size_t)np * 16 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  const int* count_dev;
+  if ((rc = dms_deform_graph_device(f->gdeform, table_dev, &count_dev))) return rc;
+  *nodes = res.nodes;
+  f->fern_deforms += 1;  // fernDeforms += rawGraph.size() > 0 (:350)
+  return DMS_OK;
+}
+
+// Context::poseGraph().push_back(tick, currPose) (:571-573) behind a frame: the pose is in device memory, one 64-byte copy
+static int keep_pose(dms_fusion* f, long long tick, hipStream_t s) {
+  DMS_HIP(hipMemcpyAsync(f->pg_poses_dev + 16 * f->pg_ticks.size(), f->state->cur.pose, 16 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  f->pg_ticks.push_back(tick);
+  return DMS_OK;
+}
+
+static int process_frame_one_call(dms_fusion* f, const void* rgb_dev, int rgb_channels, const unsigned short* depth_dev, const float* inPose16,
+                                  float weightMultiplier, dms_stream st);
+
 int dms_fusion_process_frame(dms_fusion* f, const void* rgb_dev, int rgb_channels, const unsigned short* depth_dev, const float* inPose16,
                              float weightMultiplier, dms_stream st) {
+  if (!f || !f->global_solver) return process_frame_one_call(f, rgb_dev, rgb_channels, depth_dev, inPose16, weightMultiplier, st);
+  DMS_REQUIRE(f->model->sharers == 1 && f->clusters.size() == 1 && f->req_cluster == 0,
+              "the global loop solver needs a map this camera owns alone, without clusters");
+  if ((int)f->pg_ticks.size() >= f->max_poses) {
+    set_error("%s: the pose graph holds the %d poses it was made for", __func__, f->max_poses);
+    return DMS_ERR_CAPACITY;
+  }
+  // the global object takes DMS_DEFORM_MAX_RELATIVE relative rows: an armed frame that would hand over more is refused here, whole
+  if (f->orb_armed && f->relative_cons.size() / 8 > (size_t)DMS_DEFORM_MAX_RELATIVE) {
+    set_error("%s: %zu kept relative constraints, the global solve takes %d", __func__, f->relative_cons.size() / 8, DMS_DEFORM_MAX_RELATIVE);
+    return DMS_ERR_CAPACITY;
+  }
+  const long long tick = f->tick;
+  const int rc = process_frame_one_call(f, rgb_dev, rgb_channels, depth_dev, inPose16, weightMultiplier, st);
+  if (rc) return rc;
+  return keep_pose(f, tick, (hipStream_t)st);
+}
+
+static int process_frame_one_call(dms_fusion* f, const void* rgb_dev, int rgb_channels, const unsigned short* depth_dev, const float* inPose16,
+                                  float weightMultiplier, dms_stream st) {
   // what the loop solver cannot run on is refused before anything of the frame is enqueued
   DMS_REQUIRE(!f || !f->loop_solver || (f->model->sharers == 1 && f->clusters.size() == 1 && f->req_cluster == 0),
               "the loop solver needs a map this camera owns alone, without clusters");
@@ -1602,6 +1680,17 @@ int dms_fusion_process_frame(dms_fusion* f, const void* rgb_dev, int rgb_channel
   int rc = dms_fusion_process_frame_begin(f, rgb_dev, rgb_channels, depth_dev, inPose16, weightMultiplier, st);
   if (f) f->one_call_now = false;
   if (rc) return rc;
+  if (f->global_solver && f->gloop_ran && !f->cur_bootstrap) {
+    // the ORB loop's solve (ElasticFusion.cpp:327-353).  Applied: the frame ends as dms_fusion_process_frame_end(graph, nodes, NULL)
+    // ends an ORB-armed frame; not applied: it goes on into the local block below
+    const float* table_dev = nullptr;
+    int nodes = 0;
+    if ((rc = solve_global_loop(f, (hipStream_t)st, &table_dev, &nodes))) {
+      (void)process_frame_end(f, nullptr, 0, nullptr, st, true);
+      return rc;
+    }
+    if (nodes > 0) return process_frame_end(f, nullptr, nodes, nullptr, st, true, table_dev);
+  }
   if (f->loop_solver && f->p.local_loop_closure && !f->cur_bootstrap && !f->lost) {
     const float* table_dev = nullptr;
     const float* est_pose = nullptr;
@@ -1641,6 +1730,45 @@ int dms_fusion_set_loop_solver(dms_fusion* f, int on, int sampleRate) {
   return DMS_OK;
 }
 
+int dms_fusion_set_global_loop_solver(dms_fusion* f, int on, int max_poses) {
+  DMS_REQUIRE(f, "null argument");
+  DMS_REQUIRE(!f->in_frame && !f->in_global_loop, "between process_frame_begin and _end");
+  if (!on) {
+    f->global_solver = false;
+    return DMS_OK;
+  }
+  DMS_REQUIRE(f->p.hybrid_loops, "the context was created without hybrid_loops");
+  DMS_REQUIRE(f->model == f->clusters[0] && f->model->sharers == 1 && f->clusters.size() == 1 && f->req_cluster == 0,
+              "the global loop solver needs a map this camera owns alone, without clusters");
+  const int cons = (f->p.width / 20) * (f->p.height / 20);
+  DMS_REQUIRE(cons >= 1 && cons <= DMS_DEFORM_MAX_CONSTRAINTS, "the frame size gives more constraint samples than the solver takes");
+  DMS_REQUIRE(max_poses >= 1 && max_poses <= DMS_DEFORM_MAX_POSES, "max_poses outside [1, DMS_DEFORM_MAX_POSES]");
+  DMS_REQUIRE(!f->gdeform || max_poses == f->max_poses, "max_poses differs from the first switching on");
+  int rc;
+  if (!f->deform && (rc = dms_deform_create(&f->deform, DMS_DEFORM_MAX_NODES - 1, cons))) return rc;
+  if (!f->gdeform) {
+    if ((rc = dms_deform_create_global(&f->gdeform, DMS_DEFORM_MAX_GLOBAL_NODES, cons, DMS_DEFORM_MAX_RELATIVE, max_poses))) return rc;
+    DMS_HIP(hipMalloc((void**)&f->pg_ticks_dev, (size_t)max_poses * sizeof(long long)));
+    DMS_HIP(hipMalloc((void**)&f->pg_poses_dev, (size_t)max_poses * 16 * sizeof(float)));
+    f->max_poses = max_poses;
+  }
+  f->global_solver = true;
+  return DMS_OK;
+}
+dms_deform* dms_fusion_global_deformation(dms_fusion* f) { return f ? f->gdeform : nullptr; }
+int dms_fusion_get_fern_deforms(dms_fusion* f) { return f ? f->fern_deforms : 0; }
+int dms_fusion_get_pose_graph(dms_fusion* f, long long* ticks_host, float* poses16_host, int max_poses, int* n) {
+  DMS_REQUIRE(f && n && ((ticks_host && poses16_host) || max_poses == 0), "null argument");
+  *n = (int)f->pg_ticks.size();
+  const int take = *n < max_poses ? *n : max_poses;
+  if (take > 0) {
+    DMS_HIP(hipDeviceSynchronize());
+    memcpy(ticks_host, f->pg_ticks.data(), (size_t)take * sizeof(long long));
+    DMS_HIP(hipMemcpy(poses16_host, f->pg_poses_dev, (size_t)take * 16 * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  return DMS_OK;
+}
+
 dms_deform* dms_fusion_deformation(dms_fusion* f) { return f ? f->deform : nullptr; }
 int dms_fusion_get_deforms(dms_fusion* f) { return f ? f->deforms : 0; }
 int dms_fusion_get_relative_constraints(dms_fusion* f, float* rows8_host, int max_rows, int* n) {
@@ -1651,7 +1779,12 @@ int dms_fusion_get_relative_constraints(dms_fusion* f, float* rows8_host, int ma
 }
 
 int dms_fusion_process_frame_end(dms_fusion* f, const float* graph_host, int graph_nodes, const float* newPose16, dms_stream st) {
-  return process_frame_end(f, graph_host, graph_nodes, newPose16, st, false);
+  if (!f || !f->global_solver || !f->in_frame) return process_frame_end(f, graph_host, graph_nodes, newPose16, st, false);
+  // the pose graph has no holes: a two-phase frame run while the global loop solver is on is kept as a one-call frame is
+  const long long tick = f->tick;
+  const int rc = process_frame_end(f, graph_host, graph_nodes, newPose16, st, false);
+  if (rc) return rc;
+  return keep_pose(f, tick, (hipStream_t)st);
 }
 
 int dms_fusion_get_lazy_stats(dms_fusion* f, int* eager, long* deferred, long* materialised, long* stale) {
@@ -1862,10 +1995,31 @@ int dms_fusion_apply_global_loop_begin(dms_fusion* f, const float* orbTcwOld16, 
   return DMS_OK;
 }
 
+static int apply_global_loop_end(dms_fusion* f, const float* graph_host, const float* graph_dev, int graph_nodes, int accepted, dms_stream st);
 int dms_fusion_apply_global_loop_end(dms_fusion* f, const float* graph_host, int graph_nodes, int accepted, dms_stream st) {
+  return apply_global_loop_end(f, graph_host, nullptr, graph_nodes, accepted, st);
+}
+// ElasticFusion::applyGlobalLoop (:1148-1240) whole: _begin, the solve, _end(table, nodes, accepted) with the table from device memory
+int dms_fusion_apply_global_loop(dms_fusion* f, const float* orbTcwOld16, const float* orbTcwNew16, dms_stream st) {
+  DMS_REQUIRE(f && f->global_solver, "dms_fusion_set_global_loop_solver is off");
+  DMS_REQUIRE(f->model->sharers == 1 && f->clusters.size() == 1 && f->req_cluster == 0,
+              "the global loop solver needs a map this camera owns alone, without clusters");
+  if (f->relative_cons.size() / 8 > (size_t)DMS_DEFORM_MAX_RELATIVE) {
+    set_error("%s: %zu kept relative constraints, the global solve takes %d", __func__, f->relative_cons.size() / 8, DMS_DEFORM_MAX_RELATIVE);
+    return DMS_ERR_CAPACITY;
+  }
+  int rc = dms_fusion_apply_global_loop_begin(f, orbTcwOld16, orbTcwNew16, st);
+  if (rc) return rc;
+  const float* table_dev = nullptr;
+  int nodes = 0;
+  rc = solve_global_loop(f, (hipStream_t)st, &table_dev, &nodes);
+  const int rc_end = apply_global_loop_end(f, nullptr, table_dev, rc ? 0 : nodes, !rc && nodes > 0, st);
+  return rc ? rc : rc_end;
+}
+static int apply_global_loop_end(dms_fusion* f, const float* graph_host, const float* graph_dev, int graph_nodes, int accepted, dms_stream st) {
   DMS_REQUIRE(f, "null argument");
   DMS_REQUIRE(f->in_global_loop, "dms_fusion_apply_global_loop_begin has not been called");
-  DMS_REQUIRE(graph_nodes == 0 || graph_host, "null graph");
+  DMS_REQUIRE(graph_nodes == 0 || graph_host || graph_dev, "null graph");
   hipStream_t s = (hipStream_t)st;
   f->in_global_loop = false;
   int rc;
@@ -1879,7 +2033,7 @@ int dms_fusion_apply_global_loop_end(dms_fusion* f, const float* graph_host, int
   if ((rc = index_map(f->model, &f->state->cur, &f->cam, f->tick, f->p.timeIdx, f->p.maxDepthProcessed, timeDeltaEff, f->zbuf, &f->imap, 1, 1, s)))
     return rc;
   return model_clean(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->imap, nullptr, &f->cam, f->p.confidence, graph_host, graph_nodes,
-                     timeDeltaEff, f->p.maxDepthProcessed, accepted ? 1 : 0, 1, &f->state->surfels, s);
+                     timeDeltaEff, f->p.maxDepthProcessed, accepted ? 1 : 0, 1, &f->state->surfels, s, graph_dev);
 }
 
 int dms_relative_transform(const float* recoveryPose16, const float* currPose16, float* out16) {

@@ -134,6 +134,7 @@ int model_clean(dms_model* m, const dms_pose_block* pose, int time, int timeIdx,
 int deform_add_rows(dms_deform* d, const float* rows_dev, int stride, int n, int srcTime, int pin, hipStream_t s);
 // status block and new relative-constraint rows (pinned, rows of 8 floats) behind one synchronisation
 int deform_fetch(dms_deform* d, dms_deform_result* res, const float** rel8);
+const float* deform_poses_device(dms_deform* d);
 
 // track.hip
 struct TrackFold {  // the track call a model pyramid launch prepares (odometry_initModel_fused)

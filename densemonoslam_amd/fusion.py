@@ -768,6 +768,49 @@ class ElasticFusion:
               "dms_fusion_get_relative_constraints")
         return out[:n.value].copy()
 
+    def setGlobalLoopSolver(self, on=True, max_poses=4096):
+        """A processFrame armed by setOrbLoop, and applyGlobalLoop, close the ORB loop themselves (dms_fusion_set_global_loop_solver);
+        the context keeps its pose graph while this is on"""
+        lib.dms_fusion_set_global_loop_solver.argtypes = [_P, _I, _I]
+        check(lib.dms_fusion_set_global_loop_solver(self.h, int(bool(on)), int(max_poses)), "dms_fusion_set_global_loop_solver")
+        self._max_poses = int(max_poses)
+
+    def applyGlobalLoop(self, orbTcwOld, orbTcwNew, stream=None):
+        """ElasticFusion::applyGlobalLoop (ElasticFusion.cpp:1148-1240) in one call, the solve on the GPU"""
+        a = np.ascontiguousarray(orbTcwOld, np.float32).reshape(16)
+        b = np.ascontiguousarray(orbTcwNew, np.float32).reshape(16)
+        fp = lambda v: v.ctypes.data_as(C.POINTER(C.c_float))
+        lib.dms_fusion_apply_global_loop.argtypes = [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), _P]
+        check(lib.dms_fusion_apply_global_loop(self.h, fp(a), fp(b), stream), "dms_fusion_apply_global_loop")
+
+    def globalDeformation(self):
+        """The context's global solver as a deform.GlobalDeformation view (None until the global loop solver was first switched on)"""
+        from . import deform
+
+        lib.dms_fusion_global_deformation.restype = C.c_void_p
+        lib.dms_fusion_global_deformation.argtypes = [_P]
+        h = lib.dms_fusion_global_deformation(self.h)
+        if not h:
+            return None
+        d = deform.GlobalDeformation.view(h, (self.width // 20) * (self.height // 20), deform.MAX_GLOBAL_NODES)
+        d.max_relative, d.max_poses = deform.MAX_RELATIVE, self._max_poses
+        return d
+
+    def fernDeforms(self):
+        """ElasticFusion::getFernDeforms: ORB loops the global loop solver closed"""
+        lib.dms_fusion_get_fern_deforms.argtypes = [_P]
+        return int(lib.dms_fusion_get_fern_deforms(self.h))
+
+    def poseGraph(self):
+        """Context::poseGraph(): (ticks int64, poses n x 4 x 4 float32)"""
+        lib.dms_fusion_get_pose_graph.argtypes = [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_float), _I, C.POINTER(C.c_int)]
+        n = C.c_int(0)
+        check(lib.dms_fusion_get_pose_graph(self.h, None, None, 0, C.byref(n)), "dms_fusion_get_pose_graph")
+        t, p = np.zeros(max(1, n.value), np.int64), np.zeros((max(1, n.value), 4, 4), np.float32)
+        check(lib.dms_fusion_get_pose_graph(self.h, t.ctypes.data_as(C.POINTER(C.c_longlong)), p.ctypes.data_as(C.POINTER(C.c_float)), n.value,
+                                            C.byref(n)), "dms_fusion_get_pose_graph")
+        return t[:n.value].copy(), p[:n.value].copy()
+
     OPTIONS = {"rgbOnly": 0, "icpWeight": 1, "pyramid": 2, "fastOdom": 3, "so3": 4, "frameToFrameRGB": 5, "confidence": 6, "depthCut": 7}
 
     def setOption(self, name, value):

@@ -8,8 +8,14 @@
  * order and no floating-point atomic is used: the same input gives the same bits on every run.  Row and weight arithmetic is
  * csrc/deform_rows.hpp, which states the order rules; tests/deform_ref.py is the CPU restatement the results are held against.
  *
- * Not here (the caller's solver, through dms_fusion_process_frame_begin / _end as before): relative constraints, fernMatch = true,
- * applyGraphToPoses.
+ * A second kind of object (dms_deform_create_global, at the end of this header) is rf.globalDeformation(): relative constraints,
+ * fernMatch = true with its two early exits and its acceptance test, and applyGraphToPoses.  Relative constraints break the band, so
+ * its factorisation is a block Cholesky over the row envelope of A.
+ *
+ * dms_fusion_set_global_loop_solver (last section) lets the frame step drive it: an ORB-armed frame becomes one call.
+ *
+ * Not here: no fern-matched closure policy (the reference compiles it out, ElasticFusion.cpp:359), no relocalisation, not several
+ * cameras on one map.
  *
  * EDGE RULES
  *   no enabled node (every node's time <= lastDeformTime)   zero delta, the table of the untouched nodes, applied = 1, exit reason
@@ -46,7 +52,10 @@ enum {
   DMS_DEFORM_EXIT_SMALL_DELTA = 2,
   DMS_DEFORM_EXIT_SMALL_ERROR = 3,
   DMS_DEFORM_EXIT_SMALL_CHANGE = 4,
-  DMS_DEFORM_EXIT_NO_ENABLED_NODE = 5
+  DMS_DEFORM_EXIT_NO_ENABLED_NODE = 5,
+  /* objects of dms_deform_create_global only (fernMatch = true) */
+  DMS_DEFORM_EXIT_CONSTRAINTS_MET = 6, /* meanConsErr < 0.06 before the loop (:465): optimised = 0, no iteration */
+  DMS_DEFORM_EXIT_ERROR_LARGE = 7      /* error > 10 after iteration 1 (:516), the last test of :515 */
 };
 
 typedef struct dms_deform_result {
@@ -115,6 +124,57 @@ int dms_deform_get_first_delta(dms_deform* d, double* delta_host, int max_unknow
 /* the pool after applyGraphToVertices (Deformation.cpp:169): xyz per vertex */
 int dms_deform_get_pool(dms_deform* d, float* xyz_host, int max_vertices, int* n);
 
+/* ---- rf.globalDeformation(): relative constraints, fernMatch = true, the poses -----------------------------------------------------
+ * An object of dms_deform_create_global keeps every call above (dms_deform_constrain on it is the band solve, and gives a
+ * dms_deform_create object's bits; not while its pool holds relative constraints: DMS_ERR_STATE) and adds the calls below.
+ *
+ * dms_deform_constrain_global is Deformation::constrain(..., fernMatch = true, poseGraph, relaxGraph = true): lastDeformTime is taken
+ * as 0 (:161) and not advanced (:203), no newRelativeCons are made.  Enqueued whole, no host read inside.
+ *   rows     a relative constraint has a row when any node of its source vertex is enabled, or else any of its target vertex
+ *            (:668-680); residual (srcPos - tarPos) sqrt(wCon); Jacobian row from the two weight maps merged as csrc/deform_rows.hpp
+ *            states (one entry per column where both vertices have a node).  meanConsErr sums the non-relative constraints, pins
+ *            included, over the count of ALL constraints (:1011-1026).
+ *   exits    DMS_DEFORM_EXIT_CONSTRAINTS_MET and _ERROR_LARGE above, besides those of the band object
+ *   applied  only when optimised && meanConsErr < 0.0003 && error < 0.12 (Deformation.cpp:165).  When not applied the poses, the pool
+ *            (dms_deform_get_pool then still gives the last applied solve's) and the node table are not written; the node rotations
+ *            stay as the loop left them, as the reference's do, until the next dms_deform_set_nodes / _sample_from.
+ *   poses    applyGraphToPoses (:102-131) with setPosesSeq's weights, one lane per pose.  U V^T of rotation * R is the orthogonal
+ *            polar factor, taken in fp64 by a fixed number of Newton steps (csrc/deform_rows.hpp) and rounded to fp32 once: Eigen's
+ *            fp32 Jacobi SVD cannot be pinned bit for bit; the fp64 result is closer to the exact factor than the reference's fp32
+ *            rounding.  A matrix that is not finite, or whose determinant has magnitude below 2^-20, keeps the pose's old rotation
+ *            and is counted (dms_deform_get_kept_rotations).
+ *   solve    A = J^T J is assembled in fp64 over its row envelope (first[i] = the smallest block column any row of J couples
+ *            enabled node i to) into a dense lower block triangle allocated at create time (97 MB at 410 nodes) and factored by a
+ *            right-looking block Cholesky whose fill stays inside the envelope.  Fixed orders, no floating-point atomic.
+ *   the singular-pivot rule and the no-graph rule are those of the EDGE RULES above. */
+#define DMS_DEFORM_MAX_GLOBAL_NODES 410 /* ceil(2047 / 5): sampleGraphFrom takes every 5th node of at most 2047 */
+#define DMS_DEFORM_MAX_RELATIVE 2048    /* relative constraint rows per solve (two pool vertices each) */
+#define DMS_DEFORM_MAX_POSES 65536
+/* max_nodes in [5, DMS_DEFORM_MAX_GLOBAL_NODES], max_constraints as above, max_relative in [0, DMS_DEFORM_MAX_RELATIVE], max_poses in
+ * [0, DMS_DEFORM_MAX_POSES]. */
+int dms_deform_create_global(dms_deform** out, int max_nodes, int max_constraints, int max_relative, int max_poses);
+/* Deformation::sampleGraphFrom (Deformation.cpp:222-249): every 5th node row of `local` (a dms_deform_create object), counted on the
+ * device; the graph is replaced (identity rotations, zero translations) only when count / 5 > 4, else kept.  A local graph that
+ * gives more samples than this object was made for gives the first max_nodes of them (the rule of dms_deform_sample_model). */
+int dms_deform_sample_from(dms_deform* global, dms_deform* local, dms_stream s);
+/* n rows {source xyz, target xyz, source time, target time} (what dms_deform_get_relative_constraints writes), each a
+ * Constraint(..., relative = true): TWO pool vertices (Deformation.cpp:131-140), source then target.  Constraints stand in the pool in
+ * the order of the calls, dms_deform_add_constraints included.  More than max_relative in all: DMS_ERR_CAPACITY, nothing added. */
+int dms_deform_add_relative_constraints(dms_deform* d, const float* rows8_dev, int n, dms_stream s);
+/* the same from host memory (copied on `s` into the object's staging buffer; the rows may be reused once `s` has passed the call) */
+int dms_deform_add_relative_constraints_host(dms_deform* d, const float* rows8_host, int n, dms_stream s);
+/* The poses the next solve corrects: n times and row-major 4 x 4 matrices in device memory (copied).  n > max_poses:
+ * DMS_ERR_CAPACITY, nothing changed.  dms_deform_get_poses copies them back (corrected, after an applied solve); synchronises. */
+int dms_deform_set_poses(dms_deform* d, const long long* times_dev, const float* poses16_dev, int n, dms_stream s);
+int dms_deform_get_poses(dms_deform* d, long long* times_host, float* poses16_host, int max_poses, int* n);
+int dms_deform_constrain_global(dms_deform* d, int time, dms_stream s);
+/* poses whose rotation the last global solve kept (see `poses` above) */
+int dms_deform_get_kept_rotations(dms_deform* d, int* kept);
+/* for tests: setPosesSeq's nodes and weights of the last global solve's poses, and the row envelope (per enabled node, its first
+ * block column counted from the first enabled node; empty when no iteration ran) */
+int dms_deform_get_pose_weights(dms_deform* d, int* ids4_host, double* weights4_host, int max_poses, int* n);
+int dms_deform_get_envelope(dms_deform* d, int* first_host, int max_nodes, int* n);
+
 /* ---- the frame step closes its local loops itself --------------------------------------------------------------------------------
  * With the solver on and local_loop_closure = 1, dms_fusion_process_frame does what ElasticFusion.cpp:441-493 does: after the loop
  * candidate the host reads the frame's loop_ok word (one mid-frame synchronisation, as the NID gate and --rl have and as the reference
@@ -133,6 +193,32 @@ dms_deform* dms_fusion_deformation(dms_fusion* f);
 int dms_fusion_get_deforms(dms_fusion* f);
 /* context.relativeCons(): the kept rows {deformed source xyz, target xyz, source time, target time} of all closing frames so far */
 int dms_fusion_get_relative_constraints(dms_fusion* f, float* rows8_host, int max_rows, int* n);
+
+/* ---- the frame step closes ORB-triggered global loops itself -----------------------------------------------------------------------
+ * With the global loop solver on (needs hybrid_loops; the refusals of dms_fusion_set_loop_solver hold: a map the camera owns alone, no
+ * clusters, W/20 x H/20 <= DMS_DEFORM_MAX_CONSTRAINTS; off by default, with it off nothing changes; the two-phase calls are not
+ * affected otherwise) the context keeps Context::poseGraph() (ElasticFusion.cpp:571-573): behind every frame, one-call or two-phase,
+ * the tick before its increment and the pose after the frame (one 64-byte copy in device memory, no synchronisation).  A frame that
+ * would be pose max_poses + 1 returns DMS_ERR_CAPACITY before anything of it is enqueued.  So does an ORB-armed one-call frame, and
+ * dms_fusion_apply_global_loop, once the context has kept more than DMS_DEFORM_MAX_RELATIVE relative rows (3 to 4 per local closure).
+ *
+ * A one-call dms_fusion_process_frame armed by dms_fusion_set_orb_loop then does what :292-355 does: after the constraint kernel the
+ * host reads the row count; the local graph is sampled from the map as it stands (the local solver object is created if the local
+ * solver never was; sampleRate as there, 5000 until set) and every 5th of its nodes becomes the global graph
+ * (dms_deform_sample_from); the frame's rows go in with srcTime = tick and pins (:327-330), then the context's kept relative rows
+ * (:335-341), the pose graph as the poses, and dms_deform_constrain_global; the host reads the status.  Applied: the corrected poses
+ * replace the pose graph, fernDeforms is counted and the frame ends as dms_fusion_process_frame_end(graph, nodes, NULL) ends an
+ * ORB-armed frame, the table taken from device memory.  Not applied: the frame goes on into the local block as before, with the local
+ * solver if that is on.  dms_fusion_apply_global_loop is ElasticFusion::applyGlobalLoop (:1148-1240): _begin, the same solve, and
+ * _end(table, nodes, accepted).
+ * Known deviation: the reference re-samples both graphs at the end of every frame (:578-581), this samples when a loop arrives; the
+ * two differ only when the earlier frame's sample passed count / 5 > 4 and the current one does not. */
+int dms_fusion_set_global_loop_solver(dms_fusion* f, int on, int max_poses);
+int dms_fusion_apply_global_loop(dms_fusion* f, const float* orbTcwOld16, const float* orbTcwNew16, dms_stream s);
+/* rf.globalDeformation() of this context (NULL until first switched on); ElasticFusion::fernDeforms; Context::poseGraph() */
+dms_deform* dms_fusion_global_deformation(dms_fusion* f);
+int dms_fusion_get_fern_deforms(dms_fusion* f);
+int dms_fusion_get_pose_graph(dms_fusion* f, long long* ticks_host, float* poses16_host, int max_poses, int* n);
 
 #ifdef __cplusplus
 }

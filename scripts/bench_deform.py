@@ -7,6 +7,13 @@
           the loop is found and dropped - and of a stream on which no loop is accepted (timeDelta = 200: the INACTIVE view stays empty), ON against OFF: that difference is the cost of
           the mid-frame read of the loop's verdict.  ON and OFF runs alternate (A B A B ...), one context each, same frames.
 
+  global  the stand-alone dms_deform_constrain_global at 410 nodes and 2048 pinned rows with 0, 4 and 32 relative rows between the two
+          ends of the graph, and the band object's dms_deform_constrain on the same absolute-only problem for comparison; and the
+          closing frame: a 640 x 480 stream whose map is sampled at a rate that fills the local graph (2047 nodes, so 410 global
+          nodes), the frame armed with an ORB loop against the same frame not armed, global loop solver on in both.  The frame step
+          takes its relative rows from the context's own earlier closures and this stream has none, so the closing frame is measured
+          with 0 relative rows only.
+
     python scripts/bench_deform.py [--reps 20] [--warmup 3] [--rounds 4] [--frames 12] [--out profiles/deform_bench.jsonl]
 """
 import argparse
@@ -49,6 +56,93 @@ def solve_table(args):
                          status=r.status, ms_median=float(np.median(ms)), ms_min=float(np.min(ms)), ms_max=float(np.max(ms)), reps=len(ms)))
         d.close()
     return dict(table="solve", rows=rows)
+
+
+def global_table(args):
+    import torch
+
+    from densemonoslam_amd import deform
+    from tests import deform_global_cases as GC
+
+    def timed(run, prepare):
+        ms = []
+        for rep in range(args.warmup + args.reps):
+            prepare()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            run()
+            b.record()
+            b.synchronize()
+            if rep >= args.warmup:
+                ms.append(a.elapsed_time(b))
+        return dict(ms_median=float(np.median(ms)), ms_min=float(np.min(ms)), ms_max=float(np.max(ms)), reps=len(ms))
+
+    rows = []
+    for nrel in (0, 4, 32):
+        c = GC.GCase("n410_c2048_r%d" % nrel, 410, 35, lambda c: [GC._abs(c, 2048, 35, 8.0)] + (
+            [GC._rels(c, [(409 - 3 * (i % 8) - i // 8, 2 * (i % 8) + i // 8) for i in range(nrel)], 35)] if nrel else []))
+        d = deform.GlobalDeformation(max_nodes=410, max_constraints=2048, max_relative=32, max_poses=16)
+
+        def prepare(d=d, c=c):
+            d.setNodes(c.nodes)
+            d.clearConstraints()
+            for call in c.calls:
+                d.addConstraints(call[1], call[2], call[3]) if call[0] == "abs" else d.addRelativeConstraints(call[1])
+            d.setPoses(c.pose_times, c.poses)
+
+        t = timed(lambda: d.constrainGlobal(c.tick), prepare)
+        r = d.result()
+        first = d.envelope()
+        rows.append(dict(solver="global", nodes=410, constraints=2048, relative=nrel, tall_rows=int((np.arange(len(first)) - first > 19).sum()),
+                         iterations=r.iterations, exit_reason=r.exit_reason, status=r.status, applied=r.applied, **t))
+        if nrel == 0:
+            b = deform.Deformation(max_nodes=410, max_constraints=2048)
+
+            def prepare_band(b=b, c=c):
+                b.setNodes(c.nodes)
+                b.setLastDeformTime(0)
+                b.clearConstraints()
+                b.addConstraints(c.calls[0][1], c.tick, True)
+
+            t = timed(lambda: b.constrain(c.tick), prepare_band)
+            r = b.result()
+            rows.append(dict(solver="band", nodes=410, constraints=2048, relative=0, tall_rows=0, iterations=r.iterations, exit_reason=r.exit_reason,
+                             status=r.status, applied=r.applied, **t))
+            b.close()
+        d.close()
+    return dict(table="global", rows=rows, closing_frame=closing_frame(args))
+
+
+def closing_frame(args):
+    from densemonoslam_amd import fusion, synth
+
+    W, H, K = 640, 480, (528.0, 528.0, 320.0, 240.0)
+    frames = _stream(fusion, synth, 8, True)
+    ms = {True: [], False: []}
+    info = {}
+    for rnd in range(args.rounds):
+        for armed in (True, False):
+            g = fusion.ElasticFusion(W, H, K, model_capacity=2500000, timeDelta=2, confidence=1.0, local_loop_closure=True, hybrid_loops=1)
+            g.setLoopSolver(True, 100)
+            g.setLoopSolver(False, 100)
+            g.setGlobalLoopSolver(True, 64)
+            poses = []
+            for k, (rgb, d) in enumerate(frames):
+                if armed and k == 6:
+                    new = poses[-1].copy()
+                    new[:3, 3] += np.array([0.1, -0.05, 0.033], np.float32)
+                    g.setOrbLoop(poses[2].copy(), new)
+                t0 = time.perf_counter()
+                r = g.processFrame(rgb, d)
+                if k == 6:
+                    ms[armed].append(1e3 * (time.perf_counter() - t0))
+                    if armed:
+                        res = g.globalDeformation().result()
+                        info = dict(nodes=res.nodes, rows=res.constraints // 2, iterations=res.iterations, exit_reason=res.exit_reason, applied=res.applied)
+                poses.append(np.array(r.pose, np.float32).reshape(4, 4))
+            g.close()
+    return dict(relative=0, rounds=args.rounds, ms_armed=float(np.median(ms[True])), ms_not_armed=float(np.median(ms[False])), **info)
 
 
 def _stream(fusion, synth, frames, closing):
@@ -103,8 +197,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-frames", action="store_true")
     ap.add_argument("--skip-solve", action="store_true")
+    ap.add_argument("--skip-global", action="store_true")
     args = ap.parse_args()
     tables = [] if args.skip_solve else [solve_table(args)]
+    if not args.skip_global:
+        tables.append(global_table(args))
     if not args.skip_frames:
         tables.append(frame_table(args))
     for t in tables:
