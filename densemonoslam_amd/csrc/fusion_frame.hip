@@ -18,6 +18,7 @@
 #include "internal.hpp"
 #include "host_util.hpp"
 #include "late_frame.hpp"
+#include "resident_rule.hpp"
 #include "smallmath.hpp"
 #include "surfel.hpp"
 #include "canon.hpp"
@@ -831,20 +832,8 @@ int dms_fusion_create(dms_fusion** out, const dms_fusion_params* p) {
   }
   for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&f->ev_prep_done[k], hipEventDisableTiming);
   for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&f->ev_main_done[k], hipEventDisableTiming);
-  {  // Fat blocks of the depth pre-filter beside the tracker: at most 40, and never more than the resident tracker kernels leave
-    // free — a fat block holds a whole compute unit for the length of the filter, and a resident grid that finds fewer free units
-    // than it has blocks starts incomplete, its blocks spinning until the filter's retire.  Measured at 640x480 (round 4, the
-    // table form of the filter: 112 us on 56 units), driver's form: 16 / 24 / 32 / 40 / 43 / 48 / 50 / 56 / 60 blocks ->
-    // 2300 / 2326 / 2375 / 2386 / 2387 / 2388 / 2334 / 2305 / 2290 frames/s; the leg with three predictions per frame: 2412 at
-    // 34 - 40 blocks, 2292 at 43, 2370 at 56.  Below the cap the count is the smallest that keeps the number of rounds over the
-    // image's 64 x 16 tiles (300 tiles, 8 rounds: 38 blocks).
-    const int tiles = ((p->width + 63) / 64) * ((p->height + 15) / 16);
-    int cap = 40;
-    const int free_cus = odometry_free_cus(f->odom);
-    if (free_cus >= 16 && free_cus < cap) cap = free_cus;
-    const int rounds = (tiles + cap - 1) / cap;
-    f->prep_blocks = (tiles + rounds - 1) / rounds;
-  }
+  // fat blocks of the depth pre-filter beside the tracker, over the image's 64 x 16 tiles (the rule and its measurements: resident_rule.hpp)
+  f->prep_blocks = prep_blocks(((p->width + 63) / 64) * ((p->height + 15) / 16), odometry_free_cus(f->odom));
   if (const char* pb = getenv("DMS_PREP_BLOCKS")) f->prep_blocks = atoi(pb);
   if (const char* fl = getenv("DMS_FUSED_LIVE")) f->fused_live = atoi(fl) != 0;
   if (const char* ft = getenv("DMS_FOLD_TRACK_INIT")) f->fold_track_init = atoi(ft) != 0;

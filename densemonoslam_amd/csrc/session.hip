@@ -17,6 +17,7 @@
 
 #include "../../include/dmslam_session.h"
 #include "common.hpp"
+#include "resident_rule.hpp"
 
 namespace {
 
@@ -574,9 +575,9 @@ int drain_entries(dms_session* s) {
 
 // Trackers that run at the same time share the device.  In a pipelined tick the cameras of different hosted maps run on different streams;
 // by default resident tracker launches of different streams wait for each other (each needs all its blocks on the device at once:
-// level 0 takes 200 of the 256 units).  With `concurrent` streams the session caps every hosted camera's grids at (units - 16) /
-// concurrent blocks and lifts the chain for them (dms_odometry_set_resident_budget: 120 blocks each for two streams - level 0 then runs
-// five pixels per thread); one stream, a synchronous tick, or a frame too large for the capped grid: full grids, chained.  Same bits
+// level 0 takes 200 of the 256 units).  With `concurrent` streams the session caps every hosted camera's grids and lifts the chain for
+// them (resident_rule.hpp session_cap is the one statement of the rule; dms_odometry_set_resident_budget: 120 blocks each for two streams
+// - level 0 then runs five pixels per thread); one stream, a synchronous tick, or a frame too large for the capped grid: full grids, chained.  Same bits
 // either way.  Measured, two cameras before their maps merge: 3 155 against 2 566 frames/s; one stream with the cap: 2 258 against 2 437 -
 // hence per tick, by what the tick will run.  The inter-map trackers (queries, refinement) run in woken ticks, after every frame of
 // the tick has been fetched: alone.
@@ -584,11 +585,8 @@ int apply_tracker_policy(dms_session* s, int concurrent) {
   int cap = 0;
   if (s->share_device && concurrent >= 2) {
     int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus >= 64) {
-      cap = (cus - 16) / concurrent;
-      const long long px = (long long)s->W * s->H;
-      if (px > (long long)cap * 512 * 5) cap = 0;  // (level 0 at five pixels per thread of 512-thread blocks would not fit: a capped handle falls back to a launch per phase)
-    }
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
+      cap = dms::session_cap(cus, concurrent, s->W, s->H, s->share_device);
   }
   // (the "late frame" of dmslam_fusion.h is not for a session's cameras: the host has the exchange to enqueue and the earlier ticks'
   // tails to wait for between two frames, and its slack does not show where the context looks for it - measured with one hosted camera:

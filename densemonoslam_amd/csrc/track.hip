@@ -40,6 +40,7 @@
 #include "track_init.hpp"
 #include "model_bodies.hpp"
 #include "surfel.hpp"
+#include "resident_rule.hpp"
 #include <mutex>
 
 namespace dms {
@@ -74,19 +75,17 @@ struct dms_odometry {
   // every call let a changing environment switch the execution mode in the middle of a session.)
   bool resident = true;       // false: three launches per iteration (DMS_TRACK_MODE=launches)
   int early_exit_force = -1;  // -1: as `early_exit`; 0 / 1: forced (DMS_TRACK_EARLY_EXIT)
-  int persist_target = 160;   // largest grid that still gets 1 or 2 pixels per thread (DMS_PERSIST_BLOCKS)
-  // Resident kernels spin on each other: ALL blocks of a launch must be on the device at once.  One block (512 threads x
-  // up to 256 registers) fills a compute unit, so a grid may have at most as many blocks as the device has compute units
-  // (hipDeviceProp_t::multiProcessorCount: 256 on a whole MI355X, fewer on a partition / under a CU mask), checked against the
-  // occupancy API at creation; DMS_PERSIST_MAX_BLOCKS lowers it further.  A level that does not fit with <= 4 pixels per
-  // thread runs launch-per-phase.
-  int max_resident_blocks = 256;
+  int persist_target = kPersistTarget;  // largest grid that still gets 1 or 2 pixels per thread (DMS_PERSIST_BLOCKS)
+  // Resident kernels spin on each other: ALL blocks of a launch must be on the device at once (resident_rule.hpp holds every rule
+  // that follows from it).  The device's bound, set at creation (device_bound, lowered_bound); a level that does not fit it runs
+  // launch-per-phase.
+  int max_resident_blocks = kMaxPersistBlocks;
   // dms_odometry_set_resident_budget: a cap below the device's own bound, and the owner's word that every handle that may track at the same
   // time carries a cap such that all their grids fit the device together - such a handle's launches need no chain (PersistSection)
   int budget_cap = 0;
   bool unchained_ok = false;
   bool fell_back = false;     // a resident kernel timed out at a grid-wide wait: this handle has switched to launch-per-phase
-  // what persistent_shape() gave each level of the last tracker call (dms_odometry_get_level_shape); 0 blocks: launch-per-phase
+  // what call_level_shape() gave each level of the last tracker call (dms_odometry_get_level_shape); 0 blocks: launch-per-phase
   int last_shape_P[DMS_NUM_PYRS] = {1, 1, 1}, last_shape_nb[DMS_NUM_PYRS] = {0, 0, 0};
   // What the kernel that prepared the model side has left to the NEXT track call on this handle (frame step).  Two writers, each
   // overwriting the whole record: odometry_initModel_fused, and odometry_model_views_begin through fold_init_args.  One reader:
@@ -139,14 +138,9 @@ struct dms_odometry {
   unsigned* tickets = nullptr; // [4] arrival counters of the last-block-solves hand-off (zero between launches)
   unsigned long long* ar = nullptr;   // [kArSets][kArWords] all-reduce words of the resident kernels, zeroed by k_track_init
   int first_delay = -1;               // integer all-reduce: pause before the first read of the totals (DMS_AR_FIRST_DELAY; -1 = by grid size)
-  // the later the last arrival can be after one's own, the longer the pause pays: ~0.4 us on the 150 / 200-block levels, next to
-  // nothing on 38 blocks (measured: level 2 is best at 0 - 8 units, levels 1 and 0 at 12 - 20)
   bool long_levels_resident = true;   // levels of more than kArRing iterations (inter-map calls: 50) as resident launches too (DMS_TRACK_LONG_RESIDENT=0: launch-per-phase, as before round 6)
   int first_delay_lvl[4] = {-1, -1, -1, -1};  // per stage (levels 0, 1, 2, SO3): DMS_AR_FIRST_DELAY_BY_LEVEL="l0,l1,l2,so3" (-1 = the rule)
-  int first_delay_for(int nb, int stage = -1) const {
-    if (stage >= 0 && stage < 4 && first_delay_lvl[stage] >= 0) return first_delay_lvl[stage];
-    return first_delay >= 0 ? first_delay : (nb >= 96 ? 24 : 8);
-  }
+  int first_delay_for(int nb, int stage) const { return dms::first_delay_for(nb, stage >= 0 && stage < 4 ? first_delay_lvl[stage] : -1, first_delay); }
   int depth_bias = 0;                 // production rule (key "depth_exp_bias"): the frame step's depth cut-off raises the static exponents (canon::depth_exp_bias)
   int exp_bias = 0;                   // test hook (dms_odometry_debug_set "exp_bias"): added to the static exponents of a call's first reductions (negative: they do not fit and are repeated)
   long long* prof = nullptr;          // [16] phase clocks of the persistent kernels (profiling only)
@@ -831,9 +825,8 @@ __global__ __launch_bounds__(kBlock) void k_gn_solve(TrackState* st, GnArgs a, c
 //     grid — a uniform decision again — on a word set from the launch's pool.
 // Hand-off rules follow cdna_hip_programming.md G16 (relaxed polling, agent-scope words, bounded spins, words zeroed
 // by an earlier kernel on the stream); scripts/bench_gridbarrier.hip is the protocol's stand-alone visibility test.
-constexpr int kPB = 512;                 // 8 waves: 256 VGPRs per thread, half the reduction tail of 16 waves
+// (kPB threads per block, at most kMaxPersistBlocks blocks: resident_rule.hpp)
 constexpr int kPWaves = kPB / kWave;
-constexpr int kMaxPersistBlocks = 256;   // one block per CU
 constexpr unsigned kSpinLimit = 1u << 22;
 
 struct LevelArgs {
@@ -863,7 +856,6 @@ constexpr int kArPairStride = 16;                   // apart from the lines the 
 constexpr int kArWords = kArPairBase + kArShards * kArPairStride;  // 5 KB per reduction
 constexpr int kArSlotCnt = 0, kArSlotSig = 1;
 constexpr int kArPool = 6;                          // extra word sets per resident launch for repeated reductions
-constexpr int kArRing = 10;                          // word sets a stage cycles through, one per iteration (re-armed in flight when a level runs more iterations)
 constexpr int kArSetsPerKernel = kArRing + kArPool;
 constexpr int kArSets = 4 * kArSetsPerKernel;       // SO3 + three levels
 
@@ -1757,13 +1749,11 @@ int dms_odometry_create(dms_odometry** out, int width, int height, float cx, flo
       if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 0;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_gn_level<true, true, 3, false>, kPB, 0) != hipSuccess) per_cu = 0;
       (void)hipGetLastError();
-      // (the API is known to answer one block per CU too many near register-file edges, MI355X_MICROARCH.md: a 512-thread block
-      // at > 128 registers can only ever be alone on its CU, so one per CU is what is relied on)
-      o->max_resident_blocks = per_cu >= 1 ? (cus < kMaxPersistBlocks ? cus : kMaxPersistBlocks) : 0;
+      o->max_resident_blocks = device_bound(cus, per_cu);
       if (o->max_resident_blocks <= 0) o->resident = false;
     }
     e = getenv("DMS_PERSIST_MAX_BLOCKS");
-    if (e && atoi(e) > 0 && atoi(e) < o->max_resident_blocks) o->max_resident_blocks = atoi(e);
+    o->max_resident_blocks = lowered_bound(o->max_resident_blocks, e ? atoi(e) : 0);
     e = getenv("DMS_AR_FIRST_DELAY");  // units of 64 cycles before the first read of the totals; default: by grid size
     if (e && atoi(e) >= 0 && atoi(e) <= 1000) o->first_delay = atoi(e);
     e = getenv("DMS_TRACK_LONG_RESIDENT");
@@ -2034,63 +2024,16 @@ namespace dms {
 // ---- persistent level kernels: launch shape and cross-stream serialisation ----
 // dms_odometry::resident = false (DMS_TRACK_MODE=launches at creation) selects the three-launches-per-iteration path.
 
-// pixels per thread (1 - 5) and grid of k_gn_level for an n-pixel level; 0 blocks = not eligible
-static void persistent_shape(int n, int target, int max_blocks, int& P, int& nb, int reserve = 56) {
-  // 1 or 2 pixels per thread if that keeps the grid at <= `target` blocks (cheap barriers win on the small levels; 96 while
-  // the cross-block sums went through per-block records and a gather, 160 since the integer all-reduce: level 1 of
-  // 640x480 on 150 blocks with one pixel per thread instead of 75 with two, +1 % frame rate);
-  // otherwise 3 pixels per thread on up to 256 blocks (the full-resolution
-  // level is bound by its per-CU arithmetic: measured 221 us at 200 blocks vs 230 us at 150), else 4
-  auto blocks = [&](int p) { return (n + kPB * p - 1) / (kPB * p); };
-  const int cap = max_blocks < kMaxPersistBlocks ? max_blocks : kMaxPersistBlocks;  // every block must be resident at once
-  const int small = target < cap ? target : cap;
-  // ... and among 3 / 4 / 5 the fewest that leaves `reserve` compute units to whatever overlaps the tracker (the frame step's
-  // prep stream holds whole units for the length of its depth filter: 1241x376 on 228 blocks beside 97 filter blocks started
-  // incomplete; 5 pixels per thread = 183 blocks leave 73), else the fewest that fits at all
-  if (blocks(1) <= small)
-    P = 1;
-  else if (blocks(2) <= small)
-    P = 2;
-  else {
-    P = 0;
-    for (int p = 3; p <= 5 && !P; ++p)
-      if (blocks(p) <= cap - reserve) P = p;
-    for (int p = 3; p <= 5 && !P; ++p)
-      if (blocks(p) <= cap) P = p;
-    if (!P) P = 5;
-  }
-  nb = (n + kPB * P - 1) / (kPB * P);
-  if (nb > cap || n >= (1 << 19)) nb = 0;  // does not fit the device (or the 19-bit count of the pair word): launch-per-phase
-}
-
-// Blocks of a persistent kernel spin on each other, so two of them must never share the device
-// half-resident.  Every persistent section of this process is therefore chained on one event per
-// device: stream-ordered, free for a single stream, and it serialises trackers of different
-// cameras / streams against each other.
-// A process that runs all its trackers on one stream (one camera per process, the usual case) needs no event at all:
-// the stream orders the sections, and the unconditional record after every tracker call cost ~6 us of idle stream per
-// frame in the rocprof trace.  The first time a section arrives on a stream other than the previous one, the device is
-// synchronised once (the previous stream may have been destroyed since: its handle must not be touched any more) and the
-// device switches to the chained form: from then on every section ends with an event recorded on its own — live —
-// stream, and a section on another stream waits for it.
+// The shapes, the bounds and the cross-stream chain's rules are resident_rule.hpp's.  Here: the chain's state per device, and the
+// section that carries out its decisions - the mutex, the device query, the event and the three HIP calls.
 struct PersistChain {
+  static constexpr int kDevices = 64;
   std::mutex mu;
-  hipEvent_t ev[64] = {};
-  hipStream_t last[64] = {};
-  bool used[64] = {};
-  bool chained[64] = {};   // several streams have run sections on this device: events from here on
-  bool ev_valid[64] = {};
-  // (round 6) ... until one stream has had the device's sections to itself for kQuietAfter calls in a row (a front end that changed
-  // streams between phases; bench.py's loops): the events stop, and the next section from another stream pays one device
-  // synchronisation as the very first change of stream did.  Two cameras that alternate never get there and keep their events.
-  int run[64] = {};
-  bool quiet[64] = {};
+  hipEvent_t ev[kDevices] = {};
+  ChainState state[kDevices];
 };
-static constexpr int kQuietAfter = 8;
 static PersistChain g_persist;
-// DMS_PERSIST_UNCHAINED=1: the caller guarantees that the resident grids of all handles that may track at the same time fit the
-// device TOGETHER (DMS_PERSIST_MAX_BLOCKS of each, summed, <= compute units; a handle whose bound exceeds half the device stays chained) — then every grid completes whatever the
-// interleaving and no section has to wait for another camera's.  Read once.
+// DMS_PERSIST_UNCHAINED=1 (chain_exempt; DMS_PERSIST_MAX_BLOCKS of each handle, summed, <= compute units).  Read once.
 static bool unchained() {
   static const bool u = [] {
     const char* e = getenv("DMS_PERSIST_UNCHAINED");
@@ -2100,55 +2043,55 @@ static bool unchained() {
 }
 struct PersistSection {
   hipStream_t s;
-  int dev = 0;
-  bool active = false;
   int budget;  // largest resident grid of the handle this section belongs to
   bool handle_unchained;
+  bool active = false;          // the mutex is held
+  ChainState* chain = nullptr;  // (active without one: a device outside the table - synchronised, no state kept)
+  hipEvent_t* ev = nullptr;
+  bool carried = false;         // the section's last launch was given the chain's event
   PersistSection(hipStream_t s_, int budget_, bool handle_unchained_ = false) : s(s_), budget(budget_), handle_unchained(handle_unchained_) {}
   void begin() {
     if (active) return;
-    if (unchained() || handle_unchained) {  // honoured only for handles that hold at most half the device: two of them always fit together
+    if (unchained() || handle_unchained) {
       static const int cus = [] {
         int dev = 0, n = 0;
         (void)hipGetDevice(&dev);
         return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess ? n : 0;
       }();
-      if (budget > 0 && 2 * budget <= cus) return;
+      if (chain_exempt(unchained(), handle_unchained, budget, cus)) return;
     }
     g_persist.mu.lock();
-    (void)hipGetDevice(&dev);
-    dev &= 63;
-    if (g_persist.used[dev] && g_persist.last[dev] != s) {
-      if (!g_persist.chained[dev] || g_persist.quiet[dev]) {
-        (void)hipDeviceSynchronize();
-        g_persist.chained[dev] = true;
-      } else if (g_persist.ev_valid[dev]) {
-        (void)hipStreamWaitEvent(s, g_persist.ev[dev], 0);
-      }
-      g_persist.run[dev] = 0;
-      g_persist.quiet[dev] = false;
-    } else if (g_persist.chained[dev] && !g_persist.quiet[dev] && ++g_persist.run[dev] >= kQuietAfter) {
-      g_persist.quiet[dev] = true;
-      g_persist.ev_valid[dev] = false;
-    }
-    g_persist.last[dev] = s;
-    g_persist.used[dev] = true;
     active = true;
-  }
-  // The section's LAST resident launch can carry the chain's event itself (its completion signal) instead of a marker recorded behind
-  // it: between two kernels of one stream a marker is a gap of about 7 us (rocprofv3, the session loop: level 0 -> index map).  Returns
-  // null when no event is owed (one stream only so far) - then nothing changes.
-  bool closed = false;
-  hipEvent_t closing_event() {
-    if (!active || !g_persist.chained[dev] || g_persist.quiet[dev] || !ext_events()) return nullptr;
-    if (!g_persist.ev[dev] && hipEventCreateWithFlags(&g_persist.ev[dev], hipEventDisableTiming) != hipSuccess) {
-      (void)hipGetLastError();
-      g_persist.ev[dev] = nullptr;
-      return nullptr;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= PersistChain::kDevices) {
+      (void)hipDeviceSynchronize();
+      return;
     }
-    closed = true;
-    g_persist.ev_valid[dev] = true;
-    return g_persist.ev[dev];
+    chain = &g_persist.state[dev];
+    ev = &g_persist.ev[dev];
+    switch (chain->enter(s)) {
+      case ChainState::device_sync: (void)hipDeviceSynchronize(); break;
+      case ChainState::wait_event: (void)hipStreamWaitEvent(s, *ev, 0); break;
+      case ChainState::proceed: break;
+    }
+  }
+  // the device's event, created at its first use
+  bool have_event() {
+    if (!*ev && hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) {
+      (void)hipGetLastError();
+      *ev = nullptr;
+    }
+    return *ev != nullptr;
+  }
+  // The event the section's LAST resident launch is to carry as its completion signal (ChainState::owes_event); null when none is
+  // owed (one stream only so far) - then nothing changes.
+  hipEvent_t closing_event() {
+    if (!chain) return nullptr;
+    chain->ext_events = ext_events();
+    if (!chain->owes_event() || !have_event()) return nullptr;
+    carried = true;
+    return *ev;
   }
   static bool ext_events() {
     static const bool on = [] {
@@ -2159,14 +2102,10 @@ struct PersistSection {
   }
   ~PersistSection() {
     if (!active) return;
-    if (closed) {
-      g_persist.mu.unlock();
-      return;
-    }
-    if (g_persist.chained[dev] && !g_persist.quiet[dev]) {
-      if (!g_persist.ev[dev]) (void)hipEventCreateWithFlags(&g_persist.ev[dev], hipEventDisableTiming);
-      g_persist.ev_valid[dev] = g_persist.ev[dev] && hipEventRecord(g_persist.ev[dev], s) == hipSuccess;
-      if (!g_persist.ev_valid[dev]) (void)hipGetLastError();
+    if (chain && chain->leave(carried)) {
+      const bool ok = have_event() && hipEventRecord(*ev, s) == hipSuccess;
+      if (!ok) (void)hipGetLastError();
+      chain->recorded(ok);
     }
     g_persist.mu.unlock();
   }
@@ -2201,15 +2140,13 @@ static void launch_gn_level(int P, int nb, hipStream_t s, TrackState* st, const 
     launch_gn_level_f<ICP, RGB, false>(P, nb, s, st, a, L, done);
 }
 
-static inline int budget_of(const dms_odometry* o) {
-  return (o->budget_cap > 0 && o->budget_cap < o->max_resident_blocks) ? o->budget_cap : o->max_resident_blocks;
-}
+static inline int budget_of(const dms_odometry* o) { return handle_bound(o->budget_cap, o->max_resident_blocks); }
+static inline int level_pixels(const dms_odometry* o, int l) { return o->vmaps_curr[l].cols * (o->vmaps_curr[l].rows / 3); }
 
 // grid of the resident SO3 kernel for this handle; 0 = the SO3 stage runs launch-per-phase
 static int so3_resident_blocks(const dms_odometry* o) {
   const Buf& li = o->lastNextImage[2];
-  const int nbp = (li.rows * li.cols + kPB - 1) / kPB;
-  return (o->resident && nbp <= kMaxPersistBlocks && nbp <= budget_of(o)) ? nbp : 0;
+  return so3_blocks(o->resident, li.rows * li.cols, budget_of(o));
 }
 
 int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot, const float* prior_pose16_dev, int rgbOnly,
@@ -2380,12 +2317,9 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
     return L;
   };
   auto level_shape = [&](int l, int& pP, int& pnb) {
-    pP = 1;
-    pnb = 0;
-    if (o->resident && (iterations[l] <= kArRing || o->long_levels_resident))  // (more iterations than ring sets: the ring is re-armed in flight)
-      persistent_shape(o->vmaps_curr[l].cols * (o->vmaps_curr[l].rows / 3), o->persist_target, budget_of(o), pP, pnb);
-    o->last_shape_P[l] = pP;
-    o->last_shape_nb[l] = pnb;
+    const LevelShape sh = call_level_shape(budget_of(o), o->persist_target, iterations[l], o->resident, o->long_levels_resident, level_pixels(o, l));
+    o->last_shape_P[l] = pP = sh.P;
+    o->last_shape_nb[l] = pnb = sh.blocks;
   };
 
   if (so3) {
@@ -2651,9 +2585,8 @@ int odometry_free_cus(const dms_odometry* o) {
   (void)hipGetDevice(&dev);
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return -1;
   int widest = so3_resident_blocks(o);
-  for (int l = 0; l < DMS_NUM_PYRS; ++l) {
-    int P = 1, nb = 0;
-    persistent_shape(o->vmaps_curr[l].cols * (o->vmaps_curr[l].rows / 3), o->persist_target, o->max_resident_blocks, P, nb);
+  for (int l = 0; l < DMS_NUM_PYRS; ++l) {  // the device's bound and no iteration count: see call_level_shape
+    const int nb = call_level_shape(o->max_resident_blocks, o->persist_target, 0, true, o->long_levels_resident, level_pixels(o, l)).blocks;
     widest = nb > widest ? nb : widest;
   }
   return cus - widest;

@@ -773,8 +773,8 @@ def test_pose_does_not_depend_on_the_grid_size(dms, gputest_pair, monkeypatch):
     rgba1, rgba2 = helpers.rgba(gputest_pair["rgb1"]), helpers.rgba(gputest_pair["rgb2"])
     outs = []
     for blocks, mode, cap in ((160, None, 0), (40, None, 0), (96, None, 0), (160, "launches", 0), (160, None, 120), (160, None, 20)):
-        # cap: a device with that many compute units — 120: level 0 takes four pixels per thread; 20: no level fits, every level
-        # runs launch-per-phase while the SO3 stage (38 blocks) does too
+        # cap: a device with that many compute units — 120: level 0 takes five pixels per thread on 120 blocks; 20: only level 2 fits
+        # (two pixels per thread on 19 blocks), levels 0 and 1 and the SO3 stage (38 blocks) run launch-per-phase
         monkeypatch.setenv("DMS_PERSIST_BLOCKS", str(blocks))
         if cap:
             monkeypatch.setenv("DMS_PERSIST_MAX_BLOCKS", str(cap))
@@ -802,6 +802,8 @@ def test_pose_does_not_depend_on_the_grid_size(dms, gputest_pair, monkeypatch):
     monkeypatch.delenv("DMS_PERSIST_MAX_BLOCKS", raising=False)
     monkeypatch.setenv("DMS_PERSIST_BLOCKS", "160")
     g = dms.RGBDOdometry(640, 480, K[2], K[3], K[0], K[1])
+    # (pixels per thread, blocks) of levels 0 / 1 / 2 under each cap; None: not resident (tests/test_resident_rule_cpu.py has the rule)
+    shapes = {120: ((5, 120), (2, 75), (1, 38)), 0: ((3, 200), (1, 150), (1, 38)), 20: (None, None, (2, 19))}
     for cap, unchained in ((120, 1), (0, 0), (20, 0)):
         assert lib.dms_odometry_set_resident_budget(g.h, cap, unchained) == 0
         g.initICPModel(verts, norms, 20.0, np.eye(4, dtype=np.float32))
@@ -811,6 +813,10 @@ def test_pose_does_not_depend_on_the_grid_size(dms, gputest_pair, monkeypatch):
         g.initFirstRGB(rgba1)
         t, R, r = g.getIncrementalTransformation(np.zeros(3, np.float32), np.eye(3, dtype=np.float32), **CONFIGS["C3_full"])
         outs.append(t.tobytes() + R.tobytes() + np.array(r.lastA).tobytes() + np.array(r.lastb).tobytes())
+        for level, want in enumerate(shapes[cap]):
+            P, nb, resident = g.levelShape(level)
+            assert (resident, nb > 0) == (want is not None, want is not None), (cap, level, P, nb, resident)
+            assert want is None or (P, nb) == want, (cap, level, P, nb)
     g.close()
     assert all(o == outs[0] for o in outs[1:])
 
