@@ -1,6 +1,7 @@
 """ctypes mirror of include/dmslam_io.h: eflcm.Frame messages, LCM event logs and .klg logs
 (the reference's LcmHandler / RawLcmLogReader / RawLogReader); and of include/dmslam_io_device.h: the same readers
-with both destinations in device memory, JPEG colour decoded on the GPU."""
+with both destinations in device memory, JPEG colour decoded on the GPU; and of the writers (include/dmslam_io.h second half,
+include/dmslam_io_write.h): JPEG colour encoded on the host or on the GPU, zlib depth, .klg and LCM-log writers."""
 import ctypes as C
 
 import numpy as np
@@ -233,3 +234,179 @@ class JpegDevice:
             self.close()
         except Exception:
             pass
+
+
+# ---- recording (include/dmslam_io.h writers' half, include/dmslam_io_write.h): JPEG colour encoded on the host or on the GPU, zlib
+# depth, .klg and LCM-log writers ----
+
+JPEG_444, JPEG_420 = 0, 2
+DMS_ERR_CAPACITY = -4
+JPEG_ENC_DEFAULT_ENTROPY_ON_HOST = 0  # DMS_JPEG_ENC_DEFAULT_ENTROPY_ON_HOST
+lib.dms_jpeg_encode_bound.argtypes = [C.c_int, C.c_int, C.c_int]
+lib.dms_jpeg_encode_bound.restype = C.c_size_t
+lib.dms_jpeg_encode.argtypes = [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]
+lib.dms_deflate_bound.argtypes = [C.c_size_t]
+lib.dms_deflate_bound.restype = C.c_size_t
+lib.dms_deflate.argtypes = [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t)]
+lib.dms_frame_pack.argtypes = [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int32, C.c_char_p, C.POINTER(FrameMsg),
+                               C.POINTER(_P)]
+lib.dms_frame_pack_free.argtypes = [_P]
+lib.dms_frame_pack_free.restype = None
+lib.dms_klg_writer_open.argtypes = [C.POINTER(_P), C.c_char_p]
+lib.dms_klg_writer_append.argtypes = [_P, C.c_int64, _P, C.c_int32, _P, C.c_int32]
+lib.dms_klg_writer_close.argtypes = [_P]
+lib.dms_lcmlog_writer_open.argtypes = [C.POINTER(_P), C.c_char_p]
+lib.dms_lcmlog_writer_append.argtypes = [_P, C.c_int64, C.c_char_p, _P, C.c_size_t]
+lib.dms_lcmlog_writer_close.argtypes = [_P]
+lib.dms_jpeg_enc_create.argtypes = [C.POINTER(_P), C.c_int, C.c_int, C.c_int]
+lib.dms_jpeg_enc_destroy.argtypes = [_P]
+lib.dms_jpeg_enc_set_image_size.argtypes = [_P, C.c_int, C.c_int]
+lib.dms_jpeg_enc_set_entropy_on_host.argtypes = [_P, C.c_int]
+lib.dms_jpeg_enc_encode.argtypes = [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]
+lib.dms_jpeg_enc_result.argtypes = [_P, C.POINTER(_P), C.POINTER(C.c_size_t)]
+lib.dms_jpeg_enc_result_at.argtypes = [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t)]
+lib.dms_frame_pack_device.argtypes = [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int32, C.c_char_p, C.POINTER(FrameMsg), _P]
+lib.dms_klg_writer_append_device.argtypes = [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, _P]
+lib.dms_lcmlog_writer_append_frame_device.argtypes = [_P, _P, C.c_char_p, _P, _P, C.c_int64, C.c_int32, C.c_char_p, C.c_int, C.c_int, _P]
+
+
+def jpeg_encode_bound(width, height, subsampling=JPEG_420):
+    """the most bytes dms_jpeg_encode can write for this size (dms_jpeg_encode_bound); 0 for bad arguments"""
+    return int(lib.dms_jpeg_encode_bound(width, height, subsampling))
+
+
+def jpeg_encode(rgb, quality=90, subsampling=JPEG_420, flipColors=False, cap=None):
+    """(H, W, 3) u8 -> the bytes of a baseline JPEG file, libjpeg's (dms_jpeg_encode).  `cap`: the size of the output buffer, for
+    tests of the refusal; the default is jpeg_encode_bound."""
+    rgb = np.ascontiguousarray(rgb, np.uint8)
+    h, w = rgb.shape[:2]
+    n = jpeg_encode_bound(w, h, subsampling) if cap is None else cap
+    buf = C.create_string_buffer(max(n, 1))
+    written = C.c_size_t(0)
+    rc = lib.dms_jpeg_encode(rgb.ctypes.data_as(_P), w, h, int(quality), int(subsampling), int(bool(flipColors)), buf, n, C.byref(written))
+    jpeg_encode.last_written = written.value
+    check(rc, "dms_jpeg_encode")
+    return buf.raw[:written.value]
+
+
+def deflate(data):
+    """zlib's compress2 at its default level, resolved at run time (dms_deflate)"""
+    data = bytes(data)
+    n = lib.dms_deflate_bound(len(data))
+    buf = C.create_string_buffer(n)
+    written = C.c_size_t(0)
+    check(lib.dms_deflate(data, len(data), buf, n, C.byref(written)), "dms_deflate")
+    return buf.raw[:written.value]
+
+
+def _frame_of(m):
+    return Frame(C.string_at(m.depth, m.depthSize), C.string_at(m.image, m.imageSize), m.timestamp, m.frameNumber,
+                 m.senderName.decode("utf-8", "replace"), m.trackOnly, m.compressed, m.last)
+
+
+def frame_pack(depth, rgb, compressed=True, quality=90, flipColors=False, timestamp=0, frameNumber=0, senderName=""):
+    """depth (H, W) u16 + rgb (H, W, 3) u8 -> a Frame (dms_frame_pack): raw, or zlib depth + JPEG colour as the reference's
+    converters write them."""
+    depth = np.ascontiguousarray(depth, np.uint16)
+    rgb = np.ascontiguousarray(rgb, np.uint8)
+    h, w = depth.shape
+    m, owned = FrameMsg(), _P()
+    check(lib.dms_frame_pack(depth.ctypes.data_as(_P), rgb.ctypes.data_as(_P), w, h, int(bool(compressed)), int(quality), int(bool(flipColors)),
+                             int(timestamp), int(frameNumber), senderName.encode("utf-8"), C.byref(m), C.byref(owned)), "dms_frame_pack")
+    try:
+        return _frame_of(m)
+    finally:
+        lib.dms_frame_pack_free(owned)
+
+
+class JpegDeviceEncoder:
+    """dms_jpeg_enc: RGB8 in device memory -> JPEG bytes in a pinned slot; `rgb_dev` / `depth_dev` arguments are device pointers
+    (int), `stream` a stream handle (int) or None."""
+
+    def __init__(self, max_width, max_height, slots=3):
+        self.h = _P()
+        self.width, self.height, self.slots = max_width, max_height, slots
+        check(lib.dms_jpeg_enc_create(C.byref(self.h), max_width, max_height, slots), "dms_jpeg_enc_create")
+
+    def set_image_size(self, width, height):
+        """frames of another size, no larger than the one the object was created for"""
+        check(lib.dms_jpeg_enc_set_image_size(self.h, width, height), "dms_jpeg_enc_set_image_size")
+        self.width, self.height = width, height
+
+    def set_entropy_on_host(self, on):
+        """the mode pack() and the writers' device forms encode in (default: the measured winner)"""
+        check(lib.dms_jpeg_enc_set_entropy_on_host(self.h, int(bool(on))), "dms_jpeg_enc_set_entropy_on_host")
+
+    def encode(self, rgb_dev, quality=90, subsampling=JPEG_420, flipColors=False, entropy_on_host=False, stream=None):
+        """enqueues the encode on `stream` and returns; refusals raise at once, with nothing enqueued"""
+        check(lib.dms_jpeg_enc_encode(self.h, _P(rgb_dev), int(quality), int(subsampling), int(bool(flipColors)), int(bool(entropy_on_host)),
+                                      _P(stream)), "dms_jpeg_enc_encode")
+
+    def result(self, back=0):
+        """waits for the last encode (or the one `back` before it) and returns its bytes"""
+        data, n = _P(), C.c_size_t(0)
+        check(lib.dms_jpeg_enc_result_at(self.h, int(back), C.byref(data), C.byref(n)), "dms_jpeg_enc_result_at")
+        return C.string_at(data, n.value)
+
+    def pack(self, depth_dev, rgb_dev, compressed=True, quality=90, timestamp=0, frameNumber=0, senderName="", stream=None):
+        """one frame from device memory -> a Frame (dms_frame_pack_device)"""
+        m = FrameMsg()
+        check(lib.dms_frame_pack_device(self.h, _P(depth_dev), _P(rgb_dev), self.width, self.height, int(bool(compressed)), int(quality), int(timestamp),
+                                        int(frameNumber), senderName.encode("utf-8"), C.byref(m), _P(stream)), "dms_frame_pack_device")
+        return _frame_of(m)
+
+    def close(self):
+        if self.h:
+            lib.dms_jpeg_enc_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KlgWriter:
+    """.klg writer (dms_klg_writer): append(timestamp, depth bytes, image bytes) takes the payloads as they go into the file."""
+
+    def __init__(self, path):
+        self.h = _P()
+        check(lib.dms_klg_writer_open(C.byref(self.h), path.encode()), "dms_klg_writer_open")
+
+    def append(self, timestamp, depth_bytes, image_bytes=b""):
+        d, i = bytes(depth_bytes), bytes(image_bytes)
+        check(lib.dms_klg_writer_append(self.h, int(timestamp), d, len(d), i, len(i)), "dms_klg_writer_append")
+
+    def append_device(self, je, depth_dev, rgb_dev, timestamp, compressed=True, quality=90, stream=None):
+        """one frame of je's size from device memory (dms_klg_writer_append_device)"""
+        check(lib.dms_klg_writer_append_device(self.h, je.h, _P(depth_dev), _P(rgb_dev), int(timestamp), int(bool(compressed)), int(quality), _P(stream)),
+              "dms_klg_writer_append_device")
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, None
+            check(lib.dms_klg_writer_close(h), "dms_klg_writer_close")
+
+
+class LcmLogWriter:
+    """LCM event log writer (dms_lcmlog_writer)."""
+
+    def __init__(self, path):
+        self.h = _P()
+        check(lib.dms_lcmlog_writer_open(C.byref(self.h), path.encode()), "dms_lcmlog_writer_open")
+
+    def append(self, timestamp_us, channel, data):
+        data = bytes(data)
+        check(lib.dms_lcmlog_writer_append(self.h, int(timestamp_us), channel.encode(), data, len(data)), "dms_lcmlog_writer_append")
+
+    def append_frame_device(self, je, channel, depth_dev, rgb_dev, timestamp, frameNumber=0, senderName="", compressed=True, quality=90, stream=None):
+        """one frame of je's size from device memory as an eflcm.Frame event (dms_lcmlog_writer_append_frame_device)"""
+        check(lib.dms_lcmlog_writer_append_frame_device(self.h, je.h, channel.encode(), _P(depth_dev), _P(rgb_dev), int(timestamp), int(frameNumber),
+                                                        senderName.encode("utf-8"), int(bool(compressed)), int(quality), _P(stream)),
+              "dms_lcmlog_writer_append_frame_device")
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, None
+            check(lib.dms_lcmlog_writer_close(h), "dms_lcmlog_writer_close")

@@ -25,6 +25,9 @@ extern "C" {
 #define DMS_ERR_UNSUPPORTED (-7) /* e.g. a progressive JPEG, or zlib not loadable */
 #endif
 #define DMS_ERR_FORMAT (-8)      /* malformed message / log */
+#ifndef DMS_ERR_CAPACITY
+#define DMS_ERR_CAPACITY (-4)    /* an output buffer is too small (dmslam.h) */
+#endif
 #define DMS_EOF 1                /* readers: no more frames (not an error) */
 
 /* eflcm::Frame with `depth` / `image` as views into the encoded message (decode) or caller
@@ -73,6 +76,47 @@ int dms_klg_num_frames(dms_klg* h);
 int dms_klg_next(dms_klg* h, unsigned short* depth_out, unsigned char* rgb_out, int64_t* timestamp);
 int dms_klg_rewind(dms_klg* h);
 int dms_klg_close(dms_klg* h);
+
+/* ---- recording: the writers' side of the formats above (csrc/record.hip; the device forms are in dmslam_io_write.h) ----
+ *
+ * RGB8 (libjpeg's R, G, B order; R and B exchanged on the way in where flipColors) -> a baseline JPEG file, SOI to EOI, the
+ * bytes libjpeg's C encoder writes with its default parameters (csrc/jpeg_enc.hpp: fixed-point colour conversion, h2v2 box
+ * filter, slow integer forward DCT, jpeg_set_quality(quality, force_baseline) tables, the standard Huffman tables, JFIF 1.01
+ * header; sequential, 8 bit, three components, no restart markers, no optimised tables).  What the reference's converters
+ * write with cvEncodeImage(".jpg", quality 90) (logs/rgbd/KlgToLcm.cpp:26-40).
+ * quality 1..100; subsampling DMS_JPEG_420 (libjpeg's and OpenCV's default) or DMS_JPEG_444; width, height 1..65535.
+ * cap below dms_jpeg_encode_bound: DMS_ERR_CAPACITY (-4) and *written receives that bound. */
+#define DMS_JPEG_444 0
+#define DMS_JPEG_420 2
+size_t dms_jpeg_encode_bound(int width, int height, int subsampling); /* the header + every block at its longest, stuffed; 0 = bad arguments */
+int dms_jpeg_encode(const unsigned char* rgb_host, int width, int height, int quality, int subsampling, int flipColors,
+                    void* out, size_t cap, size_t* written);
+
+/* zlib's compress2 at its default level, as the reference's converters deflate depth (KlgToLcm.cpp:111-145); libz.so.1 is
+ * resolved at run time: DMS_ERR_UNSUPPORTED where it is not loadable.  cap below dms_deflate_bound: DMS_ERR_CAPACITY. */
+size_t dms_deflate_bound(size_t len);
+int dms_deflate(const void* data, size_t len, void* out, size_t cap, size_t* written);
+
+/* One frame -> an eflcm::Frame ready for dms_eflcm_frame_encode.  compressed = 0: m->depth / m->image are the caller's
+ * buffers (nothing is copied; flipColors must be 0).  compressed = 1: zlib depth and JPEG colour (quality, DMS_JPEG_420) in
+ * a buffer the message owns; release it with dms_frame_pack_free (a no-op for raw messages and zeroed structs). */
+int dms_frame_pack(const unsigned short* depth_host, const unsigned char* rgb_host, int width, int height, int compressed, int quality,
+                   int flipColors, int64_t timestamp, int32_t frameNumber, const char* senderName, dms_frame_msg* m, void** owned);
+void dms_frame_pack_free(void* owned);
+
+/* .klg writer: the count is written as 0 at open and rewritten at close.  The payloads are the frame's bytes as they go into
+ * the file (raw or compressed; imageSize 0 = no image). */
+typedef struct dms_klg_writer dms_klg_writer;
+int dms_klg_writer_open(dms_klg_writer** out, const char* path);
+int dms_klg_writer_append(dms_klg_writer* w, int64_t timestamp, const void* depth_bytes, int32_t depthSize, const void* image_bytes,
+                          int32_t imageSize);
+int dms_klg_writer_close(dms_klg_writer* w);
+
+/* LCM event log writer: events numbered from 0 in the order of the appends */
+typedef struct dms_lcmlog_writer dms_lcmlog_writer;
+int dms_lcmlog_writer_open(dms_lcmlog_writer** out, const char* path);
+int dms_lcmlog_writer_append(dms_lcmlog_writer* w, int64_t timestamp_us, const char* channel, const void* data, size_t len);
+int dms_lcmlog_writer_close(dms_lcmlog_writer* w);
 
 #ifdef __cplusplus
 }
