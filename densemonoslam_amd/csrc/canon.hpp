@@ -239,15 +239,17 @@ __device__ __forceinline__ double tree_rest(const double (&o1)[SL / 2]) {
 // a pixel without correspondence; found[p] counts.  Returns, in lane l, the wave total of value slot_of_lane(l) as a
 // multiple of that value's grid (zero for slots >= NV).  s_bias: the block's bias table (write_bias).  The accumulators are
 // formed two at a time and handed to the tree's first step at once (32 live registers instead of 64).
-template <int N, int P>
+// Q <= P: only the first Q pixels of the arrays take part (the tracker's compacted photometric slots).
+template <int N, int P, int Q = P>
 __device__ __forceinline__ double wave_sum(const float (&rows)[P][N + 1], const bool (&found)[P], const double (*s_bias)[32]) {
+  static_assert(Q >= 1 && Q <= P, "wave_sum: 1 <= Q <= P");
   using Lay = Layout<N>;
   constexpr int SL = Lay::SLOTS;
   const int lane = threadIdx.x & 63;
   const double* bias = s_bias[lane >> 5];
-  double r64[P][N + 1];
+  double r64[Q][N + 1];
 #pragma unroll
-  for (int p = 0; p < P; ++p)
+  for (int p = 0; p < Q; ++p)
 #pragma unroll
     for (int c = 0; c <= N; ++c) r64[p][c] = (double)rows[p][c];
   // Groups of four values: the biases of the next group are fetched from LDS (into what will be its accumulators) before the
@@ -266,7 +268,7 @@ __device__ __forceinline__ double wave_sum(const float (&rows)[P][N + 1], const 
 #pragma unroll
     for (int h = 0; h < G; ++h) nxt[h] = ((g + 1) * G + h < Lay::NV) ? bias[(g + 1) * G + h] : 0.0;
 #pragma unroll
-    for (int p = 0; p < P; ++p) {
+    for (int p = 0; p < Q; ++p) {
 #pragma unroll
       for (int h = 0; h < G; ++h) {
         const int k = g * G + h;

@@ -29,18 +29,22 @@ __device__ __forceinline__ unsigned block_sum_u32(unsigned v) {
   return t;
 }
 
-// exclusive rank of `flag` among the 256 threads of the block (thread order), and the total
+// exclusive rank of `flag` among the NW * 64 threads of the block (thread order; 256 threads unless told otherwise), and the total.
+// Two block barriers: every thread of the block calls it, from uniform control flow.
+template <int NW = 4>
 __device__ __forceinline__ unsigned block_exclusive_rank(bool flag, unsigned& total) {
-  __shared__ unsigned s_w[4];
+  __shared__ unsigned s_w[NW];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const unsigned long long mask = __ballot(flag);
   const unsigned below = __popcll(mask & ((1ull << lane) - 1ull));
   __syncthreads();  // protect s_w from the previous call's readers
   if (lane == 0) s_w[wid] = __popcll(mask);
   __syncthreads();
-  unsigned base = 0;
+  unsigned base = 0, tot = 0;
   for (int w = 0; w < wid; ++w) base += s_w[w];
-  total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+#pragma unroll
+  for (int w = 0; w < NW; ++w) tot += s_w[w];
+  total = tot;
   return base + below;
 }
 

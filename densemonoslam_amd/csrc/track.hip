@@ -26,6 +26,7 @@
 #include <math.h>
 
 #include <map>
+#include <type_traits>
 #include <string>
 #include <vector>
 
@@ -41,6 +42,8 @@
 #include "model_bodies.hpp"
 #include "surfel.hpp"
 #include "resident_rule.hpp"
+#include "track_ownership.hpp"
+#include "scan.hpp"
 #include <mutex>
 
 namespace dms {
@@ -137,6 +140,10 @@ struct dms_odometry {
   int* part_cnt = nullptr;     // [2][1024]
   unsigned* tickets = nullptr; // [4] arrival counters of the last-block-solves hand-off (zero between launches)
   unsigned long long* ar = nullptr;   // [kArSets][kArWords] all-reduce words of the resident kernels, zeroed by k_track_init
+  unsigned* list_len = nullptr;       // [DMS_NUM_PYRS][kMaxPersistBlocks] entries of each block's photometric list in the last resident launch of a level
+  bool track_interleave = true;       // DMS_TRACK_INTERLEAVE / debug key "track_interleave": a block's pixel segments spread over the image (track_ownership.hpp)
+  bool rgb_compact = true;            // DMS_RGB_COMPACT / debug key "rgb_compact": the photometric half runs over the block's gated pixels only
+  bool last_rgb[DMS_NUM_PYRS] = {false, false, false};  // the last call ran the photometric term on this level's resident kernel
   int first_delay = -1;               // integer all-reduce: pause before the first read of the totals (DMS_AR_FIRST_DELAY; -1 = by grid size)
   bool long_levels_resident = true;   // levels of more than kArRing iterations (inter-map calls: 50) as resident launches too (DMS_TRACK_LONG_RESIDENT=0: launch-per-phase, as before round 6)
   int first_delay_lvl[4] = {-1, -1, -1, -1};  // per stage (levels 0, 1, 2, SO3): DMS_AR_FIRST_DELAY_BY_LEVEL="l0,l1,l2,so3" (-1 = the rule)
@@ -844,6 +851,9 @@ struct LevelArgs {
   float* pose16_out;
   FrameState* frame;
   float weightMultiplier;
+  int interleave;       // pixel ownership: segments of a block spread over the image (track_ownership.hpp; DMS_TRACK_INTERLEAVE)
+  int compact;          // photometric list: the block's gated pixels only (DMS_RGB_COMPACT; 0: every owned pixel, the work of the uncompacted kernel)
+  unsigned* list_len;   // [blocks] entries of each block's photometric list, written once per launch (dms_odometry_get_rgb_compaction)
 };
 
 // ---- grid-wide integer all-reduce in memory-side atomics ------------------------------------------------------
@@ -930,6 +940,29 @@ __device__ __forceinline__ constexpr unsigned so3_diag_mask() {
   return m;
 }
 
+static_assert(kOwnWaves == kPWaves && kOwnLanes == kWave, "track_ownership.hpp restates the block's shape");
+
+// f(std::integral_constant<int, q>()) for q = 1 .. P, nothing for q = 0: a piece of the photometric half over the first q of a
+// wave's compacted slots, as straight-line code per case (guards around every slot instead cost the level kernels 14 registers per
+// slot, and scratch from three pixels per thread on).  q is the same in every lane of the wave.
+template <int P, typename F>
+__device__ __forceinline__ void for_slots(int q, F&& f) {
+  static_assert(P >= 1 && P <= 5, "for_slots: one case per slot");
+  if (q == 1) f(std::integral_constant<int, 1>());
+  if constexpr (P >= 2) {
+    if (q == 2) f(std::integral_constant<int, 2>());
+  }
+  if constexpr (P >= 3) {
+    if (q == 3) f(std::integral_constant<int, 3>());
+  }
+  if constexpr (P >= 4) {
+    if (q == 4) f(std::integral_constant<int, 4>());
+  }
+  if constexpr (P >= 5) {
+    if (q == 5) f(std::integral_constant<int, 5>());
+  }
+}
+
 // EXIT: leave the level after an iteration without any correspondence (below).  A template parameter because the
 // mere presence of that exit costs the frame-to-model tracker ~1 % (codegen of the resident loop); the frame step
 // instantiates it for the model-to-model pass only.
@@ -938,6 +971,7 @@ __device__ __forceinline__ constexpr unsigned so3_diag_mask() {
 template <bool ICP, bool RGB, int P, bool EXIT>
 __device__ __forceinline__ void gn_level_body(TrackState* st, const GnArgs& a, const LevelArgs& L, const int nb) {
   constexpr bool kFma = kTrackerFma;
+  constexpr bool kSkip = P <= 3;  // waves skip the photometric slots they hold no entry for (pass 1, below)
   __shared__ sc::GnLocal s;
   __shared__ int s_redi[kPWaves][2];
   __shared__ double s_red[kPWaves][32];
@@ -953,6 +987,7 @@ __device__ __forceinline__ void gn_level_body(TrackState* st, const GnArgs& a, c
   __shared__ int s_viol;
   __shared__ int s_retries;
   __shared__ sc::KPre s_k[2];
+  __shared__ unsigned s_list[RGB ? P * kPB : 1];  // the block's photometric list: pixel indices (below)
   const int tid = threadIdx.x;
   int eb_icp = 0, eb_rgb = 0;  // wave 0: bound exponents of the values this lane adds (lanes 0-28) / polls (lane k: ICP k, lane 32 + k: photometric k)
   // optional phase clock (block 0, thread 0): wall_clock64 ticks (10 ns) summed per phase into L.prof
@@ -1003,36 +1038,91 @@ __device__ __forceinline__ void gn_level_body(TrackState* st, const GnArgs& a, c
   }
 
   // ---- pose-independent per-pixel data, once per level ----
+  // Ownership (track_ownership.hpp): slot p of this thread owns one pixel; the ICP half runs over the P owned slots.
   const int N = a.cols * a.rows;
-  int idx[P], px[P], py[P];
+  bool live[P], keep[P];
+  unsigned own[P];
   IcpOwn io[P];
-  RgbOwn ro[P];
-  short gx[P], gy[P];
 #pragma unroll
   for (int p = 0; p < P; ++p) {
-    idx[p] = (blockIdx.x * P + p) * kPB + tid;
+    const int idx = owned_index(L.interleave != 0, (int)blockIdx.x, nb, P, p, tid);
     // threads past the end shadow a pixel of the image and are masked.  (Not pixel 0 for all of them: where whole blocks lie past a
     // small level's image, tens of thousands of lanes loading one address queue up on its cache line - measured on a grid larger
     // than the level: +5 us at the start of level 2 and +0.7 us per pass.)
-    const int ic = idx[p] < N ? idx[p] : idx[p] % N;
-    py[p] = ic / a.cols;
-    px[p] = ic - py[p] * a.cols;
-    if (ICP) io[p] = icp_load_own(a.maps, px[p], py[p], a.rows);
-    if (RGB) {
-      ro[p] = rgb_load_own_gated(a.rgb, px[p], py[p]);
-      gx[p] = trow(a.rgb.dIdx, a.rgb.dI_pitch, py[p])[px[p]];
-      gy[p] = trow(a.rgb.dIdy, a.rgb.dI_pitch, py[p])[px[p]];
-    }
+    const int ic = owned_shadow(idx, N);
+    const int y = ic / a.cols, x = ic - y * a.cols;
+    live[p] = idx < N;
+    own[p] = (unsigned)ic;
+    if (ICP) io[p] = icp_load_own(a.maps, x, y, a.rows);
+    // the photometric list takes the pixel if it can ever give a correspondence: the gate image and a depth that is not NaN
+    // (RgbOwn::gate).  Without compaction (L.compact = 0) every owned pixel of the image goes in.
+    keep[p] = false;
+    if (RGB) keep[p] = live[p] && (!L.compact || rgb_load_own_gated(a.rgb, x, y).gate);
   }
   const float invFx = 1.0f / a.fx, invFy = 1.0f / a.fy;  // as projectToPointCloud passes them
   __syncthreads();
-  if (s_done) return;  // level already ended (uniform: every block read the same flag)
+  if (s_done) {  // level already ended (uniform: every block read the same flag)
+    if (RGB && tid == 0 && L.list_len) L.list_len[blockIdx.x] = 0u;
+    return;
+  }
   if (tid < 64) {
     canon::write_bias<6>(s_E[tid >> 5], s_bias[tid >> 5], tid & 31);
     eb_icp = canon::value_exp<6>(s_E[0], tid & 31);
     eb_rgb = canon::value_exp<6>(s_E[1], tid & 31);
   }
   __syncthreads();
+
+  // ---- the block's photometric list, once per level ----
+  // The block ranks the pixels it keeps (P rounds, thread order inside a round) and writes their indices into LDS; thread t then
+  // takes entries t, t + kPB, ... as its COMPACTED slots and loads their own data.  n entries fill Q = ceil(n / kPB) slots of the
+  // block; wave w holds entries in its first Qw slots (Qw = Q or Q - 1: the list is dense, so the last slot ends in some wave).
+  // Every pixel is still evaluated exactly once by the same functions on the same inputs, and the sums are exact integer sums
+  // (canon.hpp): which lane takes which pixel cannot change a bit of the totals.
+  // UNIFORMITY RULE: n, Q and Qw depend on the image.  Every __syncthreads(), every arrival at an all-reduce and every poll of
+  // one therefore stays outside anything that depends on them; only per-pixel arithmetic and the wave tree are skipped (for_slots:
+  // the slots q < Qw).  A block with an empty list (Q = 0) arrives at both all-reduces like any other, with zeros.
+  // A compacted slot holds its pixel's own data in four registers: x | y << 16, gx | gy << 16, the depth, intensity | gate << 8
+  // (image sides are below 2^15; unpacked where used - the level kernels sit at the 256-register limit).
+  unsigned pxy[P], gxy[P], gi[P];
+  float d1[P];
+  auto own_of = [&](int q) {
+    RgbOwn o;
+    o.gate = (gi[q] >> 8) != 0u;
+    o.d1 = d1[q];
+    o.i1 = (unsigned char)(gi[q] & 0xffu);
+    return o;
+  };
+  int Qw = 0;
+  if (RGB) {
+    unsigned n = 0;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      unsigned tot;
+      const unsigned r = block_exclusive_rank<kPWaves>(keep[p], tot);
+      if (keep[p]) s_list[n + r] = own[p];  // (n + r < P * kPB: at most kPB entries per round)
+      n += tot;
+    }
+    __syncthreads();
+    if (tid == 0 && L.list_len) L.list_len[blockIdx.x] = n;
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+      const unsigned e = (unsigned)(q * kPB + tid);
+      pxy[q] = gxy[q] = gi[q] = 0u;  // a lane without an entry: gate off, no correspondence, ever
+      d1[q] = 1.f;
+      if (e < n) {
+        const int i = (int)s_list[e];
+        const int y = i / a.cols, x = i - y * a.cols;
+        const RgbOwn o = rgb_load_own_gated(a.rgb, x, y);
+        const short gx = trow(a.rgb.dIdx, a.rgb.dI_pitch, y)[x], gy = trow(a.rgb.dIdy, a.rgb.dI_pitch, y)[x];
+        pxy[q] = (unsigned)x | ((unsigned)y << 16);
+        gxy[q] = (unsigned)(unsigned short)gx | ((unsigned)(unsigned short)gy << 16);
+        gi[q] = (unsigned)o.i1 | (o.gate ? 0x100u : 0u);
+        d1[q] = o.d1;
+      }
+    }
+    const unsigned first = (unsigned)(tid & ~(kWave - 1));  // this wave's first entry of slot 0
+    Qw = __builtin_amdgcn_readfirstlane(n > first ? (int)((n - first + kPB - 1) / kPB) : 0);
+  }
 
   bool ended = false;
   int pool_used = 0;  // word sets of the retry pool consumed so far (uniform)
@@ -1056,30 +1146,48 @@ __device__ __forceinline__ void gn_level_body(TrackState* st, const GnArgs& a, c
         ir[p] = icp_project<kFma>(ip, io[p]);
         im[p] = icp_load_model(a.maps, ir[p], a.rows);
       }
-      if (RGB) {
-        rr[p] = rgb_project<kFma>(rp, ro[p], px[p], py[p]);
-        rm[p] = rgb_load_model(a.rgb, rr[p]);
-      }
     }
+    // (the photometric half runs over this wave's Qw COMPACTED slots: entries of the block's list, all of them pixels of the image)
+    // The slots this wave does not hold are skipped where the registers allow it: up to three pixels per thread (kSkip; 254 of 256
+    // registers with three).  Every switch over the slot count costs the kernel 8 - 14 registers per slot, and with four or five
+    // pixels per thread it would run out of scratch memory (68 / 208 bytes per lane; the compiler's report for every instantiation is
+    // profiles/rgb_compaction_resources.txt).  There every lane runs all P slots through both passes - entries or not - as
+    // before the lists.
+    const int Qs = kSkip ? Qw : P;
+    if (RGB)
+      for_slots<P>(Qs, [&](auto qc) {
+#pragma unroll
+        for (int q = 0; q < decltype(qc)::value; ++q) {
+          rr[q] = rgb_project<kFma>(rp, own_of(q), (int)(pxy[q] & 0xffffu), (int)(pxy[q] >> 16));
+          rm[q] = rgb_load_model(a.rgb, rr[q]);
+        }
+      });
     float rows[P][7];
     bool found[P];
     int cnt = 0, sig = 0;
-    dms_dataterm c[P];
+    // a slot's correspondence, held across the wait for the count pair in two registers: model pixel x | y << 16 | valid << 31,
+    // and the intensity difference (the live pixel is the slot's own)
+    unsigned cz[P];
+    float cdiff[P];
+    if (RGB)
+      for_slots<P>(Qs, [&](auto qc) {
+#pragma unroll
+        for (int q = 0; q < decltype(qc)::value; ++q) {
+          int d2;
+          dms_dataterm c;
+          if (rgb_finish(rp, own_of(q), rr[q], rm[q], (int)(pxy[q] & 0xffffu), (int)(pxy[q] >> 16), c, d2)) {
+            cnt += 1;
+            sig += d2;
+          }
+          cz[q] = (unsigned)(unsigned short)c.zero_x | ((unsigned)(unsigned short)c.zero_y << 16) | (c.valid ? 0x80000000u : 0u);
+          cdiff[q] = c.diff;
+        }
+      });
 #pragma unroll
     for (int p = 0; p < P; ++p) {
-      const bool live = idx[p] < N;
-      if (RGB) {
-        int d2;
-        const bool ok = rgb_finish(rp, ro[p], rr[p], rm[p], px[p], py[p], c[p], d2) && live;
-        if (!live) c[p].valid = 0;
-        if (ok) {
-          cnt += 1;
-          sig += d2;
-        }
-      }
       if (ICP) {
         found[p] = icp_finish<kFma>(ip, io[p], ir[p], im[p], rows[p]);
-        if (!live) {
+        if (!live[p]) {
           found[p] = false;
 #pragma unroll
           for (int k = 0; k < 7; ++k) rows[p][k] = 0.f;
@@ -1125,17 +1233,19 @@ __device__ __forceinline__ void gn_level_body(TrackState* st, const GnArgs& a, c
         if (tid < kSE3) __hip_atomic_fetch_add(arw + tid, canon::pack_word(canon::to_units(p_icp, eb_icp)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
-    // what the photometric rows need that does not depend on sigma — the model pixel's cloud point, exactly as k_projectPoints
-    // builds it from lastDepth, and 1 / z — is taken while the count is in flight (the waves other than wave 0 only wait here)
+    // what the photometric rows need that does not depend on sigma - the model pixel's cloud point, exactly as k_projectPoints
+    // builds it from lastDepth, and 1 / z - is taken while the count is in flight (the waves other than wave 0 only wait here);
+    // with kSkip it is taken in pass 2 (held across the wait it costs the skipping kernels four registers per slot)
     f3 cpt[P];
     float cinvz[P];
-    if (RGB) {
+    auto cloud_point = [&](int q) {
+      const float z = rm[q].d0;
+      cpt[q] = mk3((((float)(short)(cz[q] & 0xffffu) - a.cx) * z) * invFx, (((float)(short)((cz[q] >> 16) & 0x7fffu) - a.cy) * z) * invFy, z);
+      cinvz[q] = rgb_row_invz(cpt[q]);
+    };
+    if (RGB && !kSkip) {
 #pragma unroll
-      for (int p = 0; p < P; ++p) {
-        const float z = rm[p].d0;
-        cpt[p] = mk3((((float)c[p].zero_x - a.cx) * z) * invFx, (((float)c[p].zero_y - a.cy) * z) * invFy, z);
-        cinvz[p] = rgb_row_invz(cpt[p]);
-      }
+      for (int q = 0; q < P; ++q) cloud_point(q);
     }
     if (RGB) {
       if (tid < 64) {
@@ -1169,19 +1279,34 @@ __device__ __forceinline__ void gn_level_body(TrackState* st, const GnArgs& a, c
       p_.fx = a.fx;
       p_.fy = a.fy;
       p_.sobelScale = a.sobelScale;
+      // this wave's photometric sums over its Qw compacted slots (wave-uniform; no barrier inside: the uniformity rule above).
+      // A wave that holds no entry skips rows and tree: a wave sum carries no bias (the two halves of the wave start from opposite
+      // biases), so the sums of nothing are zeros.
+      double r_rgb = 0.0;
+      for_slots<P>(Qs, [&](auto qc) {
+        constexpr int Q = decltype(qc)::value;
 #pragma unroll
-      for (int p = 0; p < P; ++p) {
-        RgbRowIn in;
-        in.pt = cpt[p];
-        in.gx = gx[p];
-        in.gy = gy[p];
-        rgb_row_finish<kFma>(p_, c[p], in, rows[p], cinvz[p], true);
-        found[p] = c[p].valid != 0;
-      }
+        for (int q = 0; q < Q; ++q) {
+          if (kSkip) cloud_point(q);
+          dms_dataterm c;  // (rgb_row_finish reads `valid` and `diff`)
+          c.zero_x = (short)(cz[q] & 0xffffu);
+          c.zero_y = (short)((cz[q] >> 16) & 0x7fffu);
+          c.one_x = (short)(pxy[q] & 0xffffu);
+          c.one_y = (short)(pxy[q] >> 16);
+          c.diff = cdiff[q];
+          c.valid = (cz[q] >> 31) != 0u;
+          RgbRowIn in;
+          in.pt = cpt[q];
+          in.gx = (short)(gxy[q] & 0xffffu);
+          in.gy = (short)(gxy[q] >> 16);
+          rgb_row_finish<kFma>(p_, c, in, rows[q], cinvz[q], true);
+          found[q] = c.valid != 0;
+        }
+        r_rgb = canon::wave_sum<6, P, Q>(rows, found, s_bias[1]);
+      });
       if (ICP) {
         // one fold for both reductions: lane k of wave 0 ends with the block's ICP total of value k, lane 32 + k with the
         // photometric one — exactly the slot (tid) their words have in the shard
-        const double r_rgb = canon::wave_sum<6, P>(rows, found, s_bias[1]);
         const int lane = tid & 63, wid = tid >> 6;
         // (s_red2 was last read before the barrier that follows the totals: no barrier needed in front of these stores)
         if ((lane & 1) == 0) {
@@ -1197,7 +1322,7 @@ __device__ __forceinline__ void gn_level_body(TrackState* st, const GnArgs& a, c
           __hip_atomic_fetch_add(arw + tid, canon::pack_word(canon::to_units(t, tid < 32 ? eb_icp : eb_rgb)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       } else {
-      const double p_rgb = canon::block_sum<6, P, kPWaves>(rows, found, s_bias[1], s_red);
+      const double p_rgb = canon::block_fold<6, kPWaves>(r_rgb, s_red);
       if (tid < kSE3) __hip_atomic_fetch_add(arw + 32 + tid, canon::pack_word(canon::to_units(p_rgb, eb_rgb)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
@@ -1640,6 +1765,7 @@ void layout(dms_odometry* o, Carver& c) {
   o->tickets = (unsigned*)c.take(64);
   o->ar = (unsigned long long*)c.take((size_t)kArSets * kArWords * 8);
   o->prof = (long long*)c.take((3 * 16 + 256 * 8) * 8);
+  o->list_len = (unsigned*)c.take((size_t)DMS_NUM_PYRS * kMaxPersistBlocks * 4);
   o->state = (TrackState*)c.take(sizeof(TrackState));
 }
 
@@ -1758,6 +1884,10 @@ int dms_odometry_create(dms_odometry** out, int width, int height, float cx, flo
     if (e && atoi(e) >= 0 && atoi(e) <= 1000) o->first_delay = atoi(e);
     e = getenv("DMS_TRACK_LONG_RESIDENT");
     if (e) o->long_levels_resident = atoi(e) != 0;
+    e = getenv("DMS_TRACK_INTERLEAVE");  // A/B switches of the resident level kernels: same bits either way
+    if (e) o->track_interleave = atoi(e) != 0;
+    e = getenv("DMS_RGB_COMPACT");
+    if (e) o->rgb_compact = atoi(e) != 0;
     e = getenv("DMS_AR_FIRST_DELAY_BY_LEVEL");  // "l0,l1,l2,so3" in the same units (-1 keeps the rule for that stage): the per-level sweep
     if (e) {
       int v[4] = {-1, -1, -1, -1};
@@ -1782,7 +1912,38 @@ int dms_odometry_debug_set(dms_odometry* o, const char* key, int value) {
     o->depth_bias = value;
     return DMS_OK;
   }
+  if (strcmp(key, "track_interleave") == 0) {
+    o->track_interleave = value != 0;
+    return DMS_OK;
+  }
+  if (strcmp(key, "rgb_compact") == 0) {
+    o->rgb_compact = value != 0;
+    return DMS_OK;
+  }
   DMS_REQUIRE(false, "unknown key");
+}
+
+// Photometric lists of the last tracker call's resident kernel of `level`: the largest number of compacted slots any block ran
+// (0 .. pixels per thread) and the entries of all lists together.  Zeros where the level ran launch-per-phase or without the
+// photometric term.  Waits for the device.
+int dms_odometry_get_rgb_compaction(dms_odometry* o, int level, int* max_slots, int* entries) {
+  DMS_REQUIRE(o, "null argument");
+  DMS_REQUIRE(level >= 0 && level < DMS_NUM_PYRS, "bad level");
+  int q = 0, total = 0;
+  const int nb = o->last_rgb[level] ? o->last_shape_nb[level] : 0;
+  if (nb > 0) {
+    unsigned len[kMaxPersistBlocks];
+    DMS_HIP(hipDeviceSynchronize());
+    DMS_HIP(hipMemcpy(len, o->list_len + (size_t)level * kMaxPersistBlocks, (size_t)nb * 4, hipMemcpyDeviceToHost));
+    for (int b = 0; b < nb; ++b) {
+      const int slots = (int)((len[b] + kPB - 1) / kPB);
+      if (slots > q) q = slots;
+      total += (int)len[b];
+    }
+  }
+  if (max_slots) *max_slots = q;
+  if (entries) *entries = total;
+  return DMS_OK;
 }
 
 int dms_odometry_set_resident_budget(dms_odometry* o, int max_blocks, int unchained) {
@@ -2314,6 +2475,9 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
     L.pose16_out = frame ? const_cast<float*>(prior_pose16_dev) : nullptr;
     L.frame = frame;
     L.weightMultiplier = weightMultiplier;
+    L.interleave = o->track_interleave ? 1 : 0;
+    L.compact = o->rgb_compact ? 1 : 0;
+    L.list_len = o->list_len + (size_t)l * kMaxPersistBlocks;
     return L;
   };
   auto level_shape = [&](int l, int& pP, int& pnb) {
@@ -2354,6 +2518,7 @@ int odometry_track_enqueue(dms_odometry* o, const float* trans, const float* rot
     int pP = 1, pnb = 0;
     level_shape(l, pP, pnb);
     const bool persistent = pnb > 0;
+    o->last_rgb[l] = rgb && persistent && iterations[l] > 0;
     if (rgb && !persistent) {  // the persistent kernel rebuilds the cloud point from lastDepth itself
       dms_camera k = {o->fx, o->fy, o->cx, o->cy};
       dms_image2d d = o->lastDepth[l].img(), c = o->pointClouds[l].img();

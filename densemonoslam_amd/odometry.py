@@ -276,6 +276,19 @@ class RGBDOdometry:
         """test hook: bias of the static exponents of a call's first reductions (csrc/canon.hpp)"""
         check(lib.dms_odometry_debug_set(self.h, b"exp_bias", int(bias)), "dms_odometry_debug_set")
 
+    def setOwnership(self, interleave=-1, compact=-1):
+        """A/B switches of the resident level kernels (same bits either way); -1 keeps the current setting"""
+        if interleave >= 0:
+            check(lib.dms_odometry_debug_set(self.h, b"track_interleave", int(interleave)), "dms_odometry_debug_set")
+        if compact >= 0:
+            check(lib.dms_odometry_debug_set(self.h, b"rgb_compact", int(compact)), "dms_odometry_debug_set")
+
+    def rgbCompaction(self, level):
+        """(largest number of compacted slots of any block, entries of all blocks' photometric lists) of `level` in the last call"""
+        q, n = C.c_int(0), C.c_int(0)
+        check(lib.dms_odometry_get_rgb_compaction(self.h, int(level), C.byref(q), C.byref(n)), "dms_odometry_get_rgb_compaction")
+        return q.value, n.value
+
     def canonRetries(self):
         """reductions of the last fetched call that were repeated on a coarser grid"""
         n = C.c_int(0)

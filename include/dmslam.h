@@ -279,8 +279,15 @@ int dms_odometry_get_level_shape(dms_odometry* o, int level, int* pixels_per_thr
  * grid barrier (DMS_ERR_TIMEOUT from dms_odometry_fetch_result; the frame step keeps the prior pose and fuses nothing). */
 int dms_odometry_inject_timeout(dms_odometry* o, int calls);
 /* Test hooks by name.  "exp_bias": added to the static column exponents of a call's first reductions (csrc/canon.hpp); a
- * negative value makes their diagonal totals overflow the grid, so those reductions are repeated on a coarser one. */
+ * negative value makes their diagonal totals overflow the grid, so those reductions are repeated on a coarser one.
+ * "track_interleave" / "rgb_compact" (0 / 1, both on by default; DMS_TRACK_INTERLEAVE / DMS_RGB_COMPACT at creation): how the
+ * resident level kernels assign pixels to blocks, and whether their photometric half runs over the gated pixels only.  A/B
+ * switches: the results are the same bits either way. */
 int dms_odometry_debug_set(dms_odometry* o, const char* key, int value);
+/* Photometric lists of `level` in the last tracker call enqueued on this handle (csrc/track.hip, resident level kernels): the largest
+ * number of compacted slots that any block ran per thread (0 .. pixels per thread) and the entries of all blocks' lists together.
+ * Zeros for a level that ran launch-per-phase or without the photometric term.  Waits for the device; either output may be null. */
+int dms_odometry_get_rgb_compaction(dms_odometry* o, int level, int* max_slots, int* entries);
 /* Number of reductions of the last fetched call that were repeated on a coarser grid (csrc/canon.hpp). */
 int dms_odometry_canon_retries(dms_odometry* o, int* retries);
 /* The tracker's scalar section (csrc/gn_scalar.hpp: 6x6 solve, exp map, pose update, projection parameters; SO3 update)
