@@ -16,6 +16,8 @@
 //            copies            length word and the first bytes of the stream -> pinned slot (the rest, if a stream is longer than
 //                              that, when the result is asked for)
 //     entropy on the host:     coefficients -> pinned slot; dms_jpeg_enc_result runs enc_entropy_sequential
+//   depth of a frame: copied into the slot and deflated by the host while the colour kernels run, or (set_depth_on_device) deflated
+//   by the kernels of csrc/deflate_dev.hip on the same stream, their stream landing in the slot's deflate area
 // No kernel waits on another workgroup: the stages are separate launches.
 #include <string.h>
 
@@ -23,6 +25,7 @@
 
 #include "../../include/dmslam_io_write.h"
 #include "common.hpp"
+#include "deflate_dev.hpp"
 #include "jpeg_enc.hpp"
 #include "scan.hpp"
 
@@ -224,7 +227,7 @@ struct Slot {
   bool in_flight = false, used = false, finished = false;
   int on_host = 0, hdr = 0;
   Geometry g;
-  size_t len = 0, eager = 0;
+  size_t len = 0, eager = 0, z_eager = 0;
 };
 
 inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
@@ -241,7 +244,8 @@ void size_caps(int width, int height, size_t* blocks, size_t* plane_bytes) {
 }  // namespace
 
 struct dms_jpeg_enc {
-  int width = 0, height = 0, writers_on_host = DMS_JPEG_ENC_DEFAULT_ENTROPY_ON_HOST;
+  int width = 0, height = 0, writers_on_host = DMS_JPEG_ENC_DEFAULT_ENTROPY_ON_HOST, depth_on_device = DMS_RECORD_DEFAULT_DEPTH_ON_DEVICE;
+  dms_deflate_dev* dd = nullptr;  // made by the first frame whose depth is deflated on the device; slot k of its ring serves slot k here
   size_t max_px = 0, max_blocks = 0, max_planes = 0;
   size_t off_coef = 0, off_depth = 0, off_z = 0, z_cap = 0, slot_bytes = 0, out_bytes = 0;
   std::vector<Slot> slots;
@@ -268,6 +272,7 @@ int free_all(dms_jpeg_enc* je) {
   }
   if (je->last_done) (void)hipEventDestroy(je->last_done);
   if (je->depth_done) (void)hipEventDestroy(je->depth_done);
+  if (je->dd) (void)dms_deflate_dev_destroy(je->dd);
   void* dev[] = {je->d_planes, je->d_coef, je->d_bits, je->d_words, je->d_chunks, je->d_tables};
   for (void* p : dev)
     if (p) (void)hipFree(p);
@@ -417,7 +422,8 @@ int dms_jpeg_enc_create(dms_jpeg_enc** out, int max_width, int max_height, int s
   je->off_depth = je->off_coef + align16(blocks * 64 * sizeof(short));
   je->off_z = je->off_depth + align16(je->max_px * 2);
   je->z_cap = dms_deflate_bound(je->max_px * 2);
-  je->slot_bytes = je->off_z + align16(je->z_cap);
+  const size_t z_dev = dms::dfl::dev_slot_bytes(je->max_px * 2);  // [length word | the device's stream], whose bound is the larger
+  je->slot_bytes = je->off_z + align16(je->z_cap > z_dev ? je->z_cap : z_dev);
   je->out_bytes = kLenBytes + align16(stream_bytes * 2 + 2 + 16);
   je->slots.resize((size_t)slots);
   auto fail = [&](hipError_t e, const char* what) {
@@ -467,6 +473,12 @@ int dms_jpeg_enc_set_entropy_on_host(dms_jpeg_enc* je, int on) {
   return DMS_OK;
 }
 
+int dms_jpeg_enc_set_depth_on_device(dms_jpeg_enc* je, int on) {
+  DMS_REQUIRE(je, "null argument");
+  je->depth_on_device = on ? 1 : 0;
+  return DMS_OK;
+}
+
 int dms_jpeg_enc_encode(dms_jpeg_enc* je, const void* rgb_dev, int quality, int subsampling, int flipColors, int entropy_on_host, dms_stream stream) {
   DMS_REQUIRE(je, "null argument");
   if (!encode_args_ok("dms_jpeg_enc_encode", rgb_dev, quality, subsampling)) return DMS_ERR_INVALID_ARG;
@@ -496,12 +508,21 @@ int dms_frame_pack_device(dms_jpeg_enc* je, const unsigned short* depth_dev, con
   if (compressed && !encode_args_ok("dms_frame_pack_device", rgb_dev, quality, DMS_JPEG_420)) return DMS_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
   const size_t px = (size_t)width * height;
+  const bool z_dev = compressed && je->depth_on_device;
+  if (z_dev && !je->dd) {
+    const int rc = dms_deflate_dev_create(&je->dd, je->max_px * 2, (int)je->slots.size());
+    if (rc) return rc;
+  }
   int index;
   int rc = acquire(je, st, &index);
   if (rc) return rc;
   Slot& s = je->slots[(size_t)index];
   unsigned char* depth = s.pinned + je->off_depth;
   auto work = [&]() -> int {
+    if (z_dev) {
+      const int rc = dms::dfl::dev_enqueue(je->dd, index, depth_dev, px * 2, st, s.pinned + je->off_z, &s.z_eager);
+      return rc ? rc : enqueue(je, index, rgb_dev, quality, DMS_JPEG_420, 0, je->writers_on_host, st);
+    }
     DMS_HIP(hipMemcpyAsync(depth, depth_dev, px * 2, hipMemcpyDeviceToHost, st));
     if (!compressed) {
       DMS_HIP(hipMemcpyAsync(s.pinned + kLenBytes, rgb_dev, px * 3, hipMemcpyDeviceToHost, st));
@@ -520,7 +541,16 @@ int dms_frame_pack_device(dms_jpeg_enc* je, const unsigned short* depth_dev, con
   if (senderName) strncpy(m->senderName, senderName, sizeof(m->senderName) - 1);
   const unsigned char* image = nullptr;
   size_t image_len = 0;
-  if (compressed) {
+  if (z_dev) {
+    rc = finish(je, index, &image, &image_len);
+    if (rc) return rc;
+    const unsigned char* z = nullptr;
+    size_t zn = 0;
+    rc = dms::dfl::dev_finish(je->dd, index, s.pinned + je->off_z, s.z_eager, &z, &zn);
+    if (rc) return rc;
+    m->depth = z;
+    m->depthSize = (int32_t)zn;
+  } else if (compressed) {
     // the depth is in the slot before the colour kernels have run: deflate it meanwhile
     DMS_HIP(hipEventSynchronize(je->depth_done));
     size_t zn = 0;

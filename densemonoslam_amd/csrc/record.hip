@@ -11,6 +11,7 @@
 
 #include "../../include/dmslam_io.h"
 #include "common.hpp"
+#include "deflate.hpp"
 #include "jpeg_enc.hpp"
 
 namespace {
@@ -106,6 +107,21 @@ int dms_deflate(const void* data, size_t len, void* out, size_t cap, size_t* wri
     return DMS_ERR_FORMAT;
   }
   *written = (size_t)n;
+  return DMS_OK;
+}
+
+size_t dms_deflate_blocks_block_size(void) { return dms::dfl::kBlock; }
+size_t dms_deflate_blocks_bound(size_t len) { return dms::dfl::stream_bound(len); }
+
+int dms_deflate_blocks(const void* data, size_t len, void* out, size_t cap, size_t* written) {
+  DMS_REQUIRE(data && out && written, "null argument");
+  DMS_REQUIRE(len >= 1 && len <= ((size_t)1 << 31), "len outside 1 .. 2^31");
+  if (cap < dms::dfl::stream_bound(len)) {
+    *written = dms::dfl::stream_bound(len);
+    dms::set_error("dms_deflate_blocks: buffer of %zu bytes, %zu needed", cap, *written);
+    return DMS_ERR_CAPACITY;
+  }
+  *written = dms::dfl::encode((const unsigned char*)data, len, (unsigned char*)out);
   return DMS_OK;
 }
 

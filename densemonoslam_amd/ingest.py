@@ -242,12 +242,24 @@ class JpegDevice:
 JPEG_444, JPEG_420 = 0, 2
 DMS_ERR_CAPACITY = -4
 JPEG_ENC_DEFAULT_ENTROPY_ON_HOST = 0  # DMS_JPEG_ENC_DEFAULT_ENTROPY_ON_HOST
+RECORD_DEFAULT_DEPTH_ON_DEVICE = 0  # DMS_RECORD_DEFAULT_DEPTH_ON_DEVICE
 lib.dms_jpeg_encode_bound.argtypes = [C.c_int, C.c_int, C.c_int]
 lib.dms_jpeg_encode_bound.restype = C.c_size_t
 lib.dms_jpeg_encode.argtypes = [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]
 lib.dms_deflate_bound.argtypes = [C.c_size_t]
 lib.dms_deflate_bound.restype = C.c_size_t
 lib.dms_deflate.argtypes = [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t)]
+lib.dms_deflate_blocks_block_size.argtypes = []
+lib.dms_deflate_blocks_block_size.restype = C.c_size_t
+lib.dms_deflate_blocks_bound.argtypes = [C.c_size_t]
+lib.dms_deflate_blocks_bound.restype = C.c_size_t
+lib.dms_deflate_blocks.argtypes = [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t)]
+lib.dms_deflate_dev_create.argtypes = [C.POINTER(_P), C.c_size_t, C.c_int]
+lib.dms_deflate_dev_destroy.argtypes = [_P]
+lib.dms_deflate_dev_encode.argtypes = [_P, _P, C.c_size_t, _P]
+lib.dms_deflate_dev_result.argtypes = [_P, C.POINTER(_P), C.POINTER(C.c_size_t)]
+lib.dms_deflate_dev_result_at.argtypes = [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t)]
+lib.dms_jpeg_enc_set_depth_on_device.argtypes = [_P, C.c_int]
 lib.dms_frame_pack.argtypes = [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int32, C.c_char_p, C.POINTER(FrameMsg),
                                C.POINTER(_P)]
 lib.dms_frame_pack_free.argtypes = [_P]
@@ -299,6 +311,60 @@ def deflate(data):
     return buf.raw[:written.value]
 
 
+def deflate_blocks_block_size():
+    """input bytes per deflate block of deflate_blocks (dms_deflate_blocks_block_size)"""
+    return int(lib.dms_deflate_blocks_block_size())
+
+
+def deflate_blocks_bound(n):
+    """the most bytes deflate_blocks can write for n input bytes (dms_deflate_blocks_bound)"""
+    return int(lib.dms_deflate_blocks_bound(n))
+
+
+def deflate_blocks(data, cap=None):
+    """a zlib stream of blocks that can all be made at once, the bytes DeflateDeviceEncoder writes (dms_deflate_blocks); no libz
+    needed.  `cap`: the size of the output buffer, for tests of the refusal; the default is deflate_blocks_bound."""
+    data = bytes(data)
+    n = deflate_blocks_bound(len(data)) if cap is None else cap
+    buf = C.create_string_buffer(max(n, 1))
+    written = C.c_size_t(0)
+    rc = lib.dms_deflate_blocks(data, len(data), buf, n, C.byref(written))
+    deflate_blocks.last_written = written.value
+    check(rc, "dms_deflate_blocks")
+    return buf.raw[:written.value]
+
+
+class DeflateDeviceEncoder:
+    """dms_deflate_dev: bytes in device memory -> a zlib stream in a pinned slot; `data_dev` is a device pointer (int), `stream` a
+    stream handle (int) or None."""
+
+    def __init__(self, max_len, slots=3):
+        self.h = _P()
+        self.max_len, self.slots = max_len, slots
+        check(lib.dms_deflate_dev_create(C.byref(self.h), max_len, slots), "dms_deflate_dev_create")
+
+    def encode(self, data_dev, n, stream=None):
+        """enqueues the encode of n bytes on `stream` and returns; refusals raise at once, with nothing enqueued"""
+        check(lib.dms_deflate_dev_encode(self.h, _P(data_dev), int(n), _P(stream)), "dms_deflate_dev_encode")
+
+    def result(self, back=0):
+        """waits for the last encode (or the one `back` before it) and returns its stream"""
+        data, n = _P(), C.c_size_t(0)
+        check(lib.dms_deflate_dev_result_at(self.h, int(back), C.byref(data), C.byref(n)), "dms_deflate_dev_result_at")
+        return C.string_at(data, n.value)
+
+    def close(self):
+        if self.h:
+            lib.dms_deflate_dev_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _frame_of(m):
     return Frame(C.string_at(m.depth, m.depthSize), C.string_at(m.image, m.imageSize), m.timestamp, m.frameNumber,
                  m.senderName.decode("utf-8", "replace"), m.trackOnly, m.compressed, m.last)
@@ -336,6 +402,10 @@ class JpegDeviceEncoder:
     def set_entropy_on_host(self, on):
         """the mode pack() and the writers' device forms encode in (default: the measured winner)"""
         check(lib.dms_jpeg_enc_set_entropy_on_host(self.h, int(bool(on))), "dms_jpeg_enc_set_entropy_on_host")
+
+    def set_depth_on_device(self, on):
+        """pack() and the writers' device forms deflate the depth with kernels (deflate_blocks' bytes) instead of zlib on the host"""
+        check(lib.dms_jpeg_enc_set_depth_on_device(self.h, int(bool(on))), "dms_jpeg_enc_set_depth_on_device")
 
     def encode(self, rgb_dev, quality=90, subsampling=JPEG_420, flipColors=False, entropy_on_host=False, stream=None):
         """enqueues the encode on `stream` and returns; refusals raise at once, with nothing enqueued"""

@@ -97,6 +97,14 @@ int dms_jpeg_encode(const unsigned char* rgb_host, int width, int height, int qu
 size_t dms_deflate_bound(size_t len);
 int dms_deflate(const void* data, size_t len, void* out, size_t cap, size_t* written);
 
+/* A zlib stream of independent-to-make deflate blocks (csrc/deflate_core.hpp: a block per 4096 input bytes, each the cheapest of
+ * stored, fixed and dynamic Huffman, matches reaching back into earlier blocks' input), the bytes dms_deflate_dev (dmslam_io_write.h)
+ * writes on the device; no libz needed.  Any inflate reads it.  len == 0 or above 2^31: DMS_ERR_INVALID_ARG; cap below
+ * dms_deflate_blocks_bound(len): DMS_ERR_CAPACITY with the bound in *written. */
+size_t dms_deflate_blocks_block_size(void);
+size_t dms_deflate_blocks_bound(size_t len);
+int dms_deflate_blocks(const void* data, size_t len, void* out, size_t cap, size_t* written);
+
 /* One frame -> an eflcm::Frame ready for dms_eflcm_frame_encode.  compressed = 0: m->depth / m->image are the caller's
  * buffers (nothing is copied; flipColors must be 0).  compressed = 1: zlib depth and JPEG colour (quality, DMS_JPEG_420) in
  * a buffer the message owns; release it with dms_frame_pack_free (a no-op for raw messages and zeroed structs). */

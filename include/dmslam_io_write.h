@@ -7,8 +7,10 @@
  * the caller's stream.  The Huffman stage behind them runs either on the device (per block: bit length; one exclusive scan
  * places every block; all blocks write their bits at once; a second scan places the stuffed bytes) or on the host (the
  * coefficients are copied into a pinned slot and the sequential entropy stage of dms_jpeg_encode runs inside
- * dms_jpeg_enc_result) - selectable per encode.  Depth is copied into the pinned slot and deflated on the host (zlib resolved
- * at run time) while the colour kernels run.  Plain C99. */
+ * dms_jpeg_enc_result) - selectable per encode.  Depth is either copied into the pinned slot and deflated on the host (zlib
+ * resolved at run time) while the colour kernels run, or deflated by kernels too (csrc/deflate_dev.hip: per block of 4 KB a
+ * hash-table match search, a parse, length-limited Huffman codes and the cheapest of a stored, fixed or dynamic block; one
+ * exclusive scan places the blocks) - selectable per encoder object, also usable alone (dms_deflate_dev).  Plain C99. */
 #ifndef DMSLAM_IO_WRITE_H_
 #define DMSLAM_IO_WRITE_H_
 
@@ -20,6 +22,22 @@ extern "C" {
 #endif
 
 typedef struct dms_jpeg_enc dms_jpeg_enc;
+typedef struct dms_deflate_dev dms_deflate_dev;
+
+/* dms_deflate_blocks (dmslam_io.h) for a buffer in DEVICE memory: the same bytes, made by kernels on the caller's stream
+ * (csrc/deflate_dev.hip; both compile csrc/deflate_core.hpp).  The object owns the token and block-record buffers for inputs of
+ * at most max_len bytes (1 .. 2^31: offsets are 32-bit) and a ring of `slots` (1..16) pinned output slots, as dms_jpeg_enc has:
+ * an encode call returns once everything is enqueued and blocks only when its slot is still in flight.  Encodes of one object
+ * are ordered among themselves whatever streams they are enqueued on. */
+int dms_deflate_dev_create(dms_deflate_dev** out, size_t max_len, int slots);
+int dms_deflate_dev_destroy(dms_deflate_dev* dd);
+/* data_dev: len bytes in device memory -> a zlib stream in the next pinned slot.  data_dev may be written again once the work
+ * enqueued here is done.  Refusals (null pointer, len == 0, len > max_len: DMS_ERR_INVALID_ARG) enqueue nothing. */
+int dms_deflate_dev_encode(dms_deflate_dev* dd, const void* data_dev, size_t len, dms_stream stream);
+/* Waits for the last encode (dms_deflate_dev_result) or for the one `back` encodes before it (back < slots) and hands out the
+ * slot's stream.  It stays valid until the slot comes round again. */
+int dms_deflate_dev_result(dms_deflate_dev* dd, const unsigned char** data, size_t* len);
+int dms_deflate_dev_result_at(dms_deflate_dev* dd, int back, const unsigned char** data, size_t* len);
 
 /* The encoder object for frames of at most max_width x max_height.  It owns the device plane, coefficient and bit buffers
  * and a ring of `slots` (1..16) pinned output slots: an encode call returns once everything is enqueued and blocks only when
@@ -48,9 +66,17 @@ int dms_jpeg_enc_result_at(dms_jpeg_enc* je, int back, const unsigned char** dat
 #define DMS_JPEG_ENC_DEFAULT_ENTROPY_ON_HOST 0
 int dms_jpeg_enc_set_entropy_on_host(dms_jpeg_enc* je, int on);
 
+/* Where the frame and log functions below deflate the depth of a compressed frame.  0: the depth is copied into the pinned slot
+ * and deflated by dms_deflate (zlib, one host thread) while the colour kernels run.  1: the deflate kernels run on the same
+ * stream as the colour kernels and their stream lands in the same slot - no copy of the raw depth, no zlib call, and libz need
+ * not be loadable; the bytes are dms_deflate_blocks'.  The deflate buffers are created by the first frame that needs them. */
+#define DMS_RECORD_DEFAULT_DEPTH_ON_DEVICE 0
+int dms_jpeg_enc_set_depth_on_device(dms_jpeg_enc* je, int on);
+
 /* dms_frame_pack with both sources in device memory (depth_dev: width * height u16, rgb_dev: width * height * 3 bytes;
  * width x height must be the object's current size).  The depth goes into the pinned slot and, with compressed = 1, is
- * deflated on the host while the colour kernels run (quality, DMS_JPEG_420); compressed = 0 copies both raw.  Waits for the
+ * deflated on the host while the colour kernels run (quality, DMS_JPEG_420), or on the device
+ * (dms_jpeg_enc_set_depth_on_device); compressed = 0 copies both raw.  Waits for the
  * frame: on return m->depth and m->image point into the object's slot (valid until it comes round again) and m is ready for
  * dms_eflcm_frame_encode. */
 int dms_frame_pack_device(dms_jpeg_enc* je, const unsigned short* depth_dev, const unsigned char* rgb_dev, int width, int height, int compressed,
