@@ -326,6 +326,9 @@ struct dms_fusion {
   dms_pose_block* lazy_pose = nullptr;    // device: the pose block (pose + inverse) of the deferred frame, copied by its project launch
   bool lazy_observed = false;             // the final prediction's images have been asked for, pending record or not: eager (the dual pass) for the rest of the context's life
   long lazy_deferred = 0, lazy_materialised = 0, lazy_stale = 0;
+  // fused_clean_projection: cleans of the frame step whose scatter carried the next tracking prediction's project pass, and those
+  // that ran alone (dms_fusion_get_clean_project_stats)
+  long clean_project_fused = 0, clean_project_separate = 0;
   FrameState* state = nullptr;
   FrameState* h_state_dev = nullptr;  // device view of h_state
   FrameState* h_state = nullptr;  // pinned, four slots, frame % 4 (the host may read a slot once that frame's event has completed)
@@ -449,12 +452,38 @@ struct PredictOpts {
   bool have_prior = false;                    // tracking: the caller brought a pose
   const TrackInitArgs* track_init = nullptr;  // tracking, fused_model_prediction: the tracker call's set-up, to ride on that pass
   const PredictModelArgs* model = nullptr;    // tracking, fused_model_prediction: resolve into the tracker's model maps (track_frame)
+  bool projected_by_clean = false;            // final, fused_clean_projection: the frame's clean has filled zbuf2 and carried the rider
 };
+
+// what block 0 of a deferred final prediction's project launch carries: the frame's result block into its pinned slot, and the pose
+// the projection is rendered from into the lazy record
+static ProjectRider final_rider(const dms_fusion* f, void* state_mirror) {
+  return ProjectRider{(const unsigned*)f->state, (unsigned*)state_mirror, (int)(sizeof(FrameState) / 4),
+                      (const unsigned*)&f->state->cur, (unsigned*)f->lazy_pose, (int)(sizeof(dms_pose_block) / 4)};
+}
 
 // a tracking prediction resolves the projection the previous frame's final prediction rendered ahead (zbuf2) when that is still
 // what it would render itself; otherwise it projects into zbuf
 static bool tracking_resolves_shared(const dms_fusion* f, bool have_prior) {
   return f->pre_valid && !have_prior && f->pre_tick == f->tick && f->pre_version == f->model->version;
+}
+
+// fused fill-in for a prediction of this kind (the denseEnough decision of a fused pass is taken by the tracker's model pyramid
+// kernel: only when that kernel follows, i.e. with hybrid tracking)
+static bool fill_in_fused(const dms_fusion* f, bool dense_test) {
+  return f->p.fused_fill_in && f->p.width <= 2048 && f->p.height <= 2048 && (!dense_test || f->p.hybrid_tracking);
+}
+
+// a final prediction also projects for the next frame's tracking prediction
+// (a projection rendered ahead for this camera's next frame is stale by then when other cameras fuse into the same map: not rendered)
+static bool final_prediction_dual(const dms_fusion* f) { return f->p.share_projection && f->p.hybrid_tracking && f->model->sharers == 1; }
+
+// lazy_final_prediction: this frame's final prediction is not rendered, only the next frame's tracking prediction is projected
+// (the readers that make a frame eager: predict_body).  Asked by predict_body, and by process_frame_end before the clean, which
+// carries that projection when it can (fused_clean_projection).
+static bool final_prediction_deferred(const dms_fusion* f, bool one_call, const void* state_mirror) {
+  return final_prediction_dual(f) && one_call && fill_in_fused(f, false) && state_mirror && f->p.lazy_final_prediction && !f->lazy_observed &&
+         !f->armed_now.block && !f->p.nid_keyframing && !f->p.local_loop_closure && !f->p.hybrid_loops && !f->lost && !f->cur_bootstrap;
 }
 
 int predict_body(dms_fusion* f, hipStream_t s, Predict kind, const PredictOpts& o) {
@@ -471,7 +500,7 @@ int predict_body(dms_fusion* f, hipStream_t s, Predict kind, const PredictOpts& 
   // the denseEnough decision of a fused pass is taken by the tracker's model pyramid kernel from the counters filled here
   // (fill.hpp): only when that kernel follows, i.e. with hybrid tracking
   f->dense_by_counters = false;
-  if (f->p.fused_fill_in && f->p.width <= 2048 && f->p.height <= 2048 && (!dense_test || f->p.hybrid_tracking)) {
+  if (fill_in_fused(f, dense_test)) {
     fused = &fa;
     if (dense_test) {
       fa.dense_cnt = f->tickets;
@@ -512,7 +541,8 @@ int predict_body(dms_fusion* f, hipStream_t s, Predict kind, const PredictOpts& 
       const int next_tick = f->lost ? f->tick : f->tick + 1;  // (the tick advances at the end of the frame unless the camera is lost)
       const float second[3] = {0.7f, (float)next_tick, (float)next_tick};
       // (a projection rendered ahead for this camera's next frame is stale by then when other cameras fuse into the same map: not rendered)
-      const bool dual = kind == Predict::final && f->p.share_projection && f->p.hybrid_tracking && f->model->sharers == 1;
+      const bool dual = kind == Predict::final && final_prediction_dual(f);
+      DMS_REQUIRE(!o.projected_by_clean || (dual && !f->pre_valid), "the clean projects for a deferred final prediction only");
       if (dual && f->pre_valid && (rc = clear_zbuf(f->zbuf2, W * H, s))) return rc;  // (never consumed)
       // lazy_final_prediction: this prediction's images (f->pred, f->fill) are overwritten by the next frame's tracking prediction;
       // when nothing can read them before that, only that next prediction is projected.  Their readers, all in this file:
@@ -530,13 +560,13 @@ int predict_body(dms_fusion* f, hipStream_t s, Predict kind, const PredictOpts& 
       //     dms_fusion_apply_global_loop_* render the images anew (the record is dropped above);
       //   the result mirror (h_state): written by block 0 of the project launch below instead of the resolve's.
       // dms_fusion_arm_frame_block reads nothing: it makes the NEXT frame eager through armed_now.
-      const bool defer = dual && o.one_call && fused && o.state_mirror && f->p.lazy_final_prediction && !f->lazy_observed && !f->armed_now.block &&
-                         !f->p.nid_keyframing && !f->p.local_loop_closure && !f->p.hybrid_loops && !f->lost && !f->cur_bootstrap;
+      const bool defer = kind == Predict::final && final_prediction_deferred(f, o.one_call, o.state_mirror);
+      DMS_REQUIRE(!o.projected_by_clean || defer, "the clean projects for a deferred final prediction only");
       if (defer) {
-        const ProjectRider rider = {(const unsigned*)f->state, (unsigned*)o.state_mirror, (int)(sizeof(FrameState) / 4),
-                                    (const unsigned*)&f->state->cur, (unsigned*)f->lazy_pose, (int)(sizeof(dms_pose_block) / 4)};
-        if ((rc = splat_project_only(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, second[0], next_tick, f->p.timeIdx, next_tick,
-                                     f->p.timeDelta, 1, f->zbuf2, s, &rider)))
+        // (fused_clean_projection: the clean's scatter has projected, with this rider - process_frame_end; the record is kept here)
+        const ProjectRider rider = final_rider(f, o.state_mirror);
+        if (!o.projected_by_clean && (rc = splat_project_only(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, second[0], next_tick,
+                                                              f->p.timeIdx, next_tick, f->p.timeDelta, 1, f->zbuf2, s, &rider)))
           return rc;
         dms_fusion::LazyRecord& r = f->lazy;
         r.pending = true;
@@ -582,8 +612,11 @@ int predict_tracking(dms_fusion* f, hipStream_t s, bool have_prior, const TrackI
 }
 
 // finalPredict (ElasticFusion.cpp:586); its last kernel mirrors the result block into the pinned host slot
-int predict_final(dms_fusion* f, hipStream_t s, void* state_mirror, bool one_call) {
-  return predict_body(f, s, Predict::final, PredictOpts{f->p.confidence, state_mirror, one_call});
+// (projected_by_clean: bookkeeping only - the lazy record and the pre_* fields, for the map version the clean left)
+int predict_final(dms_fusion* f, hipStream_t s, void* state_mirror, bool one_call, bool projected_by_clean = false) {
+  PredictOpts o{f->p.confidence, state_mirror, one_call};
+  o.projected_by_clean = projected_by_clean;
+  return predict_body(f, s, Predict::final, o);
 }
 
 // The final prediction a deferred frame skipped (lazy_final_prediction), rendered now: the ordinary project + resolve + fill-in
@@ -704,6 +737,23 @@ int dms_model_clean(dms_model* m, const dms_pose_block* pose, int time, int time
   return model_clean(m, pose, time, timeIdx, im, depth_synth, cam, confThreshold, graph_host, graph_nodes, timeDelta, maxDepth, isFern, 0,
                      nullptr, (hipStream_t)s);
 }
+int dms_model_clean_project(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_indexmap_out* im, const dms_camera* cam,
+                            float confThreshold, int timeDelta, float maxDepth, float projConfThreshold, int projTime, int projMaxTime,
+                            int projTimeDelta, int active, unsigned long long* zbuf, int* projected, dms_stream s) {
+  DMS_REQUIRE(m && pose && cam && zbuf, "null argument");
+  CleanProjection cp = {maxDepth, projConfThreshold, projTime, projMaxTime, projTimeDelta, active, zbuf, nullptr, 0};
+  if (int rc = model_clean(m, pose, time, timeIdx, im, nullptr, cam, confThreshold, nullptr, 0, timeDelta, maxDepth, 0, 0, nullptr,
+                           (hipStream_t)s, nullptr, &cp))
+    return rc;
+  if (projected) *projected = cp.projected;
+  if (cp.projected) return DMS_OK;
+  return splat_project_only(m, pose, cam, maxDepth, projConfThreshold, projTime, timeIdx, projMaxTime, projTimeDelta, active, zbuf,
+                            (hipStream_t)s, nullptr);
+}
+int dms_splat_project_only(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, float maxDepth, float confThreshold, int time,
+                           int timeIdx, int maxTime, int timeDelta, int active, unsigned long long* zbuf, dms_stream s) {
+  return splat_project_only(m, pose, cam, maxDepth, confThreshold, time, timeIdx, maxTime, timeDelta, active, zbuf, (hipStream_t)s, nullptr);
+}
 int dms_fill_in(const dms_predict_out* ex, const dms_image2d* d, const dms_image2d* rgba, const dms_camera* cam, int pg, int pr,
                 dms_predict_out* out, dms_stream s) {
   return fill_in(ex, d, rgba, cam, pg, pr, out, (hipStream_t)s);
@@ -750,6 +800,7 @@ void dms_fusion_default_params(dms_fusion_params* p, int width, int height, floa
   p->lazy_final_prediction = 1;
   p->fused_associate = 1;
   p->fused_model_prediction = 1;
+  p->fused_clean_projection = 1;
 }
 
 // far depth cut-offs raise the static exponents of the trackers' first reductions (canon.hpp): set at creation and whenever the
@@ -842,6 +893,7 @@ int dms_fusion_create(dms_fusion** out, const dms_fusion_params* p) {
   if (const char* lz = getenv("DMS_LAZY_FINAL_PREDICTION")) f->p.lazy_final_prediction = atoi(lz) != 0 ? 1 : 0;  // A/B runs
   if (const char* fa = getenv("DMS_FUSED_ASSOCIATE")) f->p.fused_associate = atoi(fa) != 0 ? 1 : 0;                // A/B runs
   if (const char* fm = getenv("DMS_FUSED_MODEL_PREDICTION")) f->p.fused_model_prediction = atoi(fm) != 0 ? 1 : 0;  // A/B runs
+  if (const char* fc = getenv("DMS_FUSED_CLEAN_PROJECTION")) f->p.fused_clean_projection = atoi(fc) != 0 ? 1 : 0;  // A/B runs
   if (const char* pt = getenv("DMS_PREDICT_MODEL_THREADS")) {
     const int t = atoi(pt);
     if (t == 256 || t == 512 || t == 1024) f->predict_model_threads = t;
@@ -1508,10 +1560,32 @@ static int synthesise_depth(dms_fusion* f, int timeDeltaEff, hipStream_t s) {
                        f->tick - timeDeltaEff, 65535, 0, f->zbuf, nullptr, &f->depth_synth, 1, s);
 }
 
-static int clean_map(dms_fusion* f, const float* graph_host, const float* graph_dev, int graph_nodes, int timeDeltaEff, hipStream_t s) {
+// fused_clean_projection (state_mirror given): the frame's final prediction is deferred (final_prediction_deferred), so all it
+// launches is the project pass of the next frame's tracking prediction, over the map this clean writes, from the pose this clean
+// uses - the clean's scatter carries it (fusion_fuse.hip: k_clean_scatter_project) unless it runs in suffix mode or applies a
+// graph.  *projected: whether it did; predict_final then only keeps the books.
+static int clean_map(dms_fusion* f, const float* graph_host, const float* graph_dev, int graph_nodes, int timeDeltaEff, hipStream_t s,
+                     void* state_mirror = nullptr, bool* projected = nullptr) {
   StageTimer t(f->clock, s, "clean", f->profiling);
-  return model_clean(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->imap, graph_nodes > 0 ? &f->depth_synth : nullptr, &f->cam,
-                     f->p.confidence, graph_host, graph_nodes, timeDeltaEff, f->p.maxDepthProcessed, 0, 1, &f->state->surfels, s, graph_dev);
+  if (!state_mirror || graph_nodes > 0) {
+    f->clean_project_separate += 1;
+    return model_clean(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->imap, graph_nodes > 0 ? &f->depth_synth : nullptr, &f->cam,
+                       f->p.confidence, graph_host, graph_nodes, timeDeltaEff, f->p.maxDepthProcessed, 0, 1, &f->state->surfels, s, graph_dev);
+  }
+  int rc;
+  if (f->pre_valid) {  // (a projection rendered ahead that nothing consumed: predict_body would clear it before projecting)
+    if ((rc = clear_zbuf(f->zbuf2, f->p.width * f->p.height, s))) return rc;
+    f->pre_valid = false;
+  }
+  const int next_tick = f->tick + 1;  // (the camera is not lost: predict_body)
+  const ProjectRider rider = final_rider(f, state_mirror);
+  CleanProjection cp = {f->p.maxDepthProcessed, 0.7f, next_tick, next_tick, f->p.timeDelta, 1, f->zbuf2, &rider, 0};
+  if ((rc = model_clean(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->imap, nullptr, &f->cam, f->p.confidence, graph_host, 0, timeDeltaEff,
+                        f->p.maxDepthProcessed, 0, 1, &f->state->surfels, s, graph_dev, &cp)))
+    return rc;
+  *projected = cp.projected != 0;
+  (cp.projected ? f->clean_project_fused : f->clean_project_separate) += 1;
+  return DMS_OK;
 }
 
 // graph_dev: the node table in device memory (the loop solver's) instead of graph_host
@@ -1524,6 +1598,8 @@ static int process_frame_end(dms_fusion* f, const float* graph_host, int graph_n
   int rc;
   int fused = 0;
   bool surfels_written = false;
+  bool projected = false;  // the clean has projected for the next frame's tracking prediction (fused_clean_projection)
+  const int k4 = (int)(f->frames % 4);
   f->in_frame = false;
   if (f->cur_bootstrap) {
     fused = f->adopting ? 0 : 1;
@@ -1546,7 +1622,9 @@ static int process_frame_end(dms_fusion* f, const float* graph_host, int graph_n
       if ((rc = fuse_measurements(f, s))) return rc;
       if ((rc = index_map_for_clean(f, timeDeltaEff, s))) return rc;
       if (graph_nodes > 0 && (rc = synthesise_depth(f, timeDeltaEff, s))) return rc;
-      if ((rc = clean_map(f, graph_host, graph_dev, graph_nodes, timeDeltaEff, s))) return rc;
+      // fused_clean_projection: a deferred final prediction's only launch rides on the clean
+      const bool carry = f->p.fused_clean_projection && graph_nodes == 0 && final_prediction_deferred(f, one_call, f->h_state_dev + k4);
+      if ((rc = clean_map(f, graph_host, graph_dev, graph_nodes, timeDeltaEff, s, carry ? f->h_state_dev + k4 : nullptr, &projected))) return rc;
       surfels_written = true;  // the clean's scan also stores the new count into the result block
       fused = 1;
     }
@@ -1556,8 +1634,7 @@ static int process_frame_end(dms_fusion* f, const float* graph_host, int graph_n
     hipLaunchKernelGGL(k_frame_end, dim3(1), dim3(64), 0, s, f->state, f->model->d_count);
     DMS_CHECK_LAUNCH();
   }
-  const int k4 = (int)(f->frames % 4);
-  if ((rc = predict_final(f, s, f->h_state_dev + k4, one_call))) return rc;
+  if ((rc = predict_final(f, s, f->h_state_dev + k4, one_call, projected))) return rc;
   f->last_slot = k4;
   DMS_HIP(hipEventRecord(f->ev_main_done[k4], s));  // (also without the pipeline: it gates the reading of this frame's result slot)
   f->fused_last = fused;
@@ -1782,6 +1859,13 @@ int dms_fusion_get_lazy_stats(dms_fusion* f, int* eager, long* deferred, long* m
   if (deferred) *deferred = f->lazy_deferred;
   if (materialised) *materialised = f->lazy_materialised;
   if (stale) *stale = f->lazy_stale;
+  return DMS_OK;
+}
+
+int dms_fusion_get_clean_project_stats(dms_fusion* f, long* fused, long* separate) {
+  DMS_REQUIRE(f, "null argument");
+  if (fused) *fused = f->clean_project_fused;
+  if (separate) *separate = f->clean_project_separate;
   return DMS_OK;
 }
 

@@ -21,6 +21,7 @@
 
 #include "surfel.hpp"
 #include "internal.hpp"
+#include "splat_project.hpp"
 
 namespace dms {
 
@@ -701,6 +702,55 @@ __global__ __launch_bounds__(256) void k_clean_copy_back(SurfelPlanes staged, Su
   }
 }
 
+// ---- the whole-map scatter, in the parts its two kernels share ------------------------------------------------------------------
+// Offset of the block's first survivor.  block_count given (small grids): every block sums the flag counts of the blocks before
+// it itself (and block 0 the grand total = new map size, which it publishes), which saves the scan launch between the two clean
+// kernels; otherwise the offset comes from that launch.  `new_count`: what block 0 published, valid in each of its threads.
+__device__ __forceinline__ unsigned clean_block_offset(const unsigned* __restrict__ block_count, const unsigned* __restrict__ block_offset,
+                                                       size_t cap, unsigned* __restrict__ count_new, unsigned* __restrict__ count_new2,
+                                                       unsigned& new_count) {
+  new_count = 0;
+  if (!block_count) return block_offset[blockIdx.x];
+  unsigned below = 0, all = 0;
+  for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x) {
+    const unsigned c = block_count[b];
+    all += c;
+    below += b < blockIdx.x ? c : 0u;
+  }
+  const unsigned running = block_sum_u32(below);
+  if (blockIdx.x == 0) {
+    const unsigned tot = block_sum_u32(all);
+    new_count = tot < (unsigned)cap ? tot : (unsigned)cap;
+    if (threadIdx.x == 0) {
+      count_new[0] = new_count;
+      if (count_new2) count_new2[0] = new_count;
+    }
+  }
+  return running;
+}
+
+// a surviving element as the new map holds it
+template <bool DEFORM>
+__device__ __forceinline__ void clean_survivor(const CleanArgs& a, unsigned e, unsigned M, const SurfelPlanes& sp, size_t cap,
+                                               const float4* slot_pos, const float4* slot_col, const float4* slot_nrm,
+                                               const unsigned char* slot_flag, CleanElem& v) {
+  clean_load(e, M, sp, cap, slot_pos, slot_col, slot_nrm, slot_flag, a.nslots, a.timeIdx, a.planes, v);
+  if (v.vt == -2.f) {  // copy_unstable.vert:124-129
+    v.col.w = (float)a.time;
+    v.vt = (float)a.time;
+  }
+  if (DEFORM && a.nodes > 0 && v.col.z != (float)a.time) clean_deform(a, v);  // :161
+}
+
+__device__ __forceinline__ void clean_store(const CleanArgs& a, const SurfelPlanes& out, size_t cap, size_t dst, const CleanElem& v) {
+  out.pos[dst] = to4(v.pos);
+  out.col[dst] = to4(v.col);
+  out.nrm[dst] = to4(v.nrm);
+#pragma unroll
+  for (int s = 0; s < DMS_MAX_SENSORS; ++s)
+    if (s < a.planes) out.times[(size_t)s * cap + dst] = (s == a.timeIdx) ? v.vt : v.times[s];  // (the other planes hold -3 already)
+}
+
 __global__ __launch_bounds__(256) void k_clean_scatter(CleanArgs a, SurfelPlanes sp, size_t cap, const unsigned* __restrict__ d_count,
                                                        const float4* slot_pos, const float4* slot_col, const float4* slot_nrm,
                                                        unsigned char* slot_flag, const unsigned char* __restrict__ keep,
@@ -710,28 +760,8 @@ __global__ __launch_bounds__(256) void k_clean_scatter(CleanArgs a, SurfelPlanes
   const unsigned M = d_count[0];
   const unsigned total = M + (unsigned)a.nslots;
   const unsigned base = blockIdx.x * kScanChunk;
-  unsigned running;
-  if (block_count) {
-    // small grids: every block sums the flag counts of the blocks before it itself (and block 0 the
-    // grand total = new map size), which saves the scan launch between the two clean kernels
-    unsigned below = 0, all = 0;
-    for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x) {
-      const unsigned c = block_count[b];
-      all += c;
-      below += b < blockIdx.x ? c : 0u;
-    }
-    running = block_sum_u32(below);
-    if (blockIdx.x == 0) {
-      const unsigned tot = block_sum_u32(all);
-      if (threadIdx.x == 0) {
-        const unsigned c = tot < (unsigned)cap ? tot : (unsigned)cap;
-        count_new[0] = c;
-        if (count_new2) count_new2[0] = c;
-      }
-    }
-  } else {
-    running = block_offset[blockIdx.x];
-  }
+  unsigned new_count;
+  unsigned running = clean_block_offset(block_count, block_offset, cap, count_new, count_new2, new_count);
   if (base >= total) return;
   for (int k = 0; k < kScanChunk / 256; ++k) {
     const unsigned e = base + k * 256 + threadIdx.x;
@@ -742,18 +772,8 @@ __global__ __launch_bounds__(256) void k_clean_scatter(CleanArgs a, SurfelPlanes
       const size_t dst = (size_t)running + rank;
       if (dst < cap) {
         CleanElem v;
-        clean_load(e, M, sp, cap, slot_pos, slot_col, slot_nrm, slot_flag, a.nslots, a.timeIdx, a.planes, v);
-        if (v.vt == -2.f) {  // copy_unstable.vert:124-129
-          v.col.w = (float)a.time;
-          v.vt = (float)a.time;
-        }
-        if (a.nodes > 0 && v.col.z != (float)a.time) clean_deform(a, v);  // :161
-        out.pos[dst] = to4(v.pos);
-        out.col[dst] = to4(v.col);
-        out.nrm[dst] = to4(v.nrm);
-#pragma unroll
-        for (int s = 0; s < DMS_MAX_SENSORS; ++s)
-          if (s < a.planes) out.times[(size_t)s * cap + dst] = (s == a.timeIdx) ? v.vt : v.times[s];  // (the other planes hold -3 already)
+        clean_survivor<true>(a, e, M, sp, cap, slot_pos, slot_col, slot_nrm, slot_flag, v);
+        clean_store(a, out, cap, dst, v);
       }
     }
     // the parked measurement of this element is consumed (a later clean without a fuse must not
@@ -761,6 +781,57 @@ __global__ __launch_bounds__(256) void k_clean_scatter(CleanArgs a, SurfelPlanes
     if (e >= M && e < total) slot_flag[e - M] = 0;
     running += tot;
   }
+}
+
+// fused_clean_projection: the same scatter without a deformation graph, each block then running the splat project pass
+// (splat_project.hpp) over the survivors it has just stored, from the registers that hold them: what k_splat_project<false>
+// would read back from the new map - position and confidence, the time after the -2 rule, normal and radius - under the new id
+// `dst`.  A cell's winner is the minimum of the same keys, so `zbuf` ends as that kernel leaves it.  The scatter is a chain of
+// dependent round trips (counts -> offsets -> element -> stores) and the sprite loop is bound by vector issue: here the blocks
+// that wait for memory share the CU with blocks that rasterise.  The element is fetched before the offsets are formed (it does not
+// depend on them).  Block 0 carries the project launch's rider; with the offsets formed inline it is also the block that
+// publishes the new count, which the mirrored result block must contain (count_new2 points into it): the mirror takes that word
+// from the block's registers, not from memory.
+static_assert(kScanChunk == 256, "k_clean_scatter_project: one element per thread");
+__global__ __launch_bounds__(256) void k_clean_scatter_project(CleanArgs a, SurfelPlanes sp, size_t cap, const unsigned* __restrict__ d_count,
+                                                               const float4* slot_pos, const float4* slot_col, const float4* slot_nrm,
+                                                               unsigned char* slot_flag, const unsigned char* __restrict__ keep,
+                                                               const unsigned* __restrict__ block_offset, SurfelPlanes out,
+                                                               const unsigned* __restrict__ block_count, unsigned* __restrict__ count_new,
+                                                               unsigned* __restrict__ count_new2, ProjArgs pa,
+                                                               unsigned long long* __restrict__ zbuf, ProjectRider rd) {
+  __shared__ SplatTables tb;
+  const int t = threadIdx.x;
+  const unsigned M = d_count[0];
+  const unsigned total = M + (unsigned)a.nslots;
+  const unsigned e = blockIdx.x * kScanChunk + t;
+  const bool f = (e < total) && keep[e];
+  CleanElem v;
+  if (f) clean_survivor<false>(a, e, M, sp, cap, slot_pos, slot_col, slot_nrm, slot_flag, v);
+  unsigned new_count;
+  const unsigned running = clean_block_offset(block_count, block_offset, cap, count_new, count_new2, new_count);
+  if (blockIdx.x == 0) {
+    if (t < rd.mirror_words) {
+      unsigned w = rd.mirror_src[t];
+      if (block_count && rd.mirror_src + t == count_new2) w = new_count;
+      rd.mirror_dst[t] = w;
+    }
+    if (t < rd.copy_words) rd.copy_dst[t] = rd.copy_src[t];
+  }
+  if (blockIdx.x * kScanChunk >= total) return;
+  unsigned tot;
+  const unsigned rank = block_exclusive_rank(f, tot);
+  int rows_here = 0;
+  if (f) {
+    const size_t dst = (size_t)running + rank;
+    if (dst < cap) {  // (a survivor the capacity cuts off is neither stored nor projected)
+      clean_store(a, out, cap, dst, v);
+      SplatSurfel s;
+      if (splat_vertex_held(pa, to4(v.pos), to4(v.nrm), v.vt, s)) rows_here = splat_park<false, true>(pa, s, 1, (unsigned)dst, t, tb);
+    }
+  }
+  if (e >= M && e < total) slot_flag[e - M] = 0;  // the parked measurement is consumed
+  splat_rows<false, true>(pa, splat_ray_consts(pa), rows_here, 0u, tb, zbuf, nullptr);
 }
 
 // Suffix-mode scatter (large maps, no deformation graph): the blocks before first_touched[0] hold map surfels
@@ -910,13 +981,24 @@ int model_flush_pending(dms_model* m, hipStream_t s) {
 
 int model_clean(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_indexmap_out* im, const dms_image2d* depth_synth,
                 const dms_camera* cam, float confThreshold, const float* graph_host, int graph_nodes, int timeDelta, float maxDepth,
-                int isFern, int transposed, unsigned* count_out2, hipStream_t s, const float* graph_dev) {
+                int isFern, int transposed, unsigned* count_out2, hipStream_t s, const float* graph_dev, CleanProjection* project) {
   DMS_REQUIRE(m && !m->pending_update, "a deferred update pass is still pending (index_map applies it)");
   DMS_REQUIRE(m && pose && im && cam, "null argument");
   DMS_REQUIRE(timeIdx >= 0 && timeIdx < DMS_MAX_SENSORS, "timeIdx out of range");
   const int W = m->width, H = m->height;
   DMS_REQUIRE(dense_img(im->index, 4, W, H) && dense_img(im->vertConf, 16, W, H) && dense_img(im->colorTime, 16, W, H),
               "dense W×H index-map images required");
+  if (project) {  // (the conditions of splat_project_only)
+    DMS_REQUIRE(project->zbuf, "null argument");
+    DMS_REQUIRE(fabsf(cam->fx) > 1e-18f && fabsf(cam->fx) < 1e18f && fabsf(cam->fy) > 1e-18f && fabsf(cam->fy) < 1e18f &&
+                    project->maxDepth > 1e-18f && project->maxDepth < 1e18f,
+                "focal lengths and depth cut-off must be finite, non-zero and within 1e-18 .. 1e18");
+    const ProjectRider* rider = project->rider;
+    DMS_REQUIRE(!rider || (rider->mirror_words >= 0 && rider->mirror_words <= 256 && rider->copy_words >= 0 && rider->copy_words <= 256 &&
+                           (rider->mirror_words == 0 || (rider->mirror_src && rider->mirror_dst)) &&
+                           (rider->copy_words == 0 || (rider->copy_src && rider->copy_dst))),
+                "a rider copies at most 256 dwords (one block)");
+  }
   if (graph_nodes >= m->max_nodes) {  // assert(graph.size() / 16 < MAX_NODES), GlobalModel.cpp:703
     set_error("dms_model_clean: %d deformation nodes exceed the limit %d", graph_nodes, m->max_nodes);
     return DMS_ERR_CAPACITY;
@@ -971,10 +1053,22 @@ int model_clean(dms_model* m, const dms_pose_block* pose, int time, int timeIdx,
     DMS_CHECK_LAUNCH();
   }
   const int suffix_grid = nb < 2048 ? nb : 2048;  // suffix mode: blocks loop from the first touched block on
-  if (suffix)
+  if (project) project->projected = 0;
+  if (suffix) {
     hipLaunchKernelGGL(k_clean_scatter_suffix, dim3(suffix_grid), dim3(256), 0, s, a, src, m->cap, m->d_count, m->slot_pos, m->slot_col,
                        m->slot_nrm, m->slot_flag, m->keep, m->block_offset, dst, m->clean_first);
-  else
+  } else if (project && graph_nodes == 0) {
+    ProjArgs pa;
+    fill_proj(pa, m, pose, cam, project->maxDepth, project->time, timeIdx, project->timeDelta);
+    pa.confThreshold = project->confThreshold;
+    pa.maxTime = project->maxTime;
+    pa.actv = project->active ? 1 : 0;
+    const ProjectRider no_rider = {nullptr, nullptr, 0, nullptr, nullptr, 0};
+    hipLaunchKernelGGL(k_clean_scatter_project, dim3(nb), dim3(256), 0, s, a, src, m->cap, m->d_count, m->slot_pos, m->slot_col, m->slot_nrm,
+                       m->slot_flag, m->keep, m->block_offset, dst, inline_scan ? m->block_count : (const unsigned*)nullptr, m->d_count_alt,
+                       count_out2, pa, project->zbuf, project->rider ? *project->rider : no_rider);
+    project->projected = 1;
+  } else
     hipLaunchKernelGGL(k_clean_scatter, dim3(nb), dim3(256), 0, s, a, src, m->cap, m->d_count, m->slot_pos, m->slot_col, m->slot_nrm,
                        m->slot_flag, m->keep, m->block_offset, dst, inline_scan ? m->block_count : (const unsigned*)nullptr, m->d_count_alt,
                        count_out2);

@@ -16,6 +16,7 @@
 #include "surfel.hpp"
 #include "fill.hpp"
 #include "internal.hpp"
+#include "splat_project.hpp"
 #include "host_util.hpp"
 #include "track_init.hpp"
 #include "model_bodies.hpp"
@@ -84,6 +85,7 @@ int dms_model_create(dms_model** out, size_t capacity, int width, int height) {
     return hip_fail(e, "hipHostMalloc", __FILE__, __LINE__);
   }
   DMS_HIP(hipMemset(m->d_count, 0, 8 * sizeof(unsigned)));
+  DMS_HIP(hipMemset(m->slot_flag, 0, (size_t)m->slots));  // no measurement is parked: a clean before the first fuse appends nothing
   hipLaunchKernelGGL(k_fill_u32, dim3(1024), dim3(256), 0, 0, m->winner, m->cap, kEmptyWinner);
   DMS_CHECK_LAUNCH();
   for (int b = 0; b < 2; ++b) {  // every time plane of both buffers: -3.0f, "never seen by this sensor" (surfel.hpp, live_planes)
@@ -358,24 +360,6 @@ int model_initialise(dms_model* m, const dms_image2d* rgba, const dms_image2d* d
 // ---------------------------------------------------------------------------------------
 // G5: index map (index_map.vert:41-67, index_map.frag:31-37)
 // ---------------------------------------------------------------------------------------
-struct ProjArgs {
-  const dms_pose_block* pose;
-  float cx, cy, fx, fy;
-  float colsf, rowsf;
-  int cols, rows;
-  float maxDepth;
-  int time, timeIdx, timeDelta;
-  // splat only
-  float confThreshold;
-  int maxTime;
-  int actv;
-  // index map only: 1 = images stored column-major (pixel (x, y) at x * rows + y).  The fusion
-  // consumers walk the image by columns (the reference's draw order, GlobalModel.cpp:100-108),
-  // so this is the layout that makes their 16-byte gathers coalesce.
-  int transposed;
-  int xcd;  // XCD-aware block order of the per-pixel passes (common.hpp xcd_block)
-};
-
 __global__ void k_clear_zbuf(unsigned long long* z, int n) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += blockDim.x * gridDim.x) z[i] = kZClear;
 }
@@ -384,20 +368,6 @@ int clear_zbuf(unsigned long long* zbuf, int n, hipStream_t s) {
   hipLaunchKernelGGL(k_clear_zbuf, dim3(min((n + 255) / 256, 2048)), dim3(256), 0, s, zbuf, n);
   DMS_CHECK_LAUNCH();
   return DMS_OK;
-}
-
-// window position of a camera-frame point through the shader's NDC arithmetic
-// (index_map.vert:56-57 / splat.vert:37-42) and the viewport transform xw = (x_ndc + 1) * (W/2).
-__device__ __forceinline__ bool project_window(const ProjArgs& a, const f3& p, float& xw, float& yw, float& zw) {
-  const float xn = ((((a.fx * p.x) / p.z) + a.cx) - (a.colsf * 0.5f)) / (a.colsf * 0.5f);
-  const float yn = ((((a.fy * p.y) / p.z) + a.cy) - (a.rowsf * 0.5f)) / (a.rowsf * 0.5f);
-  const float zn = p.z / a.maxDepth;
-  // GL clips a point by its centre against -w <= x,y,z <= w (w = 1)
-  if (!(xn >= -1.f && xn <= 1.f && yn >= -1.f && yn <= 1.f && zn >= -1.f && zn <= 1.f)) return false;
-  xw = (xn + 1.f) * (a.colsf * 0.5f);
-  yw = (yn + 1.f) * (a.rowsf * 0.5f);
-  zw = zn * 0.5f + 0.5f;
-  return true;
 }
 
 // APPLY: the update pass of the preceding fuse (model_fuse with defer_update) has not run: a surfel that won a measurement
@@ -489,28 +459,6 @@ static int surfel_grid(size_t upper) {
 
 static bool dense_img(const dms_image2d& im, size_t elem, int w, int h) {
   return im.data && im.cols == w && im.rows == h && im.pitch == (size_t)w * elem;
-}
-
-static void fill_proj(ProjArgs& a, const dms_model* m, const dms_pose_block* pose, const dms_camera* cam, float maxDepth, int time,
-                      int timeIdx, int timeDelta) {
-  a.pose = pose;
-  a.cx = cam->cx;
-  a.cy = cam->cy;
-  a.fx = cam->fx;
-  a.fy = cam->fy;
-  a.cols = m->width;
-  a.rows = m->height;
-  a.colsf = (float)m->width;
-  a.rowsf = (float)m->height;
-  a.maxDepth = maxDepth;
-  a.time = time;
-  a.timeIdx = timeIdx;
-  a.timeDelta = timeDelta;
-  a.confThreshold = 0.f;
-  a.maxTime = 0;
-  a.actv = 0;
-  a.transposed = 0;
-  a.xcd = xcd_remap_enabled();
 }
 
 // The projection half of index_map: zbuf (empty on entry when zclean) receives the depth-tested surfel ids
@@ -829,61 +777,6 @@ int model_sample_graph(dms_model* m, int sampleRate, float* rows4_host, int max_
 // ---------------------------------------------------------------------------------------
 // G6 / G6': splat prediction (splat.vert:57-94, combo_splat.frag:35-60, depth_splat.frag:29-46)
 // ---------------------------------------------------------------------------------------
-struct SplatSurfel {
-  f3 pos;       // camera frame
-  f3 nrm;       // camera frame, normalised
-  float rad, conf;
-  float xw, yw;  // sprite centre in window coordinates
-  float size;    // gl_PointSize
-};
-
-__device__ __forceinline__ f3 project_image(const ProjArgs& a, const f3& p) {  // splat.vert:44-49
-  return mk3(((a.fx * p.x) / p.z) + a.cx, ((a.fy * p.y) / p.z) + a.cy, p.z);
-}
-
-// vertex stage: returns false when the surfel is culled / clipped
-// (the normal / radius plane is read only for surfels that survive the cull and the clip: for a large map most do
-// not, and the pass is bandwidth-bound there — 20 instead of 36 bytes per culled surfel)
-// the cull of splat.vert for one set of (confidence threshold, time, newest time) — the part of the vertex stage that
-// differs between two predictions of the same map from the same pose
-__device__ __forceinline__ bool splat_culled(const ProjArgs& a, const f3& ph, float conf, float vt, float confThreshold, int time, int maxTime) {
-  const bool actv = a.actv != 0;
-  return !(!actv && vt == -3.f) && (ph.z > a.maxDepth || ph.z < 0.f || conf < confThreshold || (actv && vt == -3.f) ||
-                                    (vt != -3.f && (float)time - vt > (float)a.timeDelta) || vt > (float)maxTime);
-}
-
-struct SplatSecond {  // second prediction sharing the project pass (same map, pose, depth range and mode)
-  float confThreshold;
-  int time, maxTime;
-};
-
-// `pass`: bit 0 = survives the cull of `a`, bit 1 = survives the cull of `b` (when given)
-__device__ __forceinline__ bool splat_vertex(const ProjArgs& a, const float4& pc, const float4* __restrict__ nrp, float vt, SplatSurfel& o,
-                                             const SplatSecond* b = nullptr, int* pass = nullptr) {
-  const float* Tinv = a.pose->t_inv;
-  const f3 ph = xform_point(Tinv, mk3(pc.x, pc.y, pc.z));
-  int keep = splat_culled(a, ph, pc.w, vt, a.confThreshold, a.time, a.maxTime) ? 0 : 1;
-  if (b) keep |= splat_culled(a, ph, pc.w, vt, b->confThreshold, b->time, b->maxTime) ? 0 : 2;
-  if (pass) *pass = keep;
-  if (!keep) return false;
-  float zw;
-  if (!project_window(a, ph, o.xw, o.yw, zw)) return false;
-  const float4 nr = *nrp;
-  o.pos = ph;
-  o.conf = pc.w;
-  o.rad = nr.w;
-  o.nrm = normalized3(xform_dir(Tinv, mk3(nr.x, nr.y, nr.z)));
-  const f3 x1n = normalized3(mk3(o.nrm.y - o.nrm.z, -o.nrm.x, o.nrm.x));
-  const f3 x1 = mk3((x1n.x * o.rad) * 1.41421356f, (x1n.y * o.rad) * 1.41421356f, (x1n.z * o.rad) * 1.41421356f);
-  const f3 y1 = cross3(o.nrm, x1);
-  const f3 p1 = project_image(a, ph + x1), p2 = project_image(a, ph + y1), p3 = project_image(a, ph - y1), p4 = project_image(a, ph - x1);
-  const float xmin = fminf(p1.x, fminf(p2.x, fminf(p3.x, p4.x))), xmax = fmaxf(p1.x, fmaxf(p2.x, fmaxf(p3.x, p4.x)));
-  const float ymin = fminf(p1.y, fminf(p2.y, fminf(p3.y, p4.y))), ymax = fmaxf(p1.y, fmaxf(p2.y, fmaxf(p3.y, p4.y)));
-  const float xDiff = fabsf(xmax - xmin), yDiff = fabsf(ymax - ymin);
-  o.size = fmaxf(0.f, fmaxf(xDiff, yDiff));
-  return true;
-}
-
 // fragment stage at pixel (px, py): ray/disc test.  Returns false on discard.
 __device__ __forceinline__ bool splat_fragment(const ProjArgs& a, const SplatSurfel& s, int px, int py, f3& corrected, float& zw) {
   const float fcx = (float)px + 0.5f, fcy = (float)py + 0.5f;  // gl_FragCoord
@@ -897,50 +790,7 @@ __device__ __forceinline__ bool splat_fragment(const ProjArgs& a, const SplatSur
   return true;
 }
 
-// The same fragment in fewer instructions for the project pass, whose sprite loop is bound by vector-instruction issue: four IEEE
-// quotients, a square root and the 64-bit depth conversion were 70 of a fragment's 115 instructions.  exact_arith.hpp: the divisors
-// fx, fy and 2 maxDepth are constants of the launch (reciprocal once, two correction steps per quotient); the ray's squared length is
-// in [1, 16) for any pixel within 3.8 focal lengths of the principal point (square root without the small-operand scaling, reciprocal
-// by one Newton step - both compared with the IEEE results over their whole domains on the device).  Same bits as splat_fragment:
-// the accept / reject decision, the depth and `corrected` (a -0 quotient becomes +0 only where 0.5 is added next or the operand is
-// an exact difference, which is never -0; NaN / infinite depths are rejected on both sides).
-struct SplatRay {
-  exact::Divisor fx, fy, z2;
-};
-__device__ __forceinline__ SplatRay splat_ray_consts(const ProjArgs& a) {
-  return SplatRay{exact::divisor(a.fx), exact::divisor(a.fy), exact::divisor(2.f * a.maxDepth)};
-}
-__device__ __forceinline__ bool splat_fragment_lean(const SplatRay& rc, const ProjArgs& a, const SplatSurfel& s, int px, int py, f3& corrected, float& zw) {
-  const float fcx = (float)px + 0.5f, fcy = (float)py + 0.5f;  // gl_FragCoord
-  const f3 v = mk3(exact::div(fcx - a.cx, rc.fx), exact::div(fcy - a.cy, rc.fy), 1.0f);
-  const float vv = dot3(v, v);
-  const float rn = vv < 16.f ? exact::rcp_1_4(exact::sqrt_normal(vv)) : 1.0f / sqrtf(vv);
-  const f3 l = mk3(v.x * rn, v.y * rn, v.z * rn);
-  const float k = dot3(s.pos, s.nrm) / dot3(l, s.nrm);
-  corrected = mk3(k * l.x, k * l.y, k * l.z);
-  const float sqrRad = s.rad * s.rad;
-  const f3 diff = corrected - s.pos;
-  if (dot3(diff, diff) > sqrRad) return false;
-  zw = exact::div(corrected.z, rc.z2) + 0.5f;
-  return true;
-}
-
-// sprite coverage: pixel centres inside [c - size/2, c + size/2); a size below 1 rasterises as 1
-__device__ __forceinline__ void sprite_range(float c, float size, int n, int& lo, int& hi) {
-  const float sz = fmaxf(size, 1.0f);
-  const float a = c - sz * 0.5f, b = c + sz * 0.5f;
-  lo = (int)ceilf(a - 0.5f);
-  hi = (int)ceilf(b - 0.5f) - 1;
-  if (lo < 0) lo = 0;
-  if (hi > n - 1) hi = n - 1;
-}
-
-// Sprite sizes differ by up to 3x inside a wave (5x5 ... 9x9 pixels), so "one thread rasterises its
-// surfel" leaves ~55 % of the lanes idle in a loop that is instruction bound.  Here a block runs the
-// vertex stage for 256 surfels, parks their parameters in LDS, and then hands out sprite ROWS to
-// threads (prefix sum of the row counts + binary search): a thread's trip count is one sprite width,
-// and the rows of a large sprite are spread over many threads.  The winners are decided by 64-bit
-// atomicMin, so the work order does not matter.
+// The project pass over the map (splat_project.hpp: vertex stage, sprite rows, fragments), 256 surfels per block and chunk.
 // DUAL: one pass over the map feeds two z-buffers — two predictions of the same map from the same pose that differ in
 // the cull only (the frame's final prediction and the next frame's tracking prediction): the vertex stage and the sprite
 // loop run once, a fragment competes in the z-buffer of every prediction its surfel survives the cull of.
@@ -950,15 +800,9 @@ __global__ __launch_bounds__(256) void k_splat_project(ProjArgs a, SurfelPlanes 
                                                        unsigned long long* __restrict__ zbuf2, ProjectRider rd) {
   // (a project pass that no resolve follows - the deferred final prediction of fusion_frame.hip - is the frame's last kernel:
   // its block 0 carries what the resolve's block 0 would have, before anything else; both counts are 0 otherwise)
-  if (blockIdx.x == 0) {
-    if ((int)threadIdx.x < rd.mirror_words) rd.mirror_dst[threadIdx.x] = rd.mirror_src[threadIdx.x];
-    if ((int)threadIdx.x < rd.copy_words) rd.copy_dst[threadIdx.x] = rd.copy_src[threadIdx.x];
-  }
-  __shared__ float s_par[10][256];  // pos.xyz, nrm.xyz, rad, window x / y of the centre, squared reach (below)
-  __shared__ int s_box[4][256];     // x0, width, y0, cull survivors (DUAL)
-  __shared__ unsigned s_off[257];   // exclusive prefix of the row counts
-  __shared__ unsigned s_w[4];
-  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+  if (blockIdx.x == 0) splat_rider(rd);
+  __shared__ SplatTables tb;
+  const int t = threadIdx.x;
   const unsigned M = d_count[0];
   const SplatRay ray = splat_ray_consts(a);
   // position and time of the next chunk are fetched while this one is scanned and rasterised: on a large map
@@ -987,126 +831,9 @@ __global__ __launch_bounds__(256) void k_splat_project(ProjArgs a, SurfelPlanes 
     if (i < M) {
       SplatSurfel s;
       int pass = 1;
-      if (splat_vertex(a, pc, sp.nrm + i, vt, s, DUAL ? &b2 : nullptr, &pass) && s.size == s.size) {
-        int x0, x1, y0, y1;
-        sprite_range(s.xw, s.size, a.cols, x0, x1);
-        sprite_range(s.yw, s.size, a.rows, y0, y1);
-        // The sprite is the square around four points at sqrt(2) r along the tangent axes; the disc test passes on about
-        // 40 % of its fragments.  A fragment can only pass if its ray comes within r of the centre P = Z (xc, yc, 1):
-        // the distance of P from the ray along v = (x, y, 1) is Z |(xc, yc, 1) x v| / |v| >= Z rho / |v|, with
-        // rho^2 = (x - xc)^2 + (y - yc)^2 — the fragment's offset from the centre in normalised image coordinates —
-        // and |v|^2 <= G2 = 1 + (|xc| + h)^2 + (|yc| + h)^2 inside the sprite (half size h).  So rho > r sqrt(G2) / Z
-        // rules a fragment out; with 2 % (and 0.02 pixel) added, far more than the rounding of the fragment test itself, the
-        // rows and the columns of each row are cut to that circle before any fragment is evaluated.
-        float reach = 3.0e18f;  // normalised units; no cut when the bound cannot be formed
-        {
-          const float ifx = 1.f / a.fx, ify = 1.f / a.fy;
-          const float h = (0.5f * fmaxf(s.size, 1.f) + 1.f) * fmaxf(ifx, ify);
-          const float xc = fabsf((s.xw - a.cx) * ifx) + h, yc = fabsf((s.yw - a.cy) * ify) + h;
-          const float g2 = 1.f + xc * xc + yc * yc;
-          const float rn = (s.rad * sqrtf(g2) / s.pos.z) * 1.02f + 0.02f * fmaxf(ifx, ify);
-          if (s.pos.z > 0.f && rn == rn && rn < 3.0e18f) reach = rn;
-          const float ry = fminf(reach * a.fy, 1.0e9f);
-          const int c0 = (int)ceilf(fmaxf(s.yw - ry - 0.5f, -1.0e9f)), c1 = (int)floorf(fminf(s.yw + ry - 0.5f, 1.0e9f));  // |py + 0.5 - yw| <= ry
-          y0 = max(y0, c0);
-          y1 = min(y1, c1);
-        }
-        if (x1 >= x0 && y1 >= y0) {
-          rows_here = y1 - y0 + 1;
-          s_par[0][t] = s.pos.x;
-          s_par[1][t] = s.pos.y;
-          s_par[2][t] = s.pos.z;
-          s_par[3][t] = s.nrm.x;
-          s_par[4][t] = s.nrm.y;
-          s_par[5][t] = s.nrm.z;
-          s_par[6][t] = s.rad;
-          s_par[7][t] = s.xw;
-          s_par[8][t] = s.yw;
-          s_par[9][t] = reach * reach;
-          s_box[0][t] = x0;
-          s_box[1][t] = x1 - x0 + 1;
-          s_box[2][t] = y0;
-          if (DUAL) s_box[3][t] = pass;
-        }
-      }
+      if (splat_vertex(a, pc, sp.nrm + i, vt, s, DUAL ? &b2 : nullptr, &pass)) rows_here = splat_park<DUAL, false>(a, s, pass, 0u, t, tb);
     }
-    // block-wide exclusive scan of rows_here
-    unsigned incl = (unsigned)rows_here;
-    for (int off = 1; off < 64; off <<= 1) {
-      const unsigned up = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += up;
-    }
-    if (lane == 63) s_w[wid] = incl;
-    __syncthreads();
-    unsigned wbase = 0;
-    for (int w = 0; w < wid; ++w) wbase += s_w[w];
-    s_off[t] = wbase + incl - (unsigned)rows_here;
-    if (t == 255) s_off[256] = wbase + incl;
-    __syncthreads();
-    const unsigned total = s_off[256];
-    for (unsigned u = t; u < total; u += 256u) {
-      // surfel j with s_off[j] <= u < s_off[j + 1]
-      int lo = 0, hi = 256;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int mid = (lo + hi) >> 1;
-        if (s_off[mid] <= u)
-          lo = mid;
-        else
-          hi = mid;
-      }
-      const int j = lo;
-      SplatSurfel s;
-      s.pos = mk3(s_par[0][j], s_par[1][j], s_par[2][j]);
-      s.nrm = mk3(s_par[3][j], s_par[4][j], s_par[5][j]);
-      s.rad = s_par[6][j];
-      const int x0 = s_box[0][j], w = s_box[1][j];
-      const int py = s_box[2][j] + (int)(u - s_off[j]);
-      const unsigned long long id = (unsigned long long)(base + (unsigned)j);
-      const int pass = DUAL ? s_box[3][j] : 1;
-      // columns of this row inside the surfel's reach (see the vertex stage)
-      const float dyn = (((float)py + 0.5f) - s_par[8][j]) * (1.f / a.fy);
-      const float left = s_par[9][j] - dyn * dyn;
-      if (left < 0.f) continue;
-      const float rx = fminf(sqrtf(left) * a.fx, 1.0e9f), xwc = s_par[7][j];
-      const int xa = max(x0, (int)ceilf(fmaxf(xwc - rx - 0.5f, -1.0e9f)));  // |px + 0.5 - xw| <= rx
-      const int xb = min(x0 + w - 1, (int)floorf(fminf(xwc + rx - 0.5f, 1.0e9f)));
-      // The row in groups of four fragments: the z-buffer cells a group will compete for are fetched first (their addresses
-      // depend on the pixel only), the ray / disc tests run while those loads are in flight, and a fragment goes to the
-      // atomic only when it beats the value fetched (cells only ever decrease: a stale value can cost an atomic, never a win).
-      const bool use1 = !DUAL || (pass & 1), use2 = DUAL && (pass & 2);
-      for (int px0 = xa; px0 <= xb; px0 += 4) {
-        unsigned long long z1[4], z2[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int px = px0 + k;
-          const size_t q = (size_t)px * a.rows + py;  // column-major z-buffer
-          const bool in = px <= xb;
-          z1[k] = (in && use1) ? zbuf[q] : 0ull;
-          z2[k] = (in && use2) ? zbuf2[q] : 0ull;
-        }
-        // (the four ray / disc tests first, the atomics behind them: an atomic between two tests made the next test wait for it -
-        // the counter that guards the prefetched cells also counts the atomics in flight)
-        unsigned long long key[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int px = px0 + k;
-          key[k] = ~0ull;
-          f3 c;
-          float zw;
-          if (px <= xb && splat_fragment_lean(ray, a, s, px, py, c, zw)) {
-            const unsigned d = depth24(zw);
-            if (d < 0xFFFFFFu) key[k] = ((unsigned long long)d << 32) | id;
-          }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const size_t q = (size_t)(px0 + k) * a.rows + py;
-          if (key[k] < z1[k]) atomicMin(zbuf + q, key[k]);
-          if (DUAL && key[k] < z2[k]) atomicMin(zbuf2 + q, key[k]);
-        }
-      }
-    }
+    splat_rows<DUAL, false>(a, ray, rows_here, base, tb, zbuf, zbuf2);
     __syncthreads();  // the parameter tables are rewritten by the next chunk
   }
 }

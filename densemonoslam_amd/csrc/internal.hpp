@@ -126,9 +126,22 @@ int model_fuse_zbuf(dms_model* m, const dms_pose_block* pose, int time, int time
                     const float* weighting_dev, hipStream_t s, int defer_update = 0);
 int model_fuse_scratch(dms_model* m, float* slot_pos4, float* slot_col4, float* slot_nrm4, unsigned* slot_best, unsigned char* slot_flag,
                        unsigned* winner, size_t winner_count, hipStream_t s);
+// fused_clean_projection: a splat project pass (the arguments of splat_project_only, from the clean's pose, camera and time slot)
+// that the clean's scatter carries - every survivor is projected by the thread that has just stored it, under its new id, into the
+// CLEAN `zbuf`: the cells splat_project_only would leave after the clean.  Taken by a whole-map clean without a deformation graph;
+// `projected` says whether it was (0: suffix mode or a graph - the caller projects by itself).  `rider`: see ProjectRider; its
+// mirror may contain the word count_out2 points to.
+struct CleanProjection {
+  float maxDepth, confThreshold;
+  int time, maxTime, timeDelta, active;
+  unsigned long long* zbuf;
+  const ProjectRider* rider;
+  int projected;
+};
 int model_clean(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_indexmap_out* im, const dms_image2d* depth_synth,
                 const dms_camera* cam, float confThreshold, const float* graph_host, int graph_nodes, int timeDelta, float maxDepth,
-                int isFern, int transposed, unsigned* count_out2, hipStream_t s, const float* graph_dev = nullptr);
+                int isFern, int transposed, unsigned* count_out2, hipStream_t s, const float* graph_dev = nullptr,
+                CleanProjection* project = nullptr);
 
 // deform.hip: dms_deform_add_constraints over rows of `stride` >= 7 floats
 int deform_add_rows(dms_deform* d, const float* rows_dev, int stride, int n, int srcTime, int pin, hipStream_t s);

@@ -41,7 +41,7 @@ class FusionParams(C.Structure):
         ("nid_bins_depth", C.c_int), ("nid_pyramid_level", C.c_int),
         ("local_loop_closure", C.c_int), ("reloc", C.c_int), ("num_sensors", C.c_int), ("share_projection", C.c_int),
         ("fused_fill_in", C.c_int), ("hybrid_loops", C.c_int), ("lazy_final_prediction", C.c_int),
-        ("fused_associate", C.c_int), ("fused_model_prediction", C.c_int),
+        ("fused_associate", C.c_int), ("fused_model_prediction", C.c_int), ("fused_clean_projection", C.c_int),
     ]
 
 
@@ -54,6 +54,8 @@ class FrameResult(C.Structure):
         ("tracking_ok", C.c_int), ("lost", C.c_int),
     ]
 
+
+Z_CLEAR = (0xFFFFFF << 32) | 0xFFFFFFFF  # an empty z-buffer cell: depth 1.0 (24 bits), no surfel (csrc/surfel.hpp: kZClear)
 
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 _I2 = C.POINTER(Image2D)
@@ -86,7 +88,9 @@ lib.dms_model_apply_pending.argtypes = [_P, _P]
 lib.dms_model_fuse_scratch.argtypes = [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]
 lib.dms_fusion_debug_keep_assoc_zbuf.argtypes = [_P, _I]
 lib.dms_model_clean.argtypes = [_P, _P, _I, _I, C.POINTER(IndexMapOut), _I2, _K, _F, C.POINTER(C.c_float), _I, _I, _F, _I, _P]
-lib.dms_fill_in.argtypes = [C.POINTER(PredictOut), _I2, _I2, _K, _I, _I, C.POINTER(PredictOut), _P]
+lib.dms_model_clean_project.argtypes = [_P, _P, _I, _I, C.POINTER(IndexMapOut), _K, _F, _I, _F, _F, _I, _I, _I, _I, _P, C.POINTER(C.c_int), _P]
+lib.dms_splat_project_only.argtypes = [_P, _P, _K, _F, _F, _I, _I, _I, _I, _I, _P, _P]
+lib.dms_fill_in.argtypes =[C.POINTER(PredictOut), _I2, _I2, _K, _I, _I, C.POINTER(PredictOut), _P]
 lib.dms_resize_nn.argtypes = [_I2, _I2, _I, _P]
 lib.dms_fusion_default_params.argtypes = [C.POINTER(FusionParams), _I, _I, _F, _F, _F, _F]
 lib.dms_fusion_default_params.restype = None
@@ -128,6 +132,7 @@ lib.dms_pose_compose.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.P
 lib.dms_fusion_set_profiling.argtypes = [_P, _I]
 lib.dms_fusion_get_lazy_stats.argtypes = [_P, C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]
 lib.dms_fusion_get_predict_stats.argtypes = [_P, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+lib.dms_fusion_get_clean_project_stats.argtypes = [_P, C.POINTER(C.c_long), C.POINTER(C.c_long)]
 
 
 class InterMapResult(C.Structure):
@@ -399,6 +404,28 @@ class GlobalModel:
         check(lib.dms_model_clean(self.h, pose.ptr, time, timeIdx, C.byref(indexmap.c), dref, C.byref(k), confThreshold, gptr, gn, timeDelta,
                                   maxDepth, int(isFern), None), "dms_model_clean")
         check(lib.dms_stream_sync(None))
+
+    def projectOnly(self, pose, K, maxDepth, confThreshold, time, timeIdx, maxTime, timeDelta, active=True):
+        """The project pass of a splat prediction alone, into self.zbuf (cleared first); returns the raw 64-bit cells (column-major)."""
+        k = _cam(K)
+        self.zbuf.upload(np.full(self.width * self.height, Z_CLEAR, np.uint64))
+        check(lib.dms_splat_project_only(self.h, pose.ptr, C.byref(k), maxDepth, confThreshold, time, timeIdx, maxTime, timeDelta,
+                                         int(bool(active)), C.c_void_p(self.zbuf.ptr), None), "dms_splat_project_only")
+        check(lib.dms_stream_sync(None))
+        return self.zbuf.download(np.uint64, self.width * self.height)
+
+    def cleanProject(self, pose, time, timeIdx, indexmap, K, confThreshold, timeDelta, maxDepth, projConfThreshold, projTime, projMaxTime,
+                     projTimeDelta, active=True):
+        """clean() whose scatter pass also projects the new map (dms_model_clean_project) into self.zbuf (cleared first); returns
+        (raw 64-bit cells, whether the scatter carried the projection)."""
+        k = _cam(K)
+        self.zbuf.upload(np.full(self.width * self.height, Z_CLEAR, np.uint64))
+        took = C.c_int(0)
+        check(lib.dms_model_clean_project(self.h, pose.ptr, time, timeIdx, C.byref(indexmap.c), C.byref(k), confThreshold, timeDelta, maxDepth,
+                                          projConfThreshold, projTime, projMaxTime, projTimeDelta, int(bool(active)),
+                                          C.c_void_p(self.zbuf.ptr), C.byref(took), None), "dms_model_clean_project")
+        check(lib.dms_stream_sync(None))
+        return self.zbuf.download(np.uint64, self.width * self.height), bool(took.value)
 
     def renderPointCloud(self, mvp, threshold, drawUnstable, drawNormals, drawColors, drawPoints, drawWindow, drawTimes,
                          drawContributions, time, timeIdx, timeDelta, clusters=None, drawClusters=False, cluster_colors=None,
@@ -722,6 +749,12 @@ class ElasticFusion:
         e, d, m, st = C.c_int(0), C.c_long(0), C.c_long(0), C.c_long(0)
         check(lib.dms_fusion_get_lazy_stats(self.h, C.byref(e), C.byref(d), C.byref(m), C.byref(st)), "dms_fusion_get_lazy_stats")
         return {"eager": bool(e.value), "deferred": int(d.value), "materialised": int(m.value), "stale": int(st.value)}
+
+    def cleanProjectStats(self):
+        """fused_clean_projection: {fused, separate} cleans of the frame step so far (dms_fusion_get_clean_project_stats)"""
+        a, b = C.c_long(0), C.c_long(0)
+        check(lib.dms_fusion_get_clean_project_stats(self.h, C.byref(a), C.byref(b)), "dms_fusion_get_clean_project_stats")
+        return {"fused": int(a.value), "separate": int(b.value)}
 
     def predictStats(self):
         """fused_model_prediction: {fused, plain} tracking predictions so far (dms_fusion_get_predict_stats)"""

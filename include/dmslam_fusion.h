@@ -161,6 +161,19 @@ int dms_model_clean(dms_model* m, const dms_pose_block* pose_dev, int time, int 
                     const dms_indexmap_out* indexmap, const dms_image2d* depth_synth, const dms_camera* cam,
                     float confThreshold, const float* graph_host, int graph_nodes, int timeDelta, float maxDepth,
                     int isFern, dms_stream s);
+/* dms_model_clean without a deformation graph whose scatter pass also runs the project pass of a splat prediction of the map it
+ * writes, from the same pose, camera and time slot, into the CLEAN column-major z-buffer `zbuf` (W x H cells, all 0xFF..FF; key =
+ * depth24 << 32 | surfel id): proj* / active are dms_splat_predict's confThreshold, time, maxTime, timeDelta and active.  The map,
+ * the count and every cell are the same bits as dms_model_clean followed by dms_splat_project_only.  *projected (may be NULL): 1
+ * when the scatter carried the projection, 0 when the clean ran in suffix mode (dms_model_set_clean_suffix_min) and the two were
+ * launched one after the other. */
+int dms_model_clean_project(dms_model* m, const dms_pose_block* pose_dev, int time, int timeIdx, const dms_indexmap_out* indexmap,
+                            const dms_camera* cam, float confThreshold, int timeDelta, float maxDepth, float projConfThreshold,
+                            int projTime, int projMaxTime, int projTimeDelta, int active, unsigned long long* zbuf, int* projected,
+                            dms_stream s);
+/* The project pass of dms_splat_predict alone, into a CLEAN z-buffer (see above); nothing is resolved. */
+int dms_splat_project_only(dms_model* m, const dms_pose_block* pose_dev, const dms_camera* cam, float maxDepth, float confThreshold,
+                           int time, int timeIdx, int maxTime, int timeDelta, int active, unsigned long long* zbuf, dms_stream s);
 
 /* G10 fill_{vertex,normal,rgb}.frag (FillIn::{vertex,normal,image}, Shaders/FillIn.cpp:65-190) */
 int dms_fill_in(const dms_predict_out* existing, const dms_image2d* depth_filtered_u16, const dms_image2d* rgba,
@@ -284,6 +297,14 @@ typedef struct dms_fusion_params {
    * poses, results, the map, the tracker's buffers and every image a caller can ask for are the same bits either way.
    * 0: resolve, then model pyramid.  DMS_FUSED_MODEL_PREDICTION=0 / 1 in the environment overrides the field (A/B runs). */
   int fused_model_prediction;
+  /* 1 (default): on a fusing frame whose final prediction is deferred (lazy_final_prediction: all it launches is the project pass
+   * of the next frame's tracking prediction), the clean's scatter pass runs that project pass itself: each survivor is projected
+   * by the thread that has just stored it, under its new id, instead of being read back from the map by a launch of its own.  Not
+   * taken when the clean runs in suffix mode (dms_model_set_clean_suffix_min) or applies a deformation graph; those frames, and
+   * every frame that renders its final prediction, launch as before.  Poses, results, the map and every image a caller can ask
+   * for are the same bits either way.  0: clean, then project.  DMS_FUSED_CLEAN_PROJECTION=0 / 1 in the environment overrides the
+   * field (A/B runs). */
+  int fused_clean_projection;
 } dms_fusion_params;
 
 void dms_fusion_default_params(dms_fusion_params* p, int width, int height, float fx, float fy, float cx, float cy);
@@ -361,6 +382,9 @@ int dms_fusion_get_lazy_stats(dms_fusion* f, int* eager, long* deferred, long* m
 /* fused_model_prediction: tracking predictions so far that went straight into the tracker's model pyramid (fused) and that were
  * rendered as images for the model pyramid kernel (plain).  Either pointer may be NULL. */
 int dms_fusion_get_predict_stats(dms_fusion* f, long* fused, long* plain);
+/* fused_clean_projection: cleans of the frame step so far whose scatter carried the next tracking prediction's project pass (fused)
+ * and those that ran alone (separate).  Either pointer may be NULL. */
+int dms_fusion_get_clean_project_stats(dms_fusion* f, long* fused, long* separate);
 /* Test hook for fused_associate: on = the frame's second index map does not hand the association's z-buffer back empty, so the next
  * fusing frame finds it in use and clears it itself - the path an error return between a frame's two index maps leaves behind. */
 int dms_fusion_debug_keep_assoc_zbuf(dms_fusion* f, int on);
