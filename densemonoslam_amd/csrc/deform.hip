@@ -422,6 +422,65 @@ __device__ __forceinline__ int slot_with(unsigned pk, unsigned v) {
   return s;
 }
 
+// ---- what both assemblies (band and row envelope) compute alike ------------------------------------------------------------------------
+// What the regularisation rows give entry (p, q) of block (i, jn) of A = J^T J, jn <= i and p % 3 == q % 3
+__device__ __forceinline__ double reg_entry(const float* gi, const float* nodes4, int i, int jn, int N, int p, int q) {
+  double acc = 0.0;
+  if (jn == i) {
+    for (int s = 0; s < K; ++s) {  // the edges i -> its neighbours
+      double c4[4];
+      reg_coeffs(gi, nodes4 + 4 * neighbour(i, N, s), c4);
+      acc += coeff_at(c4, p) * coeff_at(c4, q);
+    }
+    if (p >= 9 && q == p)  // the edges of other nodes (enabled or not) that end in i: -sqrt(wReg) each
+      for (int j2 = max(0, i - K); j2 <= min(N - 1, i + K); ++j2)
+        for (int s = 0; s < K; ++s)
+          if (j2 != i && neighbour(j2, N, s) == i) acc += (-SQRT_WREG) * (-SQRT_WREG);
+  } else if (i - jn <= K) {
+    const float* gj = nodes4 + 4 * jn;
+    for (int s = 0; s < K; ++s) {
+      if (q >= 9 && neighbour(i, N, s) == jn) {  // edge i -> jn
+        double c4[4];
+        reg_coeffs(gi, gj, c4);
+        acc += coeff_at(c4, p) * (-c4[3]);
+      }
+      if (p >= 9 && neighbour(jn, N, s) == i) {  // edge jn -> i
+        double c4[4];
+        reg_coeffs(gj, gi, c4);
+        acc += (-c4[3]) * coeff_at(c4, q);
+      }
+    }
+  }
+  return acc;
+}
+
+// Thread t < 6 fills row t of the rotation rows' Jacobian of one node (6 x 9, dense)
+__device__ __forceinline__ void load_rot_jacobian(double (*s_J)[9], const float* rot_i, int t) {
+  if (t >= ROT_ROWS) return;
+  int c[6];
+  double v[6];
+  for (int q = 0; q < 9; ++q) s_J[t][q] = 0.0;
+  const int m = rot_jacobian(rot_i, t, c, v);
+  for (int k = 0; k < m; ++k) s_J[t][c[k]] = v[k];
+}
+
+// -g at unknown p of node i = e0 + b without the constraints: the rotation rows, the node's own edges, the edges that end in it
+__device__ __forceinline__ double gradient_reg(const Dev& d, const double (*s_J)[9], int i, int b, int N, int p) {
+  double sum = 0.0;
+  if (p < 9)
+    for (int r = 0; r < ROT_ROWS; ++r) sum += s_J[r][p] * d.resid[ROT_ROWS * b + r];
+  for (int s = 0; s < K; ++s) {
+    double c4[4];
+    reg_coeffs(d.nodes4 + 4 * i, d.nodes4 + 4 * neighbour(i, N, s), c4);
+    sum += coeff_at(c4, p) * d.resid[d.edge_row[4 * i + s] + p % 3];
+  }
+  if (p >= 9)
+    for (int j2 = max(0, i - K); j2 <= min(N - 1, i + K); ++j2)
+      for (int s = 0; s < K; ++s)
+        if (j2 != i && neighbour(j2, N, s) == i) sum += (-SQRT_WREG) * d.resid[d.edge_row[4 * j2 + s] + (p - 9)];
+  return sum;
+}
+
 // The part of A = J^T J that the regularisation and constraint rows give: block row b (node i = e0 + b), blocks (i, i-19 .. i).
 // An entry at unknown p of a node lies in the row of component p % 3, so only entries with p % 3 == q % 3 meet in a row.
 __global__ __launch_bounds__(256) void k_assemble_const(Dev d, int P) {
@@ -442,31 +501,7 @@ __global__ __launch_bounds__(256) void k_assemble_const(Dev d, int P) {
     const int jn = i - (BW - jb);
     double acc = 0.0;
     if (jn >= e0 && (p % 3) == (q % 3)) {
-      if (jn == i) {
-        for (int s = 0; s < K; ++s) {  // the edges i -> its neighbours
-          double c4[4];
-          reg_coeffs(gi, d.nodes4 + 4 * neighbour(i, N, s), c4);
-          acc += coeff_at(c4, p) * coeff_at(c4, q);
-        }
-        if (p >= 9 && q == p)  // the edges of other nodes (enabled or not) that end in i: -sqrt(wReg) each
-          for (int j2 = max(0, i - K); j2 <= min(N - 1, i + K); ++j2)
-            for (int s = 0; s < K; ++s)
-              if (j2 != i && neighbour(j2, N, s) == i) acc += (-SQRT_WREG) * (-SQRT_WREG);
-      } else if (i - jn <= K) {
-        const float* gj = d.nodes4 + 4 * jn;
-        for (int s = 0; s < K; ++s) {
-          if (q >= 9 && neighbour(i, N, s) == jn) {  // edge i -> jn
-            double c4[4];
-            reg_coeffs(gi, gj, c4);
-            acc += coeff_at(c4, p) * (-c4[3]);
-          }
-          if (p >= 9 && neighbour(jn, N, s) == i) {  // edge jn -> i
-            double c4[4];
-            reg_coeffs(gj, gi, c4);
-            acc += (-c4[3]) * coeff_at(c4, q);
-          }
-        }
-      }
+      acc = reg_entry(gi, d.nodes4, i, jn, N, p, q);
       for (int c = 0; c < cnt; ++c) {  // the constraints that touch i, in pool order
         const unsigned pk = s_pk[c];
         const int t = slot_with(pk, (unsigned)jb + 1u);
@@ -493,13 +528,7 @@ __global__ __launch_bounds__(256) void k_iter_assemble(Dev d, int P) {
   int* s_l = s_dyn;
   unsigned* s_pk = (unsigned*)(s_dyn + P);
   const int cnt = compact_touching(d, P, i, e0, s_l, s_pk, s_w);
-  if (t < ROT_ROWS) {
-    int c[6];
-    double v[6];
-    for (int q = 0; q < 9; ++q) s_J[t][q] = 0.0;
-    const int m = rot_jacobian(d.rot + 9 * i, t, c, v);
-    for (int k = 0; k < m; ++k) s_J[t][c[k]] = v[k];
-  }
+  load_rot_jacobian(s_J, d.rot + 9 * i, t);
   __syncthreads();
   const double* in = d.Ac + (size_t)b * NVAR * ROWLEN;
   double* out = d.Ab + (size_t)b * NVAR * ROWLEN;
@@ -523,24 +552,108 @@ __global__ __launch_bounds__(256) void k_iter_assemble(Dev d, int P) {
   __syncthreads();
   if (t < NVAR) {
     const int p = t;
-    double sum = 0.0;
-    if (p < 9)
-      for (int r = 0; r < ROT_ROWS; ++r) sum += s_J[r][p] * d.resid[ROT_ROWS * b + r];
-    for (int s = 0; s < K; ++s) {
-      double c4[4];
-      reg_coeffs(d.nodes4 + 4 * i, d.nodes4 + 4 * neighbour(i, N, s), c4);
-      sum += coeff_at(c4, p) * d.resid[d.edge_row[4 * i + s] + p % 3];
-    }
-    if (p >= 9)
-      for (int j2 = max(0, i - K); j2 <= min(N - 1, i + K); ++j2)
-        for (int s = 0; s < K; ++s)
-          if (j2 != i && neighbour(j2, N, s) == i) sum += (-SQRT_WREG) * d.resid[d.edge_row[4 * j2 + s] + (p - 9)];
+    double sum = gradient_reg(d, s_J, i, b, N, p);
     for (int grp = 0; grp < GROUPS; ++grp) sum += s_part[grp][p];
     d.g[b * NVAR + p] = -sum;
   }
 }
 
 __device__ __forceinline__ double shfl_d(double v, int lane) { return __shfl(v, lane); }
+
+// ---- the steps of a block column that both solvers (band and row envelope) take alike -------------------------------------------------
+// The first wave on the diagonal block of column k, (p, q) at Dk[p * ld + q]: lane r < 12 holds row r of the block; L L^T = D by
+// columns, then L y = g_k.  L goes to Dk and s_L, y to gk and s_y.  diag0k: the block's diagonal as assembled.  True (in every
+// lane) when a pivot failed.
+__device__ __forceinline__ bool chol_diag_block(double* Dk, int ld, const double* diag0k, double* gk, double (*s_L)[NVAR], double* s_y, int lane) {
+  const int r = lane < NVAR ? lane : 0;
+  double row[NVAR];
+#pragma unroll
+  for (int q = 0; q < NVAR; ++q) row[q] = Dk[r * ld + q];
+  double self = 1.0;
+  bool bad = false;
+#pragma unroll
+  for (int c = 0; c < NVAR; ++c) {
+    const double dcc = shfl_d(row[c], c);
+    // a pivot at or below 2^-40 of its diagonal entry (NaN included) holds no bit worth dividing by: singular
+    if (!(dcc > 0x1p-40 * diag0k[c])) bad = true;
+    const double dd = sqrt(dcc);
+    const double lc = lane == c ? dd : row[c] / dd;
+    row[c] = lc;
+    if (lane == c) self = dd;
+#pragma unroll
+    for (int q = c + 1; q < NVAR; ++q) {
+      const double lqc = shfl_d(lc, q);
+      row[q] -= lc * lqc;  // used by lanes >= q only
+    }
+  }
+  const double gr = gk[r];
+  double acc = 0.0, yv = 0.0;
+#pragma unroll
+  for (int c = 0; c < NVAR; ++c) {
+    const double yc = shfl_d((gr - acc) / self, c);
+    if (lane == c) yv = yc;
+    acc += row[c] * yc;
+  }
+  if (lane < NVAR) {
+#pragma unroll
+    for (int q = 0; q < NVAR; ++q) {
+      const double v = q <= lane ? row[q] : 0.0;
+      s_L[lane][q] = v;
+      Dk[lane * ld + q] = v;
+    }
+    s_y[lane] = yv;
+    gk[lane] = yv;
+  }
+  return bad;
+}
+
+// One scalar row a of the panel: x = a L_kk^-T into x and over a; returns x . y_k, which the caller takes off the row's entry of g
+__device__ __forceinline__ double panel_row_solve(double* a, const double (*s_L)[NVAR], const double* s_y, double x[NVAR]) {
+  double dot = 0.0;
+#pragma unroll
+  for (int q = 0; q < NVAR; ++q) {
+    double v = a[q];
+#pragma unroll
+    for (int m = 0; m < q; ++m) v -= x[m] * s_L[q][m];
+    x[q] = v / s_L[q][q];
+  }
+#pragma unroll
+  for (int q = 0; q < NVAR; ++q) {
+    a[q] = x[q];
+    dot += x[q] * s_y[q];
+  }
+  return dot;
+}
+
+// The first wave's L_kk^T x = rhs: lane c < 12 holds column c of L_kk; returns that lane's entry of x.  rhs is gk less the `parts`
+// partial sums of s_red, in order (the band's sums over the panel below the block; the envelope's column sweep has taken them off
+// g already and passes none).  It is formed here and not by the caller so that the loads of the block stand before the band's chain
+// of 64 subtractions and are in flight while it runs.
+__device__ __forceinline__ double back_diag_block(const double* Dk, int ld, const double* gk, const double (*s_red)[NVAR], int parts, int lane) {
+  const int c0 = lane < NVAR ? lane : 0;
+  double col[NVAR];
+#pragma unroll
+  for (int m = 0; m < NVAR; ++m) col[m] = m >= c0 ? Dk[m * ld + c0] : 0.0;
+  const double self = Dk[c0 * ld + c0];
+  double rhs = gk[c0];
+  for (int part = 0; part < parts; ++part) rhs -= s_red[part][c0];
+  double acc = 0.0, xv = 0.0;
+#pragma unroll
+  for (int c = NVAR - 1; c >= 0; --c) {
+    const double xc = shfl_d((rhs - acc) / self, c);
+    if (lane == c) xv = xc;
+    acc += col[c] * xc;
+  }
+  return xv;
+}
+
+// The exit of a solve whose factorisation met a bad pivot (one thread); k_finalize / k_gfinalize reset the graph on this status
+__device__ __forceinline__ void fail_singular(Hdr* h) {
+  h->status = DMS_DEFORM_SINGULAR;
+  h->optimised = 0;
+  h->done = 1;
+  h->iterations += 1;
+}
 
 // Banded block Cholesky of Ab in place and both substitutions; delta = A^-1 g.  One workgroup.
 __global__ __launch_bounds__(1024) void k_solve(Dev d) {
@@ -571,68 +684,17 @@ __global__ __launch_bounds__(1024) void k_solve(Dev d) {
     const int nb = min(BW, E - 1 - k);
     double* Dk = Ab + (size_t)k * NVAR * ROWLEN + BW * NVAR;  // the diagonal block: (p, q) at Dk[p * ROWLEN + q]
     if (t < 64) {
-      // lane r < 12 holds row r of the block; L L^T = D by columns, then L y = g_k
-      const int r = lane < NVAR ? lane : 0;
-      double row[NVAR];
-#pragma unroll
-      for (int q = 0; q < NVAR; ++q) row[q] = Dk[r * ROWLEN + q];
-      double self = 1.0;
-      bool bad = false;
-#pragma unroll
-      for (int c = 0; c < NVAR; ++c) {
-        const double dcc = shfl_d(row[c], c);
-        // a pivot at or below 2^-40 of its diagonal entry (NaN included) holds no bit worth dividing by: singular
-        if (!(dcc > 0x1p-40 * d.diag0[k * NVAR + c])) bad = true;
-        const double dd = sqrt(dcc);
-        const double lc = lane == c ? dd : row[c] / dd;
-        row[c] = lc;
-        if (lane == c) self = dd;
-#pragma unroll
-        for (int q = c + 1; q < NVAR; ++q) {
-          const double lqc = shfl_d(lc, q);
-          row[q] -= lc * lqc;  // used by lanes >= q only
-        }
-      }
-      const double gr = g[k * NVAR + r];
-      double acc = 0.0, yv = 0.0;
-#pragma unroll
-      for (int c = 0; c < NVAR; ++c) {
-        const double yc = shfl_d((gr - acc) / self, c);
-        if (lane == c) yv = yc;
-        acc += row[c] * yc;
-      }
-      if (lane < NVAR) {
-#pragma unroll
-        for (int q = 0; q < NVAR; ++q) {
-          const double v = q <= lane ? row[q] : 0.0;
-          s_L[lane][q] = v;
-          Dk[lane * ROWLEN + q] = v;
-        }
-        s_y[lane] = yv;
-        g[k * NVAR + lane] = yv;
-      }
+      const bool bad = chol_diag_block(Dk, ROWLEN, d.diag0 + k * NVAR, g + k * NVAR, s_L, s_y, lane);
       if (bad && lane == 0) s_bad = 1;
     }
     __syncthreads();
     if (s_bad) break;
     if (t < nb * NVAR) {  // the panel: row (i, p) of L_ik = A_ik L_kk^-T, and g_i -= L_ik y_k
       const int i = k + 1 + t / NVAR, p = t % NVAR;
-      double* a = Ab + ((size_t)i * NVAR + p) * ROWLEN + (BW - (i - k)) * NVAR;
       double x[NVAR];
-      double dot = 0.0;
+      const double dot = panel_row_solve(Ab + ((size_t)i * NVAR + p) * ROWLEN + (BW - (i - k)) * NVAR, s_L, s_y, x);
 #pragma unroll
-      for (int q = 0; q < NVAR; ++q) {
-        double v = a[q];
-#pragma unroll
-        for (int m = 0; m < q; ++m) v -= x[m] * s_L[q][m];
-        x[q] = v / s_L[q][q];
-      }
-#pragma unroll
-      for (int q = 0; q < NVAR; ++q) {
-        a[q] = x[q];
-        s_P[t][q] = x[q];
-        dot += x[q] * s_y[q];
-      }
+      for (int q = 0; q < NVAR; ++q) s_P[t][q] = x[q];
       g[i * NVAR + p] -= dot;
     }
     __syncthreads();
@@ -671,12 +733,7 @@ __global__ __launch_bounds__(1024) void k_solve(Dev d) {
     __syncthreads();
   }
   if (s_bad) {
-    if (t == 0) {
-      h->status = DMS_DEFORM_SINGULAR;
-      h->optimised = 0;
-      h->done = 1;
-      h->iterations += 1;
-    }
+    if (t == 0) fail_singular(h);
     return;
   }
   for (int k = E - 1; k >= 0; --k) {  // L^T x = y
@@ -692,21 +749,8 @@ __global__ __launch_bounds__(1024) void k_solve(Dev d) {
       s_red[part][q] = acc;
     }
     __syncthreads();
-    if (t < 64) {  // lane c < 12 holds column c of L_kk
-      const int c0 = lane < NVAR ? lane : 0;
-      double col[NVAR];
-#pragma unroll
-      for (int m = 0; m < NVAR; ++m) col[m] = m >= c0 ? Dk[m * ROWLEN + c0] : 0.0;
-      const double self = Dk[c0 * ROWLEN + c0];
-      double rhs = g[k * NVAR + c0];
-      for (int part = 0; part < 64; ++part) rhs -= s_red[part][c0];
-      double acc = 0.0, xv = 0.0;
-#pragma unroll
-      for (int c = NVAR - 1; c >= 0; --c) {
-        const double xc = shfl_d((rhs - acc) / self, c);
-        if (lane == c) xv = xc;
-        acc += col[c] * xc;
-      }
+    if (t < 64) {
+      const double xv = back_diag_block(Dk, ROWLEN, g + k * NVAR, s_red, 64, lane);
       if (lane < NVAR) g[k * NVAR + lane] = xv;
     }
     __syncthreads();
@@ -990,13 +1034,7 @@ __global__ __launch_bounds__(256) void k_gassemble(Dev d, int P, int n_relative)
       if (s_l[c] >> 20) s_far[n++] = s_l[c];
     s_nfar = n;
   }
-  if (t < ROT_ROWS) {
-    int c[6];
-    double v[6];
-    for (int q = 0; q < 9; ++q) s_J[t][q] = 0.0;
-    const int m = rot_jacobian(d.rot + 9 * i, t, c, v);
-    for (int k = 0; k < m; ++k) s_J[t][c[k]] = v[k];
-  }
+  load_rot_jacobian(s_J, d.rot + 9 * i, t);
   __syncthreads();
   for (int c = t; c < cnt; c += 256) {
     const int l = s_l[c] & 0xffff;
@@ -1015,31 +1053,7 @@ __global__ __launch_bounds__(256) void k_gassemble(Dev d, int P, int n_relative)
     const int p = e / len, cc = e % len, jb = fb + cc / NVAR, q = cc % NVAR, jn = e0 + jb;
     double acc = 0.0;
     if ((p % 3) == (q % 3)) {
-      if (jn == i) {
-        for (int s = 0; s < K; ++s) {
-          double c4[4];
-          reg_coeffs(gi, d.nodes4 + 4 * neighbour(i, N, s), c4);
-          acc += coeff_at(c4, p) * coeff_at(c4, q);
-        }
-        if (p >= 9 && q == p)
-          for (int j2 = max(0, i - K); j2 <= min(N - 1, i + K); ++j2)
-            for (int s = 0; s < K; ++s)
-              if (j2 != i && neighbour(j2, N, s) == i) acc += (-SQRT_WREG) * (-SQRT_WREG);
-      } else if (i - jn <= K) {
-        const float* gj = d.nodes4 + 4 * jn;
-        for (int s = 0; s < K; ++s) {
-          if (q >= 9 && neighbour(i, N, s) == jn) {
-            double c4[4];
-            reg_coeffs(gi, gj, c4);
-            acc += coeff_at(c4, p) * (-c4[3]);
-          }
-          if (p >= 9 && neighbour(jn, N, s) == i) {
-            double c4[4];
-            reg_coeffs(gj, gi, c4);
-            acc += (-c4[3]) * coeff_at(c4, q);
-          }
-        }
-      }
+      acc = reg_entry(gi, d.nodes4, i, jn, N, p, q);
       const bool far = b - jb > BW;  // a block the band solver has not: absolute constraints and pins have nothing there
       const int* lst = far ? s_far : s_l;
       const int nl = far ? (s_has[jb] ? s_nfar : 0) : cnt;
@@ -1056,18 +1070,7 @@ __global__ __launch_bounds__(256) void k_gassemble(Dev d, int P, int n_relative)
   }
   if (t < NVAR) {
     const int p = t;
-    double sum = 0.0;
-    if (p < 9)
-      for (int r = 0; r < ROT_ROWS; ++r) sum += s_J[r][p] * d.resid[ROT_ROWS * b + r];
-    for (int s = 0; s < K; ++s) {
-      double c4[4];
-      reg_coeffs(gi, d.nodes4 + 4 * neighbour(i, N, s), c4);
-      sum += coeff_at(c4, p) * d.resid[d.edge_row[4 * i + s] + p % 3];
-    }
-    if (p >= 9)
-      for (int j2 = max(0, i - K); j2 <= min(N - 1, i + K); ++j2)
-        for (int s = 0; s < K; ++s)
-          if (j2 != i && neighbour(j2, N, s) == i) sum += (-SQRT_WREG) * d.resid[d.edge_row[4 * j2 + s] + (p - 9)];
+    double sum = gradient_reg(d, s_J, i, b, N, p);
     for (int c = 0; c < cnt; ++c) {
       const int l = s_l[c] & 0xffff;
       sum += coeff_at(d.mc + 32 * l + 4 * ((s_l[c] >> 16) & 7), p) * d.resid[d.con_row[l] + p % 3];
@@ -1094,45 +1097,8 @@ __global__ __launch_bounds__(1024) void k_gsolve(Dev d) {
   for (int k = 0; k < E; ++k) {
     const int ldk = (k + 1) * NVAR;
     double* Dk = L + tri_row(k, 0) + (size_t)k * NVAR;  // the diagonal block: (p, q) at Dk[p * ldk + q]
-    if (t < 64) {  // as the band solver's: lane r < 12 holds row r; L L^T = D by columns, then L y = g_k
-      const int r = lane < NVAR ? lane : 0;
-      double row[NVAR];
-#pragma unroll
-      for (int q = 0; q < NVAR; ++q) row[q] = Dk[r * ldk + q];
-      double self = 1.0;
-      bool bad = false;
-#pragma unroll
-      for (int c = 0; c < NVAR; ++c) {
-        const double dcc = shfl_d(row[c], c);
-        if (!(dcc > 0x1p-40 * d.diag0[k * NVAR + c])) bad = true;
-        const double dd = sqrt(dcc);
-        const double lc = lane == c ? dd : row[c] / dd;
-        row[c] = lc;
-        if (lane == c) self = dd;
-#pragma unroll
-        for (int q = c + 1; q < NVAR; ++q) {
-          const double lqc = shfl_d(lc, q);
-          row[q] -= lc * lqc;
-        }
-      }
-      const double gr = g[k * NVAR + r];
-      double acc = 0.0, yv = 0.0;
-#pragma unroll
-      for (int c = 0; c < NVAR; ++c) {
-        const double yc = shfl_d((gr - acc) / self, c);
-        if (lane == c) yv = yc;
-        acc += row[c] * yc;
-      }
-      if (lane < NVAR) {
-#pragma unroll
-        for (int q = 0; q < NVAR; ++q) {
-          const double v = q <= lane ? row[q] : 0.0;
-          s_L[lane][q] = v;
-          Dk[lane * ldk + q] = v;
-        }
-        s_y[lane] = yv;
-        g[k * NVAR + lane] = yv;
-      }
+    if (t < 64) {
+      const bool bad = chol_diag_block(Dk, ldk, d.diag0 + k * NVAR, g + k * NVAR, s_L, s_y, lane);
       if (bad && lane == 0) s_bad = 1;
     }
     // the panel of column k, ascending: rows below k whose envelope reaches it
@@ -1151,21 +1117,8 @@ __global__ __launch_bounds__(1024) void k_gsolve(Dev d) {
     __syncthreads();
     for (int r = t; r < m * NVAR; r += 1024) {  // row (i, p) of L_ik = A_ik L_kk^-T, and g_i -= L_ik y_k
       const int i = s_rows[r / NVAR], p = r % NVAR;
-      double* a = L + tri_row(i, p) + (size_t)k * NVAR;
       double x[NVAR];
-      double dot = 0.0;
-#pragma unroll
-      for (int q = 0; q < NVAR; ++q) {
-        double v = a[q];
-#pragma unroll
-        for (int m2 = 0; m2 < q; ++m2) v -= x[m2] * s_L[q][m2];
-        x[q] = v / s_L[q][q];
-      }
-#pragma unroll
-      for (int q = 0; q < NVAR; ++q) {
-        a[q] = x[q];
-        dot += x[q] * s_y[q];
-      }
+      const double dot = panel_row_solve(L + tri_row(i, p) + (size_t)k * NVAR, s_L, s_y, x);
       g[i * NVAR + p] -= dot;
     }
     __syncthreads();
@@ -1203,31 +1156,14 @@ __global__ __launch_bounds__(1024) void k_gsolve(Dev d) {
     __syncthreads();
   }
   if (s_bad) {
-    if (t == 0) {
-      h->status = DMS_DEFORM_SINGULAR;
-      h->optimised = 0;
-      h->done = 1;
-      h->iterations += 1;
-    }
+    if (t == 0) fail_singular(h);
     return;
   }
   for (int k = E - 1; k >= 0; --k) {  // L^T x = y: x_k, then y_j -= L_kj^T x_k along row k's envelope
     const int ldk = (k + 1) * NVAR;
     const double* Dk = L + tri_row(k, 0) + (size_t)k * NVAR;
     if (t < 64) {
-      const int c0 = lane < NVAR ? lane : 0;
-      double col[NVAR];
-#pragma unroll
-      for (int m2 = 0; m2 < NVAR; ++m2) col[m2] = m2 >= c0 ? Dk[m2 * ldk + c0] : 0.0;
-      const double self = Dk[c0 * ldk + c0];
-      const double rhs = g[k * NVAR + c0];
-      double acc = 0.0, xv = 0.0;
-#pragma unroll
-      for (int c = NVAR - 1; c >= 0; --c) {
-        const double xc = shfl_d((rhs - acc) / self, c);
-        if (lane == c) xv = xc;
-        acc += col[c] * xc;
-      }
+      const double xv = back_diag_block(Dk, ldk, g + k * NVAR, nullptr, 0, lane);
       if (lane < NVAR) {
         g[k * NVAR + lane] = xv;
         s_y[lane] = xv;
