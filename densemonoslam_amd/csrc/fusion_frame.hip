@@ -315,8 +315,7 @@ struct dms_fusion {
   // the frame after it reuses.
   struct LazyRecord {
     bool pending = false;
-    float confidence = 0.f, maxDepth = 0.f;
-    int tick = 0, timeIdx = 0, timeDelta = 0;
+    MapPass pass;                         // that frame's final prediction, but for the pose: lazy_pose holds it
     int pass_geom = 0, pass_rgb = 0;      // lost / lost || frameToFrameRGB of that frame (a lost camera is never deferred: 0 / ftf)
     dms_image2d depth_filtered, rgba;     // the fill-in's inputs: that frame's live image set
     dms_model* model = nullptr;
@@ -486,6 +485,90 @@ static bool final_prediction_deferred(const dms_fusion* f, bool one_call, const 
          !f->armed_now.block && !f->p.nid_keyframing && !f->p.local_loop_closure && !f->p.hybrid_loops && !f->lost && !f->cur_bootstrap;
 }
 
+// The frame's ACTIVE splat pass at its current pose and tick (ElasticFusion::predict), at the threshold `confidence`; the index
+// maps, the fuse and the clean of the frame take the same record with their own time delta.
+static MapPass frame_pass(const dms_fusion* f, float confidence) {
+  MapPass p;
+  p.pose = &f->state->cur;
+  p.cam = &f->cam;
+  p.maxDepth = f->p.maxDepthProcessed;
+  p.time = f->tick;
+  p.timeIdx = f->p.timeIdx;
+  p.timeDelta = f->p.timeDelta;
+  p.confThreshold = confidence;
+  p.maxTime = f->tick;
+  p.active = 1;
+  return p;
+}
+static MapPass frame_pass_delta(const dms_fusion* f, int timeDeltaEff) {
+  MapPass p = frame_pass(f, f->p.confidence);
+  p.timeDelta = timeDeltaEff;
+  return p;
+}
+// combinedPredict(pose, ..., confidenceThreshold, 0, id, tick - timeDelta, timeDelta, INACTIVE): the part of the map last seen
+// more than timeDelta frames ago, from `pose`
+static MapPass inactive_pass(const dms_fusion* f, const dms_pose_block* pose) {
+  MapPass p = frame_pass(f, f->p.confidence);
+  p.pose = pose;
+  p.time = 0;
+  p.maxTime = f->tick - f->p.timeDelta;
+  p.active = 0;
+  return p;
+}
+
+// a prediction into `out` through the frame's z-buffer, which every draw finds and leaves clean
+static SplatPrediction frame_prediction(dms_fusion* f, dms_predict_out* out) {
+  SplatPrediction sp;
+  sp.zbuf = f->zbuf;
+  sp.zclean = 1;
+  sp.out = out;
+  return sp;
+}
+
+// a prediction's (or fill-in's) vertex, normal and colour images as a source of the tracker's model pyramids
+static ModelImages prediction_images(const dms_predict_out& p) {
+  ModelImages i;
+  i.vertex = p.vertex.data;
+  i.normal = p.normal.data;
+  i.image = p.image.data;
+  return i;
+}
+
+// the frame's index map: column-major images, through the clean z-buffer
+static IndexMapTargets frame_index_map(dms_fusion* f) {
+  IndexMapTargets t;
+  t.zbuf = f->zbuf;
+  t.zclean = 1;
+  t.out = &f->imap;
+  t.transposed = 1;
+  return t;
+}
+// a clean over that index map with the frame's threshold; the new count also goes into the frame's result block
+static CleanInputs frame_clean(dms_fusion* f, const float* graph_host, const float* graph_dev, int graph_nodes) {
+  CleanInputs in;
+  in.im = &f->imap;
+  in.confThreshold = f->p.confidence;
+  in.graph_host = graph_host;
+  in.graph_dev = graph_dev;
+  in.graph_nodes = graph_nodes;
+  in.transposed = 1;
+  in.count_out2 = &f->state->surfels;
+  return in;
+}
+
+// the fill-in of f->pred into f->fill from a frame's live images
+static FillInputs frame_fill(dms_fusion* f, const dms_image2d* depth_filtered, const dms_image2d* rgba, int pass_geom, int pass_rgb) {
+  FillInputs in;
+  in.ex = &f->pred;
+  in.depth = depth_filtered;
+  in.rgba = rgba;
+  in.cam = &f->cam;
+  in.pass_geom = pass_geom;
+  in.pass_rgb = pass_rgb;
+  in.out = &f->fill;
+  return in;
+}
+
 int predict_body(dms_fusion* f, hipStream_t s, Predict kind, const PredictOpts& o) {
   const bool dense_test = kind == Predict::tracking;  // ElasticFusion.cpp:165-167
   int rc;
@@ -493,10 +576,15 @@ int predict_body(dms_fusion* f, hipStream_t s, Predict kind, const PredictOpts& 
   FillArgs fa;
   const FillArgs* fused = nullptr;
   // passthrough = lost (geometry), lost || frameToFrameRGB (image) (ElasticFusion.cpp:704-712)
+  FillInputs fi = frame_fill(f, &f->depth_filtered, &f->rgba, f->lost ? 1 : 0, (f->lost || f->p.frameToFrameRGB) ? 1 : 0);
   // (the frame's last fill-in also copies the result block into its pinned host slot)
-  if ((rc = fill_args(&f->pred, &f->depth_filtered, &f->rgba, &f->cam, f->lost ? 1 : 0, (f->lost || f->p.frameToFrameRGB) ? 1 : 0, &f->fill,
-                      o.state_mirror ? f->state : nullptr, o.state_mirror, (int)sizeof(FrameState), dense_test ? &f->state->fill_in : nullptr, &fa)))
-    return rc;
+  if (o.state_mirror) {
+    fi.mirror.src = f->state;
+    fi.mirror.dst = o.state_mirror;
+    fi.mirror.bytes = (int)sizeof(FrameState);
+  }
+  if (dense_test) fi.dense_flag = &f->state->fill_in;
+  if ((rc = fill_args(fi, &fa))) return rc;
   // the denseEnough decision of a fused pass is taken by the tracker's model pyramid kernel from the counters filled here
   // (fill.hpp): only when that kernel follows, i.e. with hybrid tracking
   f->dense_by_counters = false;
@@ -525,12 +613,16 @@ int predict_body(dms_fusion* f, hipStream_t s, Predict kind, const PredictOpts& 
     bool done = false;
     DMS_REQUIRE(!o.model || (fused && dense_test), "the fused prediction + model pass needs the fused fill-in of a tracking prediction");
     if (o.model) f->dense_by_counters = false;  // (every block of that pass takes the decision itself)
+    const MapPass pass = frame_pass(f, o.confidence);
+    SplatPrediction sp = frame_prediction(f, &f->pred);  // the fill-in and its riders on the resolve pass when fused
+    sp.fill = fused;
+    sp.init = fused ? o.track_init : nullptr;
+    sp.pm = o.model;
     if (kind == Predict::tracking && f->pre_valid) {
       if (tracking_resolves_shared(f, o.have_prior)) {
-        if ((rc = splat_predict(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, o.confidence, f->tick, f->p.timeIdx, f->tick,
-                                f->p.timeDelta, 1, f->zbuf2, &f->pred, nullptr, 1, s, nullptr, nullptr, 1, fused, fused ? o.track_init : nullptr,
-                                o.model)))
-          return rc;
+        sp.zbuf = f->zbuf2;
+        sp.mode = SplatMode::resolve_only;
+        if ((rc = splat_predict(f->model, pass, sp, s))) return rc;
         done = true;
       } else if ((rc = clear_zbuf(f->zbuf2, W * H, s))) {  // stale: the resolve that would have cleaned it never runs
         return rc;
@@ -539,7 +631,10 @@ int predict_body(dms_fusion* f, hipStream_t s, Predict kind, const PredictOpts& 
     }
     if (!done) {
       const int next_tick = f->lost ? f->tick : f->tick + 1;  // (the tick advances at the end of the frame unless the camera is lost)
-      const float second[3] = {0.7f, (float)next_tick, (float)next_tick};
+      MapPass next = pass;  // the next frame's tracking prediction: this pass but for the cull's threshold and times
+      next.confThreshold = 0.7f;
+      next.time = next_tick;
+      next.maxTime = next_tick;
       // (a projection rendered ahead for this camera's next frame is stale by then when other cameras fuse into the same map: not rendered)
       const bool dual = kind == Predict::final && final_prediction_dual(f);
       DMS_REQUIRE(!o.projected_by_clean || (dual && !f->pre_valid), "the clean projects for a deferred final prediction only");
@@ -564,17 +659,10 @@ int predict_body(dms_fusion* f, hipStream_t s, Predict kind, const PredictOpts& 
       DMS_REQUIRE(!o.projected_by_clean || defer, "the clean projects for a deferred final prediction only");
       if (defer) {
         // (fused_clean_projection: the clean's scatter has projected, with this rider - process_frame_end; the record is kept here)
-        const ProjectRider rider = final_rider(f, o.state_mirror);
-        if (!o.projected_by_clean && (rc = splat_project_only(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, second[0], next_tick,
-                                                              f->p.timeIdx, next_tick, f->p.timeDelta, 1, f->zbuf2, s, &rider)))
-          return rc;
+        if (!o.projected_by_clean && (rc = splat_project_only(f->model, next, f->zbuf2, final_rider(f, o.state_mirror), s))) return rc;
         dms_fusion::LazyRecord& r = f->lazy;
         r.pending = true;
-        r.confidence = o.confidence;
-        r.maxDepth = f->p.maxDepthProcessed;
-        r.tick = f->tick;
-        r.timeIdx = f->p.timeIdx;
-        r.timeDelta = f->p.timeDelta;
+        r.pass = pass;
         r.pass_geom = 0;
         r.pass_rgb = f->p.frameToFrameRGB ? 1 : 0;
         r.depth_filtered = f->depth_filtered;
@@ -583,10 +671,14 @@ int predict_body(dms_fusion* f, hipStream_t s, Predict kind, const PredictOpts& 
         r.version = f->model->version;
         r.stream = s;
         f->lazy_deferred += 1;
-      } else if ((rc = splat_predict(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, o.confidence, f->tick, f->p.timeIdx, f->tick,
-                              f->p.timeDelta, 1, f->zbuf, &f->pred, nullptr, 1, s, dual ? second : nullptr, dual ? f->zbuf2 : nullptr, 0,
-                              fused, fused ? o.track_init : nullptr, o.model)))
-        return rc;
+      } else {
+        if (dual) {
+          sp.mode = SplatMode::dual;
+          sp.second = SplatSecond{next.confThreshold, next.time, next.maxTime};
+          sp.zbuf2 = f->zbuf2;
+        }
+        if ((rc = splat_predict(f->model, pass, sp, s))) return rc;
+      }
       if (dual) {
         f->pre_valid = true;
         f->pre_tick = next_tick;
@@ -596,9 +688,7 @@ int predict_body(dms_fusion* f, hipStream_t s, Predict kind, const PredictOpts& 
   }
   if (!fused) {
     StageTimer t(f->clock, s, "fill_in", f->profiling);
-    if ((rc = fill_in(&f->pred, &f->depth_filtered, &f->rgba, &f->cam, f->lost ? 1 : 0, (f->lost || f->p.frameToFrameRGB) ? 1 : 0, &f->fill,
-                      s, o.state_mirror ? f->state : nullptr, o.state_mirror, (int)sizeof(FrameState), dense_test ? &f->state->fill_in : nullptr)))
-      return rc;
+    if ((rc = fill_in(fa, s))) return rc;
   }
   return DMS_OK;
 }
@@ -636,12 +726,14 @@ int materialise_final_prediction(dms_fusion* f, hipStream_t consumer, bool consu
   if (r.model != f->model || r.version != f->model->version) f->lazy_stale += 1;
   int rc;
   FillArgs fa;
-  if ((rc = fill_args(&f->pred, &r.depth_filtered, &r.rgba, &f->cam, r.pass_geom, r.pass_rgb, &f->fill, nullptr, nullptr, 0, nullptr, &fa))) return rc;
+  if ((rc = fill_args(frame_fill(f, &r.depth_filtered, &r.rgba, r.pass_geom, r.pass_rgb), &fa))) return rc;
   {
     StageTimer t(f->clock, r.stream, "predict", f->profiling);
-    if ((rc = splat_predict(f->model, f->lazy_pose, &f->cam, r.maxDepth, r.confidence, r.tick, r.timeIdx, r.tick, r.timeDelta, 1, f->zbuf, &f->pred,
-                            nullptr, 1, r.stream, nullptr, nullptr, 0, &fa, nullptr)))
-      return rc;
+    MapPass pass = r.pass;
+    pass.pose = f->lazy_pose;
+    SplatPrediction sp = frame_prediction(f, &f->pred);
+    sp.fill = &fa;
+    if ((rc = splat_predict(f->model, pass, sp, r.stream))) return rc;
   }
   if (!consumer_known || consumer != r.stream) DMS_HIP(hipStreamSynchronize(r.stream));
   return DMS_OK;
@@ -662,13 +754,11 @@ int global_loop_device(dms_fusion* f, const float* orbTcwOld, const float* orbTc
   StageTimer t(f->clock, s, "global_loop", f->profiling);
   const int act = active_new ? 1 : 0;
   // predict(context, rf) with currPose = the ACTIVE pose (:294-296 / :1158-1160): only its vertex map is consumed
-  if ((rc = splat_predict(f->model, f->orb_pose + act, &f->cam, f->p.maxDepthProcessed, f->p.confidence, f->tick, f->p.timeIdx, f->tick,
-                          f->p.timeDelta, 1, f->zbuf, &f->pred, nullptr, 1, s)))
-    return rc;
+  MapPass active = frame_pass(f, f->p.confidence);
+  active.pose = f->orb_pose + act;
+  if ((rc = splat_predict(f->model, active, frame_prediction(f, &f->pred), s))) return rc;
   // combinedPredict(<other pose>, ..., confidenceThreshold, 0, id, tick - timeDelta, timeDelta, INACTIVE) (:299-302 / :1163-1166)
-  if ((rc = splat_predict(f->model, f->orb_pose + (1 - act), &f->cam, f->p.maxDepthProcessed, f->p.confidence, 0, f->p.timeIdx,
-                          f->tick - f->p.timeDelta, f->p.timeDelta, 0, f->zbuf, &f->pred_old, nullptr, 1, s)))
-    return rc;
+  if ((rc = splat_predict(f->model, inactive_pass(f, f->orb_pose + (1 - act)), frame_prediction(f, &f->pred_old), s))) return rc;
   hipLaunchKernelGGL(k_global_loop_constraints, dim3(1), dim3(256), 0, s, (const float4*)f->pred.vertex.data,
                      (const unsigned short*)f->pred_old.time.data, f->p.width, f->p.height, f->p.maxDepthProcessed, f->orb_pose, active_new ? 1 : 0,
                      (int*)f->gloop, (float*)(f->gloop + 256));
@@ -689,39 +779,75 @@ int dms_model_initialise(dms_model* m, const dms_image2d* rgba, const dms_image2
                          int time, int timeIdx, float maxDepth, dms_stream s) {
   return model_initialise(m, rgba, dm, dmf, cam, time, timeIdx, maxDepth, (hipStream_t)s);
 }
+// (the flat C arguments, by name, into the records of internal.hpp)
 int dms_index_map(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, int time, int timeIdx, float maxDepth, int timeDelta,
                   unsigned long long* zbuf, dms_indexmap_out* out, dms_stream s) {
-  return index_map(m, pose, cam, time, timeIdx, maxDepth, timeDelta, zbuf, out, 0, 0, (hipStream_t)s);
+  MapPass pass;
+  pass.pose = pose, pass.cam = cam, pass.maxDepth = maxDepth;
+  pass.time = time, pass.timeIdx = timeIdx, pass.timeDelta = timeDelta;
+  IndexMapTargets t;
+  t.zbuf = zbuf, t.out = out;
+  return index_map(m, pass, t, (hipStream_t)s);
 }
 int dms_splat_predict(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, float maxDepth, float confThreshold, int time,
                       int timeIdx, int maxTime, int timeDelta, int active, unsigned long long* zbuf, dms_predict_out* out, dms_stream s) {
   DMS_REQUIRE(out, "null output");
-  return splat_predict(m, pose, cam, maxDepth, confThreshold, time, timeIdx, maxTime, timeDelta, active, zbuf, out, nullptr, 0, (hipStream_t)s);
+  MapPass pass;
+  pass.pose = pose, pass.cam = cam, pass.maxDepth = maxDepth;
+  pass.time = time, pass.timeIdx = timeIdx, pass.timeDelta = timeDelta;
+  pass.confThreshold = confThreshold, pass.maxTime = maxTime, pass.active = active;
+  SplatPrediction p;
+  p.zbuf = zbuf, p.out = out;
+  return splat_predict(m, pass, p, (hipStream_t)s);
 }
 int dms_splat_depth(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, float maxDepth, float confThreshold, int time,
                     int timeIdx, int maxTime, int timeDelta, unsigned long long* zbuf, dms_image2d* depth, dms_stream s) {
   DMS_REQUIRE(depth, "null output");
-  // synthesizeDepth never sets the `actv` uniform (IndexMap.cpp:370-452): it stays false
-  return splat_predict(m, pose, cam, maxDepth, confThreshold, time, timeIdx, maxTime, timeDelta, 0, zbuf, nullptr, depth, 0, (hipStream_t)s);
+  MapPass pass;  // synthesizeDepth never sets the `actv` uniform (IndexMap.cpp:370-452): `active` stays off
+  pass.pose = pose, pass.cam = cam, pass.maxDepth = maxDepth;
+  pass.time = time, pass.timeIdx = timeIdx, pass.timeDelta = timeDelta;
+  pass.confThreshold = confThreshold, pass.maxTime = maxTime;
+  SplatPrediction p;
+  p.zbuf = zbuf, p.depth_out = depth;
+  return splat_predict(m, pass, p, (hipStream_t)s);
 }
 int dms_model_sample_graph(dms_model* m, int sampleRate, float* rows4_host, int max_rows, int* n, dms_stream s) {
   return model_sample_graph(m, sampleRate, rows4_host, max_rows, n, (hipStream_t)s);
 }
-int dms_model_fuse(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_image2d* rgba, const dms_image2d* dr,
-                   const dms_image2d* drf, const dms_indexmap_out* im, const dms_camera* cam, float depthCutoff, float weighting,
-                   const float* weighting_dev, dms_stream s) {
-  return model_fuse(m, pose, time, timeIdx, rgba, dr, drf, im, cam, depthCutoff, weighting, weighting_dev, 0, (hipStream_t)s);
-}
-int dms_index_project(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, int time, int timeIdx, float maxDepth, int timeDelta,
-                      unsigned long long* zbuf, dms_stream s) {
-  return index_project(m, pose, cam, time, timeIdx, maxDepth, timeDelta, zbuf, 0, (hipStream_t)s);
-}
 int dms_model_fuse_ex(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_image2d* rgba, const dms_image2d* dr,
                       const dms_image2d* drf, const dms_indexmap_out* im, const unsigned long long* zbuf, const dms_camera* cam,
                       float depthCutoff, float weighting, const float* weighting_dev, int defer_update, dms_stream s) {
-  DMS_REQUIRE((im != nullptr) != (zbuf != nullptr), "exactly one of the index map's images and its z-buffer");
-  if (im) return model_fuse(m, pose, time, timeIdx, rgba, dr, drf, im, cam, depthCutoff, weighting, weighting_dev, 0, (hipStream_t)s, defer_update);
-  return model_fuse_zbuf(m, pose, time, timeIdx, rgba, dr, drf, zbuf, cam, depthCutoff, weighting, weighting_dev, (hipStream_t)s, defer_update);
+  MapPass pass;
+  pass.pose = pose, pass.cam = cam, pass.maxDepth = depthCutoff;
+  pass.time = time, pass.timeIdx = timeIdx;
+  FuseInputs in;
+  in.rgba = rgba, in.depth_raw = dr, in.depth_filtered = drf;
+  in.im = im, in.zbuf = zbuf;
+  in.weighting = weighting, in.weighting_dev = weighting_dev;
+  in.defer_update = defer_update;
+  return model_fuse(m, pass, in, (hipStream_t)s);
+}
+int dms_model_fuse(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_image2d* rgba, const dms_image2d* dr,
+                   const dms_image2d* drf, const dms_indexmap_out* im, const dms_camera* cam, float depthCutoff, float weighting,
+                   const float* weighting_dev, dms_stream s) {
+  DMS_REQUIRE(im, "null argument");
+  MapPass pass;
+  pass.pose = pose, pass.cam = cam, pass.maxDepth = depthCutoff;
+  pass.time = time, pass.timeIdx = timeIdx;
+  FuseInputs in;
+  in.rgba = rgba, in.depth_raw = dr, in.depth_filtered = drf;
+  in.im = im;
+  in.weighting = weighting, in.weighting_dev = weighting_dev;
+  return model_fuse(m, pass, in, (hipStream_t)s);
+}
+int dms_index_project(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, int time, int timeIdx, float maxDepth, int timeDelta,
+                      unsigned long long* zbuf, dms_stream s) {
+  MapPass pass;
+  pass.pose = pose, pass.cam = cam, pass.maxDepth = maxDepth;
+  pass.time = time, pass.timeIdx = timeIdx, pass.timeDelta = timeDelta;
+  IndexMapTargets t;
+  t.zbuf = zbuf;
+  return index_project(m, pass, t, (hipStream_t)s);
 }
 int dms_model_apply_pending(dms_model* m, dms_stream s) {
   DMS_REQUIRE(m, "null argument");
@@ -734,29 +860,54 @@ int dms_model_fuse_scratch(dms_model* m, float* slot_pos4, float* slot_col4, flo
 int dms_model_clean(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_indexmap_out* im,
                     const dms_image2d* depth_synth, const dms_camera* cam, float confThreshold, const float* graph_host, int graph_nodes,
                     int timeDelta, float maxDepth, int isFern, dms_stream s) {
-  return model_clean(m, pose, time, timeIdx, im, depth_synth, cam, confThreshold, graph_host, graph_nodes, timeDelta, maxDepth, isFern, 0,
-                     nullptr, (hipStream_t)s);
+  MapPass pass;
+  pass.pose = pose, pass.cam = cam, pass.maxDepth = maxDepth;
+  pass.time = time, pass.timeIdx = timeIdx, pass.timeDelta = timeDelta;
+  CleanInputs in;
+  in.im = im, in.depth_synth = depth_synth;
+  in.confThreshold = confThreshold;
+  in.graph_host = graph_host, in.graph_nodes = graph_nodes;
+  in.isFern = isFern;
+  return model_clean(m, pass, in, (hipStream_t)s);
 }
 int dms_model_clean_project(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_indexmap_out* im, const dms_camera* cam,
                             float confThreshold, int timeDelta, float maxDepth, float projConfThreshold, int projTime, int projMaxTime,
                             int projTimeDelta, int active, unsigned long long* zbuf, int* projected, dms_stream s) {
   DMS_REQUIRE(m && pose && cam && zbuf, "null argument");
-  CleanProjection cp = {maxDepth, projConfThreshold, projTime, projMaxTime, projTimeDelta, active, zbuf, nullptr, 0};
-  if (int rc = model_clean(m, pose, time, timeIdx, im, nullptr, cam, confThreshold, nullptr, 0, timeDelta, maxDepth, 0, 0, nullptr,
-                           (hipStream_t)s, nullptr, &cp))
-    return rc;
+  MapPass pass;
+  pass.pose = pose, pass.cam = cam, pass.maxDepth = maxDepth;
+  pass.time = time, pass.timeIdx = timeIdx, pass.timeDelta = timeDelta;
+  CleanProjection cp;
+  cp.pass = pass;  // the clean's pose, camera, time slot and cut-off
+  cp.pass.time = projTime, cp.pass.timeDelta = projTimeDelta;
+  cp.pass.confThreshold = projConfThreshold, cp.pass.maxTime = projMaxTime, cp.pass.active = active;
+  cp.zbuf = zbuf;
+  CleanInputs in;
+  in.im = im;
+  in.confThreshold = confThreshold;
+  in.project = &cp;
+  if (int rc = model_clean(m, pass, in, (hipStream_t)s)) return rc;
   if (projected) *projected = cp.projected;
   if (cp.projected) return DMS_OK;
-  return splat_project_only(m, pose, cam, maxDepth, projConfThreshold, projTime, timeIdx, projMaxTime, projTimeDelta, active, zbuf,
-                            (hipStream_t)s, nullptr);
+  return splat_project_only(m, cp.pass, zbuf, kNoRider, (hipStream_t)s);
 }
 int dms_splat_project_only(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, float maxDepth, float confThreshold, int time,
                            int timeIdx, int maxTime, int timeDelta, int active, unsigned long long* zbuf, dms_stream s) {
-  return splat_project_only(m, pose, cam, maxDepth, confThreshold, time, timeIdx, maxTime, timeDelta, active, zbuf, (hipStream_t)s, nullptr);
+  MapPass pass;
+  pass.pose = pose, pass.cam = cam, pass.maxDepth = maxDepth;
+  pass.time = time, pass.timeIdx = timeIdx, pass.timeDelta = timeDelta;
+  pass.confThreshold = confThreshold, pass.maxTime = maxTime, pass.active = active;
+  return splat_project_only(m, pass, zbuf, kNoRider, (hipStream_t)s);
 }
 int dms_fill_in(const dms_predict_out* ex, const dms_image2d* d, const dms_image2d* rgba, const dms_camera* cam, int pg, int pr,
                 dms_predict_out* out, dms_stream s) {
-  return fill_in(ex, d, rgba, cam, pg, pr, out, (hipStream_t)s);
+  FillInputs in;
+  in.ex = ex, in.depth = d, in.rgba = rgba, in.cam = cam;
+  in.pass_geom = pg, in.pass_rgb = pr;
+  in.out = out;
+  FillArgs a;
+  if (int rc = fill_args(in, &a)) return rc;
+  return fill_in(a, (hipStream_t)s);
 }
 int dms_resize_nn(const dms_image2d* src, dms_image2d* dst, int elem, dms_stream s) { return resize_nn(src, dst, elem, (hipStream_t)s); }
 
@@ -1333,13 +1484,20 @@ static int track_frame(dms_fusion* f, const float* inPose16, float weightMultipl
     // WARNING (reference): initICP* must be called before initRGB* (ElasticFusion.cpp:172)
     // (the set-up of the tracker call below rides on the pyramid kernel: no launch of its own, DMS_FOLD_TRACK_INIT=0 to compare)
     // (fused_model_prediction: the prediction's kernel has written the model maps - the stage is kept, it encloses no launch)
-    if (!f->model_written &&
-        (rc = odometry_initModel_fused(f->odom, f->pred.vertex.data, f->pred.normal.data, f->pred.image.data, f->fill.vertex.data,
-                                       f->fill.normal.data, f->fill.image.data, &f->state->fill_in, f->p.frameToFrameRGB ? 1 : 0,
-                                       f->state->cur.pose, s, 1,  // (last pyramid step: inside the tracker's first kernel, below)
-                                       f->dense_by_counters ? f->tickets : nullptr, (f->p.width / 20) * (f->p.height / 20),
-                                       f->fold_track_init ? &fold : nullptr)))
-      return rc;
+    if (!f->model_written) {
+      ModelSources src;  // the prediction, or its fill-in where the view is not dense enough
+      src.a = prediction_images(f->pred);
+      src.b = prediction_images(f->fill);
+      src.use_b = &f->state->fill_in;
+      src.force_b_img = f->p.frameToFrameRGB ? 1 : 0;
+      src.pose16 = f->state->cur.pose;
+      ModelHandOver next;
+      next.defer_last_step = 1;  // (last pyramid step: inside the tracker's first kernel, below)
+      if (f->dense_by_counters) next.dense_cnt = f->tickets;
+      next.dense_samples = (f->p.width / 20) * (f->p.height / 20);
+      if (f->fold_track_init) next.fold = &fold;
+      if ((rc = odometry_initModel_fused(f->odom, src, next, s))) return rc;
+    }
     // initICP / initRGB: the live half ran on the prep stream; nextDepth = lastDepth (same source)
     odometry_alias_next_depth(f->odom);
   }
@@ -1383,18 +1541,16 @@ static int local_loop_candidate(dms_fusion* f, hipStream_t s) {
   int rc;
   {
     StageTimer t(f->clock, s, "predict_old", f->profiling);  // combinedPredict(..., 0, id, tick - timeDelta, timeDelta, INACTIVE) (:403-406)
-    if ((rc = splat_predict(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, f->p.confidence, 0, f->p.timeIdx,
-                            f->tick - f->p.timeDelta, f->p.timeDelta, 0, f->zbuf, &f->pred_old, nullptr, 1, s)))
-      return rc;
+    if ((rc = splat_predict(f->model, inactive_pass(f, &f->state->cur), frame_prediction(f, &f->pred_old), s))) return rc;
   }
   {
     StageTimer t(f->clock, s, "loop_init", f->profiling);  // modelToModel().initICPModel / initRGBModel / initICP / initRGB (:409-418)
-    if ((rc = odometry_initModel_fused(f->odom_m2m, f->pred_old.vertex.data, f->pred_old.normal.data, f->pred_old.image.data,
-                                       f->pred_old.vertex.data, f->pred_old.normal.data, f->pred_old.image.data, &f->state->fill_in, 0,
-                                       f->state->cur.pose, s)))
-      return rc;
-    if ((rc = odometry_initLive_fused(f->odom_m2m, f->pred.vertex.data, f->pred.normal.data, f->pred.image.data, &f->state->fill_in, s)))
-      return rc;
+    ModelSources old;  // (one set: whatever the flag holds selects it)
+    old.a = old.b = prediction_images(f->pred_old);
+    old.use_b = &f->state->fill_in;
+    old.pose16 = f->state->cur.pose;
+    if ((rc = odometry_initModel_fused(f->odom_m2m, old, ModelHandOver{}, s))) return rc;
+    if ((rc = odometry_initLive_fused(f->odom_m2m, prediction_images(f->pred), &f->state->fill_in, s))) return rc;
   }
   {
     StageTimer t(f->clock, s, "loop_track", f->profiling);  // getIncrementalTransformation(trans, rot, false, 10, pyramid, fastOdom, false) (:424-425)
@@ -1524,30 +1680,39 @@ int dms_fusion_process_frame_begin(dms_fusion* f, const void* rgb_dev, int rgb_c
 // map's resolve pass hands it back empty.  Same bits in the slots, the winners and everything after them.
 static int index_map_for_fuse(dms_fusion* f, int timeDeltaEff, hipStream_t s) {
   StageTimer t(f->clock, s, "index_map", f->profiling);
-  if (!f->p.fused_associate)
-    return index_map(f->model, &f->state->cur, &f->cam, f->tick, f->p.timeIdx, f->p.maxDepthProcessed, timeDeltaEff, f->zbuf, &f->imap, 1, 1, s);
+  if (!f->p.fused_associate) return index_map(f->model, frame_pass_delta(f, timeDeltaEff), frame_index_map(f), s);
   const bool stale = f->zbuf_assoc_dirty;  // a frame that set it never reached its clearing resolve: clear here
   f->zbuf_assoc_dirty = true;
-  return index_project(f->model, &f->state->cur, &f->cam, f->tick, f->p.timeIdx, f->p.maxDepthProcessed, timeDeltaEff, f->zbuf_assoc,
-                       stale ? 0 : 1, s);
+  IndexMapTargets zb;
+  zb.zbuf = f->zbuf_assoc;
+  zb.zclean = stale ? 0 : 1;
+  return index_project(f->model, frame_pass_delta(f, timeDeltaEff), zb, s);
 }
 
 static int fuse_measurements(dms_fusion* f, hipStream_t s) {
   StageTimer t(f->clock, s, "fuse", f->profiling);
-  // (update pass: inside the next index map)
-  if (f->p.fused_associate)
-    return model_fuse_zbuf(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->rgba, &f->depth_metric, &f->depth_metric_filtered,
-                           f->zbuf_assoc, &f->cam, f->p.maxDepthProcessed, 1.f, &f->state->weighting, s, 1);
-  return model_fuse(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->rgba, &f->depth_metric, &f->depth_metric_filtered, &f->imap,
-                    &f->cam, f->p.maxDepthProcessed, 1.f, &f->state->weighting, 1, s, 1);
+  FuseInputs in;
+  in.rgba = &f->rgba;
+  in.depth_raw = &f->depth_metric;
+  in.depth_filtered = &f->depth_metric_filtered;
+  if (f->p.fused_associate) {
+    in.zbuf = f->zbuf_assoc;
+  } else {
+    in.im = &f->imap;
+    in.transposed = 1;
+  }
+  in.weighting = 1.f;
+  in.weighting_dev = &f->state->weighting;
+  in.defer_update = 1;  // (update pass: inside the next index map)
+  return model_fuse(f->model, frame_pass(f, f->p.confidence), in, s);
 }
 
 static int index_map_for_clean(dms_fusion* f, int timeDeltaEff, hipStream_t s) {
   StageTimer t(f->clock, s, "index_map", f->profiling);
   const bool hand_back = f->p.fused_associate && !f->zbuf_assoc_keep_dirty;
-  if (int rc = index_map(f->model, &f->state->cur, &f->cam, f->tick, f->p.timeIdx, f->p.maxDepthProcessed, timeDeltaEff, f->zbuf, &f->imap, 1,
-                         1, s, hand_back ? f->zbuf_assoc : nullptr))
-    return rc;
+  IndexMapTargets im = frame_index_map(f);
+  if (hand_back) im.zbuf_also = f->zbuf_assoc;
+  if (int rc = index_map(f->model, frame_pass_delta(f, timeDeltaEff), im, s)) return rc;
   if (hand_back) f->zbuf_assoc_dirty = false;
   return DMS_OK;
 }
@@ -1556,8 +1721,15 @@ static int index_map_for_clean(dms_fusion* f, int timeDeltaEff, hipStream_t s) {
 // time stamps to refresh (ElasticFusion.cpp:541-553; synthesizeDepth leaves `actv` false)
 static int synthesise_depth(dms_fusion* f, int timeDeltaEff, hipStream_t s) {
   StageTimer t(f->clock, s, "synth_depth", f->profiling);
-  return splat_predict(f->model, &f->state->cur, &f->cam, f->p.maxDepthProcessed, f->p.confidence, f->tick, f->p.timeIdx,
-                       f->tick - timeDeltaEff, 65535, 0, f->zbuf, nullptr, &f->depth_synth, 1, s);
+  MapPass pass = frame_pass(f, f->p.confidence);
+  pass.maxTime = f->tick - timeDeltaEff;
+  pass.timeDelta = 65535;
+  pass.active = 0;
+  SplatPrediction sp;
+  sp.zbuf = f->zbuf;
+  sp.zclean = 1;
+  sp.depth_out = &f->depth_synth;
+  return splat_predict(f->model, pass, sp, s);
 }
 
 // fused_clean_projection (state_mirror given): the frame's final prediction is deferred (final_prediction_deferred), so all it
@@ -1567,10 +1739,12 @@ static int synthesise_depth(dms_fusion* f, int timeDeltaEff, hipStream_t s) {
 static int clean_map(dms_fusion* f, const float* graph_host, const float* graph_dev, int graph_nodes, int timeDeltaEff, hipStream_t s,
                      void* state_mirror = nullptr, bool* projected = nullptr) {
   StageTimer t(f->clock, s, "clean", f->profiling);
+  const MapPass pass = frame_pass_delta(f, timeDeltaEff);
+  CleanInputs in = frame_clean(f, graph_host, graph_dev, graph_nodes);
   if (!state_mirror || graph_nodes > 0) {
     f->clean_project_separate += 1;
-    return model_clean(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->imap, graph_nodes > 0 ? &f->depth_synth : nullptr, &f->cam,
-                       f->p.confidence, graph_host, graph_nodes, timeDeltaEff, f->p.maxDepthProcessed, 0, 1, &f->state->surfels, s, graph_dev);
+    if (graph_nodes > 0) in.depth_synth = &f->depth_synth;
+    return model_clean(f->model, pass, in, s);
   }
   int rc;
   if (f->pre_valid) {  // (a projection rendered ahead that nothing consumed: predict_body would clear it before projecting)
@@ -1578,11 +1752,14 @@ static int clean_map(dms_fusion* f, const float* graph_host, const float* graph_
     f->pre_valid = false;
   }
   const int next_tick = f->tick + 1;  // (the camera is not lost: predict_body)
-  const ProjectRider rider = final_rider(f, state_mirror);
-  CleanProjection cp = {f->p.maxDepthProcessed, 0.7f, next_tick, next_tick, f->p.timeDelta, 1, f->zbuf2, &rider, 0};
-  if ((rc = model_clean(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->imap, nullptr, &f->cam, f->p.confidence, graph_host, 0, timeDeltaEff,
-                        f->p.maxDepthProcessed, 0, 1, &f->state->surfels, s, graph_dev, &cp)))
-    return rc;
+  CleanProjection cp;
+  cp.pass = frame_pass(f, 0.7f);  // the next frame's tracking prediction, as predict_body forms it
+  cp.pass.time = next_tick;
+  cp.pass.maxTime = next_tick;
+  cp.zbuf = f->zbuf2;
+  cp.rider = final_rider(f, state_mirror);
+  in.project = &cp;
+  if ((rc = model_clean(f->model, pass, in, s))) return rc;
   *projected = cp.projected != 0;
   (cp.projected ? f->clean_project_fused : f->clean_project_separate) += 1;
   return DMS_OK;
@@ -2103,10 +2280,10 @@ static int apply_global_loop_end(dms_fusion* f, const float* graph_host, const f
   // in the reference's order: the prediction images a caller reads afterwards show the map BEFORE this clean
   if ((rc = predict_view(f, f->p.confidence, s))) return rc;
   const int timeDeltaEff = f->p.timeDelta + f->frames_since_fusion;
-  if ((rc = index_map(f->model, &f->state->cur, &f->cam, f->tick, f->p.timeIdx, f->p.maxDepthProcessed, timeDeltaEff, f->zbuf, &f->imap, 1, 1, s)))
-    return rc;
-  return model_clean(f->model, &f->state->cur, f->tick, f->p.timeIdx, &f->imap, nullptr, &f->cam, f->p.confidence, graph_host, graph_nodes,
-                     timeDeltaEff, f->p.maxDepthProcessed, accepted ? 1 : 0, 1, &f->state->surfels, s, graph_dev);
+  if ((rc = index_map(f->model, frame_pass_delta(f, timeDeltaEff), frame_index_map(f), s))) return rc;
+  CleanInputs in = frame_clean(f, graph_host, graph_dev, graph_nodes);
+  in.isFern = accepted ? 1 : 0;
+  return model_clean(f->model, frame_pass_delta(f, timeDeltaEff), in, s);
 }
 
 int dms_relative_transform(const float* recoveryPose16, const float* currPose16, float* out16) {

@@ -853,6 +853,7 @@ __global__ __launch_bounds__(256) void k_clean_scatter_suffix(CleanArgs a, Surfe
       const size_t dst = (size_t)block_offset[b] + rank;
       if (dst < cap) {
         CleanElem v;
+        // (clean_survivor<false> and clean_store spelled out: through the helpers the compiler schedules this kernel differently)
         clean_load(e, M, sp, cap, slot_pos, slot_col, slot_nrm, slot_flag, a.nslots, a.timeIdx, a.planes, v);
         if (v.vt == -2.f) {  // copy_unstable.vert:124-129
           v.col.w = (float)a.time;
@@ -873,16 +874,14 @@ __global__ __launch_bounds__(256) void k_clean_scatter_suffix(CleanArgs a, Surfe
 // ---------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------
-static bool dense_img(const dms_image2d& im, size_t elem, int w, int h) {
-  return im.data && im.cols == w && im.rows == h && im.pitch == (size_t)w * elem;
-}
-
-// im: the index map as images (k_fuse_associate).  zbuf (im null): the column-major z-buffer index_project filled from the map as it is
-// now, at this pose (k_fuse_associate_zbuf); it is left as it was found.
-static int model_fuse_impl(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_image2d* rgba, const dms_image2d* dr,
-                           const dms_image2d* drf, const dms_indexmap_out* im, const unsigned long long* zbuf, const dms_camera* cam,
-                           float depthCutoff, float weighting, const float* weighting_dev, int transposed, hipStream_t s, int defer_update) {
-  DMS_REQUIRE(m && pose && rgba && dr && drf && (im || zbuf) && cam, "null argument");
+int model_fuse(dms_model* m, const MapPass& pass, const FuseInputs& in, hipStream_t s) {
+  const dms_pose_block* const pose = pass.pose;
+  const dms_camera* const cam = pass.cam;
+  const dms_image2d *const rgba = in.rgba, *const dr = in.depth_raw, *const drf = in.depth_filtered;
+  const dms_indexmap_out* const im = in.im;
+  const int time = pass.time, timeIdx = pass.timeIdx;
+  DMS_REQUIRE(m && pose && rgba && dr && drf && cam, "null argument");
+  DMS_REQUIRE((im != nullptr) != (in.zbuf != nullptr), "exactly one of the index map's images and its z-buffer");
   DMS_REQUIRE(!m->pending_update, "a deferred update pass is still pending (index_map applies it)");
   DMS_REQUIRE(timeIdx >= 0 && timeIdx < DMS_MAX_SENSORS, "timeIdx out of range");
   if (m->live_planes < timeIdx + 1) m->live_planes = timeIdx + 1;  // (the update pass stamps times[timeIdx])
@@ -906,13 +905,13 @@ static int model_fuse_impl(dms_model* m, const dms_pose_block* pose, int time, i
   a.cy = cam->cy;
   a.icx = (float)(1.0 / (double)cam->fx);
   a.icy = (float)(1.0 / (double)cam->fy);
-  a.maxDepth = depthCutoff;
+  a.maxDepth = pass.maxDepth;
   a.timef = (float)time;
-  a.weighting = weighting;
-  a.weighting_dev = weighting_dev;
+  a.weighting = in.weighting;
+  a.weighting_dev = in.weighting_dev;
   a.time = time;
   a.timeIdx = timeIdx;
-  a.transposed = transposed ? 1 : 0;
+  a.transposed = (in.zbuf || in.transposed) ? 1 : 0;  // (the z-buffer is column-major)
   const int slot_w = (W + 1) / 2;
   if (im) {
     const int tiles = ((m->slot_h + 7) / 8) * ((slot_w + 1) / 2);  // 2 x 8 candidates per wave, four lanes each
@@ -920,11 +919,11 @@ static int model_fuse_impl(dms_model* m, const dms_pose_block* pose, int time, i
     hipLaunchKernelGGL(k_fuse_associate, g, b, 0, s, a, m->slot_pos, m->slot_col, m->slot_nrm, m->slot_best, m->slot_flag, m->winner, slot_w);
   } else {
     const int tiles = ((m->slot_h + kTileJ - 1) / kTileJ) * ((slot_w + kTileI - 1) / kTileI);
-    hipLaunchKernelGGL(k_fuse_associate_zbuf, dim3(tiles), dim3(kTileThreads), 0, s, a, zbuf, m->buf[m->cur], m->cap, m->slot_pos, m->slot_col,
+    hipLaunchKernelGGL(k_fuse_associate_zbuf, dim3(tiles), dim3(kTileThreads), 0, s, a, in.zbuf, m->buf[m->cur], m->cap, m->slot_pos, m->slot_col,
                        m->slot_nrm, m->slot_best, m->slot_flag, m->winner, slot_w);
   }
   DMS_CHECK_LAUNCH();
-  if (defer_update) {  // the caller's next index_map applies the winners while it projects: one pass and one launch less
+  if (in.defer_update) {  // the caller's next index_map applies the winners while it projects: one pass and one launch less
     m->pending_update = true;
     m->pending_time = time;
     m->pending_timeIdx = timeIdx;
@@ -935,21 +934,6 @@ static int model_fuse_impl(dms_model* m, const dms_pose_block* pose, int time, i
   }
   m->version += 1;
   return DMS_OK;
-}
-
-int model_fuse(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_image2d* rgba, const dms_image2d* dr,
-               const dms_image2d* drf, const dms_indexmap_out* im, const dms_camera* cam, float depthCutoff, float weighting,
-               const float* weighting_dev, int transposed, hipStream_t s, int defer_update) {
-  DMS_REQUIRE(im, "null argument");
-  return model_fuse_impl(m, pose, time, timeIdx, rgba, dr, drf, im, nullptr, cam, depthCutoff, weighting, weighting_dev, transposed, s,
-                         defer_update);
-}
-
-int model_fuse_zbuf(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_image2d* rgba, const dms_image2d* dr,
-                    const dms_image2d* drf, const unsigned long long* zbuf, const dms_camera* cam, float depthCutoff, float weighting,
-                    const float* weighting_dev, hipStream_t s, int defer_update) {
-  DMS_REQUIRE(zbuf, "null argument");
-  return model_fuse_impl(m, pose, time, timeIdx, rgba, dr, drf, nullptr, zbuf, cam, depthCutoff, weighting, weighting_dev, 1, s, defer_update);
 }
 
 // The association's outputs as the update pass and the clean will read them, for inspection (tests): any pointer may be null
@@ -979,57 +963,56 @@ int model_flush_pending(dms_model* m, hipStream_t s) {
   return DMS_OK;
 }
 
-int model_clean(dms_model* m, const dms_pose_block* pose, int time, int timeIdx, const dms_indexmap_out* im, const dms_image2d* depth_synth,
-                const dms_camera* cam, float confThreshold, const float* graph_host, int graph_nodes, int timeDelta, float maxDepth,
-                int isFern, int transposed, unsigned* count_out2, hipStream_t s, const float* graph_dev, CleanProjection* project) {
+int model_clean(dms_model* m, const MapPass& pass, const CleanInputs& in, hipStream_t s) {
+  const dms_pose_block* const pose = pass.pose;
+  const dms_camera* const cam = pass.cam;
+  const dms_indexmap_out* const im = in.im;
+  const int timeIdx = pass.timeIdx, graph_nodes = in.graph_nodes;
+  unsigned* const count_out2 = in.count_out2;
+  CleanProjection* const project = in.project;
   DMS_REQUIRE(m && !m->pending_update, "a deferred update pass is still pending (index_map applies it)");
   DMS_REQUIRE(m && pose && im && cam, "null argument");
   DMS_REQUIRE(timeIdx >= 0 && timeIdx < DMS_MAX_SENSORS, "timeIdx out of range");
   const int W = m->width, H = m->height;
   DMS_REQUIRE(dense_img(im->index, 4, W, H) && dense_img(im->vertConf, 16, W, H) && dense_img(im->colorTime, 16, W, H),
               "dense W×H index-map images required");
-  if (project) {  // (the conditions of splat_project_only)
+  if (project) {
     DMS_REQUIRE(project->zbuf, "null argument");
-    DMS_REQUIRE(fabsf(cam->fx) > 1e-18f && fabsf(cam->fx) < 1e18f && fabsf(cam->fy) > 1e-18f && fabsf(cam->fy) < 1e18f &&
-                    project->maxDepth > 1e-18f && project->maxDepth < 1e18f,
-                "focal lengths and depth cut-off must be finite, non-zero and within 1e-18 .. 1e18");
-    const ProjectRider* rider = project->rider;
-    DMS_REQUIRE(!rider || (rider->mirror_words >= 0 && rider->mirror_words <= 256 && rider->copy_words >= 0 && rider->copy_words <= 256 &&
-                           (rider->mirror_words == 0 || (rider->mirror_src && rider->mirror_dst)) &&
-                           (rider->copy_words == 0 || (rider->copy_src && rider->copy_dst))),
-                "a rider copies at most 256 dwords (one block)");
+    DMS_REQUIRE(project->pass.pose == pose && project->pass.cam == cam && project->pass.timeIdx == timeIdx,
+                "the projection a clean carries is rendered from the clean's pose, camera and time slot");
+    if (int rc = check_map_pass(m, project->pass, project->rider)) return rc;
   }
   if (graph_nodes >= m->max_nodes) {  // assert(graph.size() / 16 < MAX_NODES), GlobalModel.cpp:703
     set_error("dms_model_clean: %d deformation nodes exceed the limit %d", graph_nodes, m->max_nodes);
     return DMS_ERR_CAPACITY;
   }
   if (graph_nodes > 0) {  // graph_dev: the table is in device memory already (the deformation solver's)
-    DMS_REQUIRE(graph_host || graph_dev, "null graph");
-    DMS_HIP(hipMemcpyAsync(m->nodes, graph_dev ? graph_dev : graph_host, (size_t)graph_nodes * 16 * sizeof(float),
-                           graph_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    DMS_REQUIRE(in.graph_host || in.graph_dev, "null graph");
+    DMS_HIP(hipMemcpyAsync(m->nodes, in.graph_dev ? in.graph_dev : in.graph_host, (size_t)graph_nodes * 16 * sizeof(float),
+                           in.graph_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
   }
   CleanArgs a;
   a.pose = pose;
   a.index = (const unsigned*)im->index.data;
   a.vertConf = (const float4*)im->vertConf.data;
   a.colorTime = (const float4*)im->colorTime.data;
-  a.depth_synth = (depth_synth && depth_synth->data) ? (const float*)depth_synth->data : nullptr;
+  a.depth_synth = (in.depth_synth && in.depth_synth->data) ? (const float*)in.depth_synth->data : nullptr;
   a.cols = W;
   a.rows = H;
   a.cx = cam->cx;
   a.cy = cam->cy;
   a.fx = cam->fx;
   a.fy = cam->fy;
-  a.confThreshold = confThreshold;
-  a.maxDepth = maxDepth;
-  a.time = time;
+  a.confThreshold = in.confThreshold;
+  a.maxDepth = pass.maxDepth;
+  a.time = pass.time;
   a.timeIdx = timeIdx;
-  a.timeDelta = timeDelta;
-  a.isFern = isFern;
+  a.timeDelta = pass.timeDelta;
+  a.isFern = in.isFern;
   a.nodes = graph_nodes;
   a.node_table = m->nodes;
   a.nslots = m->slots;
-  a.transposed = transposed ? 1 : 0;
+  a.transposed = in.transposed ? 1 : 0;
   const size_t upper = m->count_upper + (size_t)m->slots;
   const int nb = (int)((upper + kScanChunk - 1) / kScanChunk);
   // suffix mode pays one more launch: worth it once the map is large
@@ -1059,14 +1042,10 @@ int model_clean(dms_model* m, const dms_pose_block* pose, int time, int timeIdx,
                        m->slot_nrm, m->slot_flag, m->keep, m->block_offset, dst, m->clean_first);
   } else if (project && graph_nodes == 0) {
     ProjArgs pa;
-    fill_proj(pa, m, pose, cam, project->maxDepth, project->time, timeIdx, project->timeDelta);
-    pa.confThreshold = project->confThreshold;
-    pa.maxTime = project->maxTime;
-    pa.actv = project->active ? 1 : 0;
-    const ProjectRider no_rider = {nullptr, nullptr, 0, nullptr, nullptr, 0};
+    fill_proj(pa, m, project->pass);
     hipLaunchKernelGGL(k_clean_scatter_project, dim3(nb), dim3(256), 0, s, a, src, m->cap, m->d_count, m->slot_pos, m->slot_col, m->slot_nrm,
                        m->slot_flag, m->keep, m->block_offset, dst, inline_scan ? m->block_count : (const unsigned*)nullptr, m->d_count_alt,
-                       count_out2, pa, project->zbuf, project->rider ? *project->rider : no_rider);
+                       count_out2, pa, project->zbuf, project->rider);
     project->projected = 1;
   } else
     hipLaunchKernelGGL(k_clean_scatter, dim3(nb), dim3(256), 0, s, a, src, m->cap, m->d_count, m->slot_pos, m->slot_col, m->slot_nrm,

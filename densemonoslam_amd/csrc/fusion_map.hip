@@ -418,7 +418,7 @@ __global__ __launch_bounds__(256) void k_index_resolve(ProjArgs a, SurfelPlanes 
   for (int p = xcd_block(blockIdx.x, gridDim.x, a.xcd) * blockDim.x + threadIdx.x; p < n; p += blockDim.x * gridDim.x) {
     const unsigned long long key = zbuf[p];
     if (clear_after) zbuf[p] = kZClear;  // hand the z-buffer back empty: the next draw needs no clear launch
-    // (the frame step: the z-buffer its fused association read without clearing, index_project / model_fuse_zbuf; null elsewhere)
+    // (the frame step: the z-buffer its fused association read without clearing, index_project / model_fuse; null elsewhere)
     if (zbuf_also) zbuf_also[p] = kZClear;
     unsigned id;
     float4 vc, ct, nr;
@@ -457,10 +457,6 @@ static int surfel_grid(size_t upper) {
   return (int)b;
 }
 
-static bool dense_img(const dms_image2d& im, size_t elem, int w, int h) {
-  return im.data && im.cols == w && im.rows == h && im.pitch == (size_t)w * elem;
-}
-
 // The projection half of index_map: zbuf (empty on entry when zclean) receives the depth-tested surfel ids
 static int index_project_launch(dms_model* m, const ProjArgs& a, unsigned long long* zbuf, int zclean, hipStream_t s) {
   const int n = m->width * m->height;
@@ -479,41 +475,34 @@ static int index_project_launch(dms_model* m, const ProjArgs& a, unsigned long l
   return DMS_OK;
 }
 
-int index_map(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, int time, int timeIdx, float maxDepth, int timeDelta,
-              unsigned long long* zbuf, dms_indexmap_out* out, int transposed, int zclean, hipStream_t s, unsigned long long* zbuf_also) {
-  // zclean: the caller's z-buffer is empty on entry and must be handed back empty (the resolve pass
-  // clears what it reads), so a chain of draws needs no clear launches.  zbuf_also: a second z-buffer the
-  // resolve pass empties on the way (same size; what index_project filled for model_fuse_zbuf), or null
-  DMS_REQUIRE(m && pose && cam && zbuf && out, "null argument");
-  DMS_REQUIRE(timeIdx >= 0 && timeIdx < DMS_MAX_SENSORS, "timeIdx out of range");
+int index_map(dms_model* m, const MapPass& pass, const IndexMapTargets& t, hipStream_t s) {
+  dms_indexmap_out* const out = t.out;
+  DMS_REQUIRE(m && pass.pose && pass.cam && t.zbuf && out, "null argument");
+  DMS_REQUIRE(pass.timeIdx >= 0 && pass.timeIdx < DMS_MAX_SENSORS, "timeIdx out of range");
   const int W = m->width, H = m->height;
   DMS_REQUIRE(dense_img(out->index, 4, W, H) && dense_img(out->vertConf, 16, W, H) && dense_img(out->colorTime, 16, W, H) &&
                   dense_img(out->normRad, 16, W, H),
               "index-map targets must be dense W×H");
   ProjArgs a;
-  fill_proj(a, m, pose, cam, maxDepth, time, timeIdx, timeDelta);
-  a.transposed = transposed ? 1 : 0;
+  fill_proj(a, m, pass);
+  a.transposed = t.transposed ? 1 : 0;
   const int n = W * H;
-  int rc = index_project_launch(m, a, zbuf, zclean, s);
+  int rc = index_project_launch(m, a, t.zbuf, t.zclean, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_index_resolve, dim3(min((n + 255) / 256, 2048)), dim3(256), 0, s, a, m->buf[m->cur], m->cap, zbuf,
+  hipLaunchKernelGGL(k_index_resolve, dim3(min((n + 255) / 256, 2048)), dim3(256), 0, s, a, m->buf[m->cur], m->cap, t.zbuf,
                      (unsigned*)out->index.data, (float4*)out->vertConf.data, (float4*)out->colorTime.data, (float4*)out->normRad.data,
-                     zclean, zbuf_also);
+                     t.zclean, t.zbuf_also);
   DMS_CHECK_LAUNCH();
   return DMS_OK;
 }
 
-// index_map without its resolve pass: the z-buffer alone, column-major (cell of pixel (x, y) at x * rows + y), for the one reader
-// that needs no images (fusion_fuse.hip model_fuse_zbuf).  Nobody clears it here: the caller hands it to a later index_map as
-// zbuf_also, or clears it itself.
-int index_project(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, int time, int timeIdx, float maxDepth, int timeDelta,
-                  unsigned long long* zbuf, int zclean, hipStream_t s) {
-  DMS_REQUIRE(m && pose && cam && zbuf, "null argument");
-  DMS_REQUIRE(timeIdx >= 0 && timeIdx < DMS_MAX_SENSORS, "timeIdx out of range");
+int index_project(dms_model* m, const MapPass& pass, const IndexMapTargets& t, hipStream_t s) {
+  DMS_REQUIRE(m && pass.pose && pass.cam && t.zbuf, "null argument");
+  DMS_REQUIRE(pass.timeIdx >= 0 && pass.timeIdx < DMS_MAX_SENSORS, "timeIdx out of range");
   ProjArgs a;
-  fill_proj(a, m, pose, cam, maxDepth, time, timeIdx, timeDelta);
+  fill_proj(a, m, pass);
   a.transposed = 1;
-  return index_project_launch(m, a, zbuf, zclean, s);
+  return index_project_launch(m, a, t.zbuf, t.zclean, s);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1046,20 +1035,34 @@ __global__ __launch_bounds__(NT) void k_predict_model(ProjArgs a, SurfelPlanes s
   }
 }
 
-int splat_predict(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, float maxDepth, float confThreshold, int time,
-                  int timeIdx, int maxTime, int timeDelta, int active, unsigned long long* zbuf, dms_predict_out* out,
-                  dms_image2d* depth_out, int zclean, hipStream_t s, const float* second_conf_time_maxtime, unsigned long long* zbuf2,
-                  int resolve_only, const FillArgs* fill, const TrackInitArgs* init, const PredictModelArgs* pm) {
-  DMS_REQUIRE(m && pose && cam && zbuf, "null argument");
+int check_map_pass(const dms_model* m, const MapPass& pass, const ProjectRider& rider) {
+  DMS_REQUIRE(m && pass.pose && pass.cam, "null argument");
+  DMS_REQUIRE(!m->pending_update, "a deferred update pass is still pending (index_map applies it)");
+  DMS_REQUIRE(pass.timeIdx >= 0 && pass.timeIdx < DMS_MAX_SENSORS, "timeIdx out of range");
+  // (the project pass divides by fx, fy and 2 maxDepth through exact_arith.hpp: normal numbers far from the ends of the exponent range)
+  const float fx = pass.cam->fx, fy = pass.cam->fy;
+  DMS_REQUIRE(fabsf(fx) > 1e-18f && fabsf(fx) < 1e18f && fabsf(fy) > 1e-18f && fabsf(fy) < 1e18f && pass.maxDepth > 1e-18f && pass.maxDepth < 1e18f,
+              "focal lengths and depth cut-off must be finite, non-zero and within 1e-18 .. 1e18");
+  DMS_REQUIRE(rider.mirror_words >= 0 && rider.mirror_words <= 256 && rider.copy_words >= 0 && rider.copy_words <= 256 &&
+                  (rider.mirror_words == 0 || (rider.mirror_src && rider.mirror_dst)) && (rider.copy_words == 0 || (rider.copy_src && rider.copy_dst)),
+              "a rider copies at most 256 dwords (one block)");
+  return DMS_OK;
+}
+
+int splat_predict(dms_model* m, const MapPass& pass, const SplatPrediction& p, hipStream_t s) {
+  const FillArgs* const fill = p.fill;
+  const TrackInitArgs* const init = p.init;
+  const PredictModelArgs* const pm = p.pm;
+  dms_predict_out* const out = p.out;
+  dms_image2d* const depth_out = p.depth_out;
+  unsigned long long* const zbuf = p.zbuf;
+  const int zclean = p.zclean;
+  DMS_REQUIRE(m && zbuf && (p.mode != SplatMode::dual || p.zbuf2), "null argument");
   DMS_REQUIRE(!pm || (fill && !depth_out && fill->sample_mask && fill->mirror_words == 0 && !fill->thumb_block && zclean && pm->sample_cells && pm->n_cells == pm->samples &&
                       pm->samples == (m->width / 20) * (m->height / 20) && pm->samples > 0 && pm->flag_out && (pm->threads == 256 || pm->threads == 512 || pm->threads == 1024)),
               "the fused prediction + model pass takes the place of the fused resolve + fill-in pass of a tracking prediction only");
   DMS_REQUIRE(!init || init->blocks == 0 || pm, "the tracker set-up rides on the fused prediction + model pass only");
-  DMS_REQUIRE(!m->pending_update, "a deferred update pass is still pending (index_map applies it)");
-  DMS_REQUIRE(timeIdx >= 0 && timeIdx < DMS_MAX_SENSORS, "timeIdx out of range");
-  // (the project pass divides by fx, fy and 2 maxDepth through exact_arith.hpp: normal numbers far from the ends of the exponent range)
-  DMS_REQUIRE(fabsf(cam->fx) > 1e-18f && fabsf(cam->fx) < 1e18f && fabsf(cam->fy) > 1e-18f && fabsf(cam->fy) < 1e18f && maxDepth > 1e-18f && maxDepth < 1e18f,
-              "focal lengths and depth cut-off must be finite, non-zero and within 1e-18 .. 1e18");
+  if (int rc = check_map_pass(m, pass, kNoRider)) return rc;
   const int W = m->width, H = m->height;
   if (depth_out)
     DMS_REQUIRE(dense_img(*depth_out, 4, W, H), "depth target must be dense W×H f32");
@@ -1068,28 +1071,24 @@ int splat_predict(dms_model* m, const dms_pose_block* pose, const dms_camera* ca
                     dense_img(out->time, 2, W, H),
                 "prediction targets must be dense W×H");
   ProjArgs a;
-  fill_proj(a, m, pose, cam, maxDepth, time, timeIdx, timeDelta);
-  a.confThreshold = confThreshold;
-  a.maxTime = maxTime;
-  a.actv = active ? 1 : 0;
+  fill_proj(a, m, pass);
   const int n = W * H;
   if (!zclean) {
     hipLaunchKernelGGL(k_clear_zbuf, dim3(min((n + 255) / 256, 2048)), dim3(256), 0, s, zbuf, n);
     DMS_CHECK_LAUNCH();
   }
-  SplatSecond b2 = {0.f, 0, 0};
-  const ProjectRider no_rider = {nullptr, nullptr, 0, nullptr, nullptr, 0};
-  if (resolve_only) {
-    // the z-buffer was filled by an earlier dual pass with exactly these parameters
-  } else if (second_conf_time_maxtime && zbuf2) {
-    b2.confThreshold = second_conf_time_maxtime[0];
-    b2.time = (int)second_conf_time_maxtime[1];
-    b2.maxTime = (int)second_conf_time_maxtime[2];
-    hipLaunchKernelGGL(k_splat_project<true>, dim3(surfel_grid(m->count_upper)), dim3(256), 0, s, a, m->buf[m->cur], m->cap, m->d_count, zbuf, b2,
-                       zbuf2, no_rider);
-  } else {
-    hipLaunchKernelGGL(k_splat_project<false>, dim3(surfel_grid(m->count_upper)), dim3(256), 0, s, a, m->buf[m->cur], m->cap, m->d_count, zbuf,
-                       b2, (unsigned long long*)nullptr, no_rider);
+  const SplatSecond no_second = {0.f, 0, 0};
+  switch (p.mode) {
+    case SplatMode::resolve_only:
+      break;
+    case SplatMode::dual:
+      hipLaunchKernelGGL(k_splat_project<true>, dim3(surfel_grid(m->count_upper)), dim3(256), 0, s, a, m->buf[m->cur], m->cap, m->d_count, zbuf,
+                         p.second, p.zbuf2, kNoRider);
+      break;
+    case SplatMode::project_resolve:
+      hipLaunchKernelGGL(k_splat_project<false>, dim3(surfel_grid(m->count_upper)), dim3(256), 0, s, a, m->buf[m->cur], m->cap, m->d_count, zbuf,
+                         no_second, (unsigned long long*)nullptr, kNoRider);
+      break;
   }
   DMS_CHECK_LAUNCH();
   const FillArgs no_fill = {};
@@ -1127,29 +1126,14 @@ int splat_predict(dms_model* m, const dms_pose_block* pose, const dms_camera* ca
   return DMS_OK;
 }
 
-// The project pass of splat_predict alone, into a CLEAN `zbuf` that a later splat_predict(..., resolve_only = 1) with the same
-// arguments resolves (and cleans): the same keys as a dual pass leaves in its second z-buffer for that cull - a cell's winner is
-// the minimum over the fragments that survive the cull, whatever else the pass feeds.  `rider`: see ProjectRider.
-int splat_project_only(dms_model* m, const dms_pose_block* pose, const dms_camera* cam, float maxDepth, float confThreshold, int time,
-                       int timeIdx, int maxTime, int timeDelta, int active, unsigned long long* zbuf, hipStream_t s, const ProjectRider* rider) {
-  DMS_REQUIRE(m && pose && cam && zbuf, "null argument");
-  DMS_REQUIRE(!m->pending_update, "a deferred update pass is still pending (index_map applies it)");
-  DMS_REQUIRE(timeIdx >= 0 && timeIdx < DMS_MAX_SENSORS, "timeIdx out of range");
-  DMS_REQUIRE(fabsf(cam->fx) > 1e-18f && fabsf(cam->fx) < 1e18f && fabsf(cam->fy) > 1e-18f && fabsf(cam->fy) < 1e18f && maxDepth > 1e-18f && maxDepth < 1e18f,
-              "focal lengths and depth cut-off must be finite, non-zero and within 1e-18 .. 1e18");
-  DMS_REQUIRE(!rider || (rider->mirror_words >= 0 && rider->mirror_words <= 256 && rider->copy_words >= 0 && rider->copy_words <= 256 &&
-                         (rider->mirror_words == 0 || (rider->mirror_src && rider->mirror_dst)) &&
-                         (rider->copy_words == 0 || (rider->copy_src && rider->copy_dst))),
-              "a rider copies at most 256 dwords (one block)");
+int splat_project_only(dms_model* m, const MapPass& pass, unsigned long long* zbuf, const ProjectRider& rider, hipStream_t s) {
+  DMS_REQUIRE(m && zbuf, "null argument");
+  if (int rc = check_map_pass(m, pass, rider)) return rc;
   ProjArgs a;
-  fill_proj(a, m, pose, cam, maxDepth, time, timeIdx, timeDelta);
-  a.confThreshold = confThreshold;
-  a.maxTime = maxTime;
-  a.actv = active ? 1 : 0;
-  const SplatSecond b2 = {0.f, 0, 0};
-  const ProjectRider no_rider = {nullptr, nullptr, 0, nullptr, nullptr, 0};
+  fill_proj(a, m, pass);
+  const SplatSecond no_second = {0.f, 0, 0};
   hipLaunchKernelGGL(k_splat_project<false>, dim3(surfel_grid(m->count_upper)), dim3(256), 0, s, a, m->buf[m->cur], m->cap, m->d_count, zbuf,
-                     b2, (unsigned long long*)nullptr, rider ? *rider : no_rider);
+                     no_second, (unsigned long long*)nullptr, rider);
   DMS_CHECK_LAUNCH();
   return DMS_OK;
 }

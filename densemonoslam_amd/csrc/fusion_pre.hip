@@ -301,8 +301,10 @@ int depth_metric(const dms_image2d* src, dms_image2d* dst, float maxD, hipStream
 }
 
 // the argument block of the fill-in for `ex` -> `out` (shared with the prediction's fused resolve pass)
-int fill_args(const dms_predict_out* ex, const dms_image2d* depth, const dms_image2d* rgba, const dms_camera* cam, int pass_geom, int pass_rgb,
-              dms_predict_out* out, const void* mirror_src, void* mirror_dst, int mirror_bytes, int* dense_flag, FillArgs* res) {
+int fill_args(const FillInputs& in, FillArgs* res) {
+  const dms_predict_out *const ex = in.ex, *const out = in.out;
+  const dms_image2d *const depth = in.depth, *const rgba = in.rgba;
+  const dms_camera* const cam = in.cam;
   DMS_REQUIRE(ex && depth && rgba && cam && out, "null argument");
   DMS_REQUIRE(dense(&ex->vertex, 16) && dense(&ex->normal, 16) && dense(&ex->image, 4) && dense(depth, 2) && dense(rgba, 4) &&
                   dense(&out->vertex, 16) && dense(&out->normal, 16) && dense(&out->image, 4),
@@ -322,13 +324,13 @@ int fill_args(const dms_predict_out* ex, const dms_image2d* depth, const dms_ima
   a.cy = cam->cy;
   a.ifx = 1.0f / cam->fx;
   a.ify = 1.0f / cam->fy;
-  a.pass_geom = pass_geom ? 1 : 0;
-  a.pass_rgb = pass_rgb ? 1 : 0;
-  DMS_REQUIRE(mirror_bytes % 4 == 0 && mirror_bytes / 4 <= BX * BY, "mirror block too large");
-  a.mirror_src = (const unsigned*)mirror_src;
-  a.mirror_dst = (unsigned*)mirror_dst;
-  a.mirror_words = (mirror_src && mirror_dst) ? mirror_bytes / 4 : 0;
-  a.dense_flag = dense_flag;
+  a.pass_geom = in.pass_geom ? 1 : 0;
+  a.pass_rgb = in.pass_rgb ? 1 : 0;
+  DMS_REQUIRE(in.mirror.bytes % 4 == 0 && in.mirror.bytes / 4 <= BX * BY, "mirror block too large");
+  a.mirror_src = (const unsigned*)in.mirror.src;
+  a.mirror_dst = (unsigned*)in.mirror.dst;
+  a.mirror_words = (in.mirror.src && in.mirror.dst) ? in.mirror.bytes / 4 : 0;
+  a.dense_flag = in.dense_flag;
   a.rows_blocks = 0;
   a.dense_cnt = nullptr;
   a.sample_mask = nullptr;
@@ -343,14 +345,12 @@ int fill_args(const dms_predict_out* ex, const dms_image2d* depth, const dms_ima
   return DMS_OK;
 }
 
-int fill_in(const dms_predict_out* ex, const dms_image2d* depth, const dms_image2d* rgba, const dms_camera* cam, int pass_geom,
-            int pass_rgb, dms_predict_out* out, hipStream_t s, const void* mirror_src, void* mirror_dst, int mirror_bytes, int* dense_flag) {
-  FillArgs a;
-  const int rc = fill_args(ex, depth, rgba, cam, pass_geom, pass_rgb, out, mirror_src, mirror_dst, mirror_bytes, dense_flag, &a);
-  if (rc) return rc;
+// the stand-alone launch over what fill_args built
+int fill_in(const FillArgs& args, hipStream_t s) {
+  FillArgs a = args;
   dim3 b(BX, BY), g = grid2d(a.cols, a.rows, b);
   a.rows_blocks = (int)g.y;
-  if (dense_flag) g.y += 1;
+  if (a.dense_flag) g.y += 1;
   hipLaunchKernelGGL(k_fill_in, g, b, 0, s, a);
   DMS_CHECK_LAUNCH();
   return DMS_OK;

@@ -615,25 +615,25 @@ int pyrDownUcharGauss(const dms_image2d* src, dms_image2d* dst, hipStream_t s) {
   return DMS_OK;
 }
 
-int modelPyramidFused(const void* vA, const void* nA, const void* iA, const void* vB, const void* nB, const void* iB, const int* flag_dev,
-                      int force_b_img, const float* pose16_dev, dms_image2d* vmaps, dms_image2d* nmaps, dms_image2d* depths,
-                      dms_image2d* images, float cutOff, hipStream_t s, bool skip_last_step, const unsigned* dense_cnt, int dense_samples,
-                      int* flag_out, const TrackInitArgs* init) {
-  DMS_REQUIRE(vA && nA && iA && vB && nB && iB && flag_dev && vmaps && nmaps && depths && images, "null argument");
+int modelPyramidFused(const ModelSources& src, const ModelTargets& dst, const ModelPyramidOpts& opt, hipStream_t s) {
+  dms_image2d *const vmaps = dst.vmaps, *const nmaps = dst.nmaps, *const depths = dst.depths, *const images = dst.images;
+  DMS_REQUIRE(src.a.vertex && src.a.normal && src.a.image && src.b.vertex && src.b.normal && src.b.image && src.use_b && vmaps && nmaps && depths &&
+                  images,
+              "null argument");
   ModelSrc m;
-  m.vA = (const float4*)vA;
-  m.nA = (const float4*)nA;
-  m.iA = (const uchar4*)iA;
-  m.vB = (const float4*)vB;
-  m.nB = (const float4*)nB;
-  m.iB = (const uchar4*)iB;
-  m.flag = flag_dev;
-  m.dense_cnt = dense_cnt;
-  m.dense_samples = dense_samples;
-  m.flag_out = flag_out;
-  DMS_REQUIRE(!dense_cnt || (flag_out && dense_samples > 0), "dense counters need a flag destination");
-  m.force_b_img = force_b_img;
-  m.pose16 = pose16_dev;
+  m.vA = (const float4*)src.a.vertex;
+  m.nA = (const float4*)src.a.normal;
+  m.iA = (const uchar4*)src.a.image;
+  m.vB = (const float4*)src.b.vertex;
+  m.nB = (const float4*)src.b.normal;
+  m.iB = (const uchar4*)src.b.image;
+  m.flag = src.use_b;
+  m.dense_cnt = opt.dense_cnt;
+  m.dense_samples = opt.dense_samples;
+  m.flag_out = opt.flag_out;
+  DMS_REQUIRE(!opt.dense_cnt || (opt.flag_out && opt.dense_samples > 0), "dense counters need a flag destination");
+  m.force_b_img = src.force_b_img;
+  m.pose16 = src.pose16;
   const int rows0 = vmaps[0].rows / 3, cols0 = vmaps[0].cols;
   const int rows1 = vmaps[1].rows / 3, cols1 = vmaps[1].cols, rows2 = vmaps[2].rows / 3, cols2 = vmaps[2].cols;
   DMS_REQUIRE(rows1 == rows0 / 2 && cols1 == cols0 / 2 && rows2 == rows1 / 2 && cols2 == cols1 / 2, "pyramid shapes");
@@ -643,14 +643,14 @@ int modelPyramidFused(const void* vA, const void* nA, const void* iA, const void
                gs = grid2d(depths[1].cols, depths[1].rows, b);
     TrackInitArgs ti;
     memset(&ti, 0, sizeof(ti));
-    if (init) ti = *init;
+    if (opt.init) ti = *opt.init;
     hipLaunchKernelGGL(k_model_levels012, dim3(ti.blocks + g0.x * g0.y + g12.x * g12.y + gs.x * gs.y), b, 0, s, m, (int)g0.x, (int)g0.y, (int)g12.x, rows0,
-                       cols0, view<float>(&vmaps[0]), view<float>(&nmaps[0]), view<float>(&depths[0]), view<unsigned char>(&images[0]), cutOff,
+                       cols0, view<float>(&vmaps[0]), view<float>(&nmaps[0]), view<float>(&depths[0]), view<unsigned char>(&images[0]), dst.cutOff,
                        rows1, cols1, rows2, cols2, view<float>(&vmaps[1]), view<float>(&nmaps[1]), view<float>(&vmaps[2]),
                        view<float>(&nmaps[2]), (int)g12.y, (int)gs.x, view<float>(&depths[1]), view<unsigned char>(&images[1]), ti);
     DMS_CHECK_LAUNCH();
   }
-  for (int l = 2; l < 3 && !skip_last_step; ++l)  // (skipped: the caller runs that step inside a kernel of its own)
+  for (int l = 2; l < 3 && !opt.skip_last_step; ++l)  // (skipped: the caller runs that step inside a kernel of its own)
     LAUNCH2D(k_model_pyr_step, depths[l].cols, depths[l].rows, s, view<const float>(&depths[l - 1]), view<float>(&depths[l]),
              view<const unsigned char>(&images[l - 1]), view<unsigned char>(&images[l]));
   return DMS_OK;

@@ -114,10 +114,20 @@ int dms_refframe_refine(dms_refframe* r, dms_model* map, const float* recoveryPo
   const float cutoff = (float)depthCutoff;
   if ((rc = ::dms::model_flush_pending(map, s))) return rc;
   if ((rc = dms_pose_block_set(r->pose, recoveryPose16, st))) return rc;
-  // 1. :72-80 (time = 0, the querying camera's time slot, maxTime = its tick)
-  if ((rc = ::dms::splat_predict(map, r->pose, &r->cam, cutoff, confidenceThreshold, 0, timeIdx, maxTime, timeDelta, 0, r->zbuf, &r->old,
-                                 nullptr, 1, s)))
-    return rc;
+  // 1. :72-80 (time = 0 and not ACTIVE, as the record starts; the querying camera's time slot, maxTime = its tick)
+  ::dms::MapPass pass;
+  pass.pose = r->pose;
+  pass.cam = &r->cam;
+  pass.maxDepth = cutoff;
+  pass.timeIdx = timeIdx;
+  pass.timeDelta = timeDelta;
+  pass.confThreshold = confidenceThreshold;
+  pass.maxTime = maxTime;
+  ::dms::SplatPrediction view;
+  view.zbuf = r->zbuf;
+  view.zclean = 1;
+  view.out = &r->old;
+  if ((rc = ::dms::splat_predict(map, pass, view, s))) return rc;
   // 2. :82-86, in the reference's literal order: initICPModel, initICP, initRGBModel, initRGB.  It is NOT the order its own WARNING
   // asks for (ElasticFusion.cpp:172: "initICP* must be called before initRGB*" pairwise; the model-to-model tracker calls
   // initICPModel, initRGBModel, initICP, initRGB, :410-418): populateRGBDData takes the depth of a pyramid from vmaps_tmp, which

@@ -27,24 +27,24 @@ struct ProjArgs {
   int xcd;  // XCD-aware block order of the per-pixel passes (common.hpp xcd_block)
 };
 
-static inline void fill_proj(ProjArgs& a, const dms_model* m, const dms_pose_block* pose, const dms_camera* cam, float maxDepth, int time,
-                             int timeIdx, int timeDelta) {
-  a.pose = pose;
-  a.cx = cam->cx;
-  a.cy = cam->cy;
-  a.fx = cam->fx;
-  a.fy = cam->fy;
+// (the index-map kernels read none of the splat-only fields)
+static inline void fill_proj(ProjArgs& a, const dms_model* m, const MapPass& p) {
+  a.pose = p.pose;
+  a.cx = p.cam->cx;
+  a.cy = p.cam->cy;
+  a.fx = p.cam->fx;
+  a.fy = p.cam->fy;
   a.cols = m->width;
   a.rows = m->height;
   a.colsf = (float)m->width;
   a.rowsf = (float)m->height;
-  a.maxDepth = maxDepth;
-  a.time = time;
-  a.timeIdx = timeIdx;
-  a.timeDelta = timeDelta;
-  a.confThreshold = 0.f;
-  a.maxTime = 0;
-  a.actv = 0;
+  a.maxDepth = p.maxDepth;
+  a.time = p.time;
+  a.timeIdx = p.timeIdx;
+  a.timeDelta = p.timeDelta;
+  a.confThreshold = p.confThreshold;
+  a.maxTime = p.maxTime;
+  a.actv = p.active ? 1 : 0;
   a.transposed = 0;
   a.xcd = xcd_remap_enabled();
 }
@@ -83,10 +83,7 @@ __device__ __forceinline__ bool splat_culled(const ProjArgs& a, const f3& ph, fl
                                     (vt != -3.f && (float)time - vt > (float)a.timeDelta) || vt > (float)maxTime);
 }
 
-struct SplatSecond {  // second prediction sharing the project pass (same map, pose, depth range and mode)
-  float confThreshold;
-  int time, maxTime;
-};
+// (SplatSecond, the second prediction sharing the project pass: internal.hpp)
 
 // vertex stage, first half: the cull and the clip, from position, confidence and time alone.  `pass`: bit 0 = survives the cull
 // of `a`, bit 1 = survives the cull of `b` (when given).  False when the surfel is culled / clipped.

@@ -2903,15 +2903,16 @@ int odometry_model_views_begin(dms_odometry* o, const TrackFold* fold, ModelMapV
 // initICPModel + initRGBModel of the frame step in four launches (prep.hip, modelPyramidFused).
 // The operator-layer staging copy vmaps_tmp is not written on this path; nextDepth is aliased to
 // lastDepth by the caller, so nothing reads it.
-// defer_last_step: the pyramid's last step is left to the first kernel of the NEXT odometry_track_enqueue on this object
+// next.defer_last_step: the pyramid's last step is left to the first kernel of the NEXT odometry_track_enqueue on this object
 // (k_track_init_pyr), which the caller must enqueue on the same stream before anything else reads level 2 of lastDepth / lastImage
-// fold: the set-up of the NEXT odometry_track_enqueue on this object (prior = the pose block fold->prior_pose16, the given
+// next.fold: the set-up of the NEXT odometry_track_enqueue on this object (prior = the pose block fold->prior_pose16, the given
 // so3 / pyramid / fastOdom switches) runs as a block group of the pyramid kernel; that call must follow on the same stream
 // with the same arguments.  Taken only where the call's first launch is the resident SO3 level (which then carries the
 // deferred pyramid step); otherwise ignored.
-int odometry_initModel_fused(dms_odometry* o, const void* vA, const void* nA, const void* iA, const void* vB, const void* nB,
-                             const void* iB, const int* flag_dev, int force_b_img, const float* pose16_dev, hipStream_t s,
-                             int defer_last_step, unsigned* dense_cnt, int dense_samples, const TrackFold* fold) {
+int odometry_initModel_fused(dms_odometry* o, const ModelSources& src, const ModelHandOver& next, hipStream_t s) {
+  const int defer_last_step = next.defer_last_step;
+  unsigned* const dense_cnt = next.dense_cnt;
+  const TrackFold* const fold = next.fold;
   dms_image2d v[DMS_NUM_PYRS], n[DMS_NUM_PYRS], d[DMS_NUM_PYRS], im[DMS_NUM_PYRS];
   for (int i = 0; i < DMS_NUM_PYRS; ++i) {
     v[i] = o->vmaps_g_prev[i].img();
@@ -2919,7 +2920,7 @@ int odometry_initModel_fused(dms_odometry* o, const void* vA, const void* nA, co
     d[i] = o->lastDepth[i].img();
     im[i] = o->lastImage[i].img();
   }
-  // dense_cnt: the source choice comes from the 16 counters of the prediction's resolve pass instead of *flag_dev, which then
+  // dense_cnt: the source choice comes from the 16 counters of the prediction's resolve pass instead of *src.use_b, which then
   // receives the decision; the next odometry_track_enqueue on this object zeroes the counters
   DMS_REQUIRE(!dense_cnt || defer_last_step, "dense counters are zeroed by the track call that takes the deferred pyramid step");
   TrackInitArgs ti;
@@ -2931,14 +2932,24 @@ int odometry_initModel_fused(dms_odometry* o, const void* vA, const void* nA, co
     nc.kind = dms_odometry::NextCall::deferred_pyr;
   nc.dense_cnt_zero = dense_cnt;
   o->next_call = nc;
-  return modelPyramidFused(vA, nA, iA, vB, nB, iB, flag_dev, force_b_img, pose16_dev, v, n, d, im, o->maxDepthRGB, s, defer_last_step != 0, dense_cnt,
-                           dense_samples, const_cast<int*>(flag_dev), nc.kind == dms_odometry::NextCall::folded ? &ti : nullptr);
+  ModelPyramidOpts opt;
+  opt.skip_last_step = defer_last_step != 0;
+  opt.dense_cnt = dense_cnt;
+  opt.dense_samples = next.dense_samples;
+  opt.flag_out = const_cast<int*>(src.use_b);
+  if (nc.kind == dms_odometry::NextCall::folded) opt.init = &ti;
+  ModelTargets dst;
+  dst.vmaps = v;
+  dst.nmaps = n;
+  dst.depths = d;
+  dst.images = im;
+  dst.cutOff = o->maxDepthRGB;
+  return modelPyramidFused(src, dst, opt, s);
 }
 
 // initICP(vertex map, normal map) + initRGB(image) of the live side in the fused form (RGBDOdometry.cpp:118-137,
 // :162-191 through populateRGBDData): no transform, nextDepth from the same vertex map, then the Sobel / gate pyramid
-int odometry_initLive_fused(dms_odometry* o, const void* verts, const void* norms, const void* rgba, const int* any_flag_dev,
-                            hipStream_t s) {
+int odometry_initLive_fused(dms_odometry* o, const ModelImages& live, const int* any_flag_dev, hipStream_t s) {
   dms_image2d v[DMS_NUM_PYRS], n[DMS_NUM_PYRS], d[DMS_NUM_PYRS], im[DMS_NUM_PYRS];
   for (int i = 0; i < DMS_NUM_PYRS; ++i) {
     v[i] = o->vmaps_curr[i].img();
@@ -2946,7 +2957,16 @@ int odometry_initLive_fused(dms_odometry* o, const void* verts, const void* norm
     d[i] = o->nextDepth[i].img();
     im[i] = o->nextImage[i].img();
   }
-  int rc = modelPyramidFused(verts, norms, rgba, verts, norms, rgba, any_flag_dev, 0, nullptr, v, n, d, im, o->maxDepthRGB, s);
+  ModelSources src;  // (one set: whatever the flag holds selects it)
+  src.a = src.b = live;
+  src.use_b = any_flag_dev;
+  ModelTargets dst;
+  dst.vmaps = v;
+  dst.nmaps = n;
+  dst.depths = d;
+  dst.images = im;
+  dst.cutOff = o->maxDepthRGB;
+  int rc = modelPyramidFused(src, dst, ModelPyramidOpts{}, s);
   if (rc) return rc;
   return nextDerivatives(o, s);
 }
@@ -2959,7 +2979,13 @@ int dms_odometry_initModelFused(dms_odometry* o, const void* vertA, const void* 
                                 const void* normB, const void* rgbaB, const int* use_b_dev, int force_b_image,
                                 const float* modelPose16_dev, dms_stream s) {
   DMS_REQUIRE(o, "null odometry");
-  return odometry_initModel_fused(o, vertA, normA, rgbaA, vertB, normB, rgbaB, use_b_dev, force_b_image, modelPose16_dev, (hipStream_t)s, 0, nullptr, 0, nullptr);
+  ModelSources src;
+  src.a = {vertA, normA, rgbaA};
+  src.b = {vertB, normB, rgbaB};
+  src.use_b = use_b_dev;
+  src.force_b_img = force_b_image;
+  src.pose16 = modelPose16_dev;
+  return odometry_initModel_fused(o, src, ModelHandOver{}, (hipStream_t)s);
 }
 
 int dms_odometry_fetch_result(dms_odometry* o, dms_track_result* r, dms_stream st) {
